@@ -7,7 +7,12 @@ One "step" = one LiDAR frame = the reference's per-frame sequence (MeshProjector
 updateGeometry(every mesh) + commitScene (vertex transform + full BVH rebuild) + traceScene
 (ray generation + closest hit + point packing), with the mesh already resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+  A plain run sets up, primes and warms up, times exactly K frames in one window (ms_per_step = that window / K), and prints
+  the line.  --full adds everything else the line can carry: the roofline (its own counting frame and a pass that times the
+  dominant kernel), windows of 1000, one frame in flight, the stage breakdown, the drop-in legs, the CPU baseline, the other
+  configurations (also_measured) and, with N > 1, the other splits.  --dump-outputs DIR writes what the timed path returned
+  in its last step (the cloud and its hit records) as DIR/<name>.npy, before anything --full adds runs.
   N > 1: one rank per GPU over RCCL, either launched by the driver through torch.distributed.run (RANK / WORLD_SIZE in
   the environment) or -- when WORLD_SIZE is not set -- by this script itself, which then starts
   `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process BEFORE anything here touches a
@@ -52,8 +57,14 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--min-ms", type=float, default=50.0,
-                    help="keep timing windows of --steps frames until this much has been timed; the median window is reported")
+    ap.add_argument("--min-ms", type=float, default=0.0,
+                    help="keep timing windows of --steps frames until this much has been timed; the median window is reported "
+                         "(0, the default: one window, exactly --steps timed frames)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the headline (roofline, kernel timings, long windows, one frame in "
+                         "flight, stage breakdown, drop-in legs, CPU baseline, also_measured, the other N > 1 splits)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's cloud and hit records as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--prime-ms", type=int, default=50,
                     help="untimed frames for this long before the W warm-up steps (clocks, caches)")
     ap.add_argument("--no-pipeline", action="store_true",
@@ -102,6 +113,41 @@ def parse_args():
     ap.add_argument("--cpu-frames", type=int, default=6)
     ap.add_argument("--breakdown", action="store_true", help="extra pass with per-stage hipEvent timings")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, points32, hits16):
+    """The cloud a caller of the timed path receives -- n 32-byte PointCloud2 records (x, y, z f32, 0, intensity f32, ring i32, 0)
+    and n 16-byte hit records (ray, geomID, primID u32, t f32), ray-index order -- as one .npy per field: float32 where the
+    field is a float, float64 where it is an integer (exact).  Beyond DUMP_LIMIT_BYTES in all, a fixed, seeded sample of the
+    records is written (sorted, so the order stays ray order) and `sample_index` says which."""
+    points32, hits16 = np.ascontiguousarray(points32), np.ascontiguousarray(hits16)   # ([n, 32] / [n, 4] or flat bytes)
+    n = points32.nbytes // 32
+    assert hits16.nbytes == 16 * n, (points32.nbytes, hits16.nbytes)
+    pts = np.frombuffer(points32.tobytes(), dtype=np.dtype([("xyz", "<f4", 3), ("pad0", "<u4"), ("intensity", "<f4"),
+                                                            ("ring", "<i4"), ("pad1", "<u4", 2)]), count=n)
+    hits = np.frombuffer(hits16.tobytes(), dtype=capi.HIT_DTYPE, count=n)
+    per_record = 4 * 3 + 4 + 8 + 8 * 3 + 4
+    sel = None
+    if n * per_record > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (per_record + 8)
+        sel = np.sort(np.random.default_rng(12345).choice(n, size=keep, replace=False))
+        pts, hits = pts[sel], hits[sel]
+    arrays = {"n_points": np.array([n], np.float64),
+              "points_xyz": pts["xyz"].astype(np.float32), "points_intensity": pts["intensity"].astype(np.float32),
+              "points_ring": pts["ring"].astype(np.float64),
+              "hits_ray": hits["ray"].astype(np.float64), "hits_geom": hits["geom"].astype(np.float64),
+              "hits_prim": hits["prim"].astype(np.float64), "hits_t": hits["t"].astype(np.float32)}
+    if sel is not None:
+        arrays["sample_index"] = sel.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    if sel is None and os.path.exists(os.path.join(out_dir, "sample_index.npy")):   # (an earlier, sampled dump's)
+        os.remove(os.path.join(out_dir, "sample_index.npy"))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "points": n, "sampled": sel is not None, "files": sorted(arrays)}
 
 
 def build_workload(name, rank=0):
@@ -496,6 +542,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: be the launcher (before any GPU call), never a silent one-GPU run
         raise SystemExit(spawn_ranks(args))
@@ -538,6 +586,8 @@ def main():
     # LS_BENCH_REHEARSAL=1: several ranks share GPU 0 over gloo -- only to rehearse the N > 1 code path on
     # a one-GPU box (RCCL refuses two ranks on one device); never used for a reported number
     rehearsal = os.environ.get("LS_BENCH_REHEARSAL") == "1"
+    if args.dump_outputs and world > 1 and args.multi == "sharded" and (rehearsal or args.multi_driver == "torch"):
+        raise SystemExit("--dump-outputs: not available for the torch.distributed driver's sharded split (use --multi-driver c)")
     # LS_BENCH_SHIM=1 (tests/test_gpu_group_shim.py): the ranks share GPU 0 too, but the frames go through the C group driver
     # like on a real node -- its collectives on tests/shim/librccl_shim.so (LS_GROUP_RCCL_LIBRARY), torch.distributed's control
     # plane on gloo.  Every phase of the N > 1 flow meets a real peer; the line is labelled and is never a number to quote.
@@ -564,12 +614,12 @@ def main():
     force_group = world == 1 and os.environ.get("LS_BENCH_FORCE_GROUP") == "1"
     if (world == 1 and not force_group) or args.workload == "cfg5":
         t_start = time.monotonic()
-        out = measure(args, rank, world, device, dev_index, rehearsal, None)
+        out = measure(args, rank, world, device, dev_index, rehearsal, None, dump=args.dump_outputs)
         # the other configurations under the driver's own clock, next to the headline -- the BVH engine
         # `north_star` names (poses only, and with the reference's build-per-frame), SYN-10M, configs[4] as one GPU runs it.
         # Lean passes of the same measure(): the timed windows and the dominant kernel's own duration, nothing else; skipped when
-        # the headline run already took long (the default run stays within minutes).
-        if world == 1 and args.workload == "syn128x1m" and args.engine in ("auto", "projection") and not args.no_also and not args.reregister:
+        # the headline run already took long (the --full run stays within minutes).
+        if args.full and world == 1 and args.workload == "syn128x1m" and args.engine in ("auto", "projection") and not args.no_also and not args.reregister:
             also, budget_s = [], float(os.environ.get("LS_BENCH_ALSO_BUDGET_S", "240"))
             for label, changes in (("bvh_poses_only", {"engine": "bvh"}),
                                    ("bvh_rebuild_every_frame", {"engine": "bvh", "bvh_rebuild": True}),
@@ -581,6 +631,7 @@ def main():
                 extra = argparse.Namespace(**vars(args))
                 extra.lean, extra.no_cpu_baseline, extra.no_dropin, extra.breakdown = True, True, True, False
                 extra.steps = max(args.steps, 20)
+                extra.min_ms = args.min_ms or 50.0
                 for k, v in changes.items():
                     setattr(extra, k, v)
                 try:
@@ -618,8 +669,27 @@ def main():
                 store = None
         dog = Watchdog(result_fd, rank, store)
         limit = float(os.environ.get("LS_BENCH_WATCHDOG_S", "240"))
+        if not args.full:   # the split the line reports, nothing else
+            dog.arm("frames interleaved over the ranks" if args.multi == "interleaved" else "azimuth shards + all-gather, " + args.workload, limit)
+            try:
+                out = measure(args, rank, world, device, dev_index, rehearsal, args.multi, force_group=force_group, dump=args.dump_outputs)
+            except (Exception, SystemExit) as e:
+                dog.failed(e)
+            dog.disarm()
+            if rank == 0:
+                sys.stdout.flush()
+                os.write(result_fd, (json.dumps(front_loaded(out)) + "\n").encode())
+            if world > 1:
+                dist.destroy_process_group()
+            return
+
+        def secondary(ns):   # the measurements besides `value` keep their windows of at least 50 ms
+            ns = argparse.Namespace(**vars(ns))
+            ns.min_ms = args.min_ms or 50.0
+            return ns
         dog.arm("frames interleaved over the ranks", limit)
-        inter = measure(args, rank, world, device, dev_index, rehearsal, "interleaved", force_group=force_group)
+        inter = measure(args if args.multi == "interleaved" else secondary(args), rank, world, device, dev_index, rehearsal, "interleaved",
+                        force_group=force_group, dump=args.dump_outputs if args.multi == "interleaved" else None)
         # The sharded split in two arrangements, the plain one first ("keep ONE_COMMUNICATOR as the default
         # until a run with two or more ranks exists" -- it is not the default, but it is what the line falls back on): one
         # communicator, the collective on a stream of its own behind an event, plain launches -- how RCCL is used
@@ -627,7 +697,7 @@ def main():
         # the frame one captured graph), whose multi-rank collectives inside a captured graph nobody has run yet.
         plain = None
         if args.multi_driver == "c" and not rehearsal and args.group_flags != 1:
-            safe = argparse.Namespace(**vars(args))
+            safe = secondary(args)
             safe.group_flags = 1
             dog.arm("azimuth shards + all-gather on one communicator, " + args.workload, limit, inter)
             try:
@@ -640,14 +710,15 @@ def main():
             fallback["also_measured"] = [brief(inter)]
         dog.arm("azimuth shards + all-gather" + (", per-set communicators and frame graphs, " if plain is not None else ", ") + args.workload, limit, fallback)
         try:
-            shard = measure(args, rank, world, device, dev_index, rehearsal, "sharded", force_group=force_group)
+            shard = measure(args if args.multi == "sharded" else secondary(args), rank, world, device, dev_index, rehearsal, "sharded",
+                            force_group=force_group, dump=args.dump_outputs if args.multi == "sharded" else None)
         except (Exception, SystemExit) as e:
             dog.failed(e)
         out, also = (shard, [brief(inter)]) if args.multi == "sharded" else (inter, [brief(shard)])
         if plain is not None:
             also.insert(0, brief(plain))
         if args.workload == "syn128x1m" and not rehearsal:
-            big = argparse.Namespace(**vars(args))
+            big = secondary(args)
             big.workload = "syn128x10m"
             partial = dict(out)
             partial["also_measured"] = list(also)
@@ -666,10 +737,12 @@ def main():
         dist.destroy_process_group()
 
 
-def measure(args, rank, world, device, dev_index, rehearsal, multi, force_group=False):
+def measure(args, rank, world, device, dev_index, rehearsal, multi, force_group=False, dump=None):
     """One measurement.  multi: None (single GPU, or cfg5's replicas), "sharded" (azimuth sectors + one all-gather of
     hit-record slots per frame: a frame's latency is what is split) or "interleaved" (rank g traces the whole raster of
-    frames f with f mod N == g, nothing is exchanged on the frame path: the stream's throughput is what is multiplied)."""
+    frames f with f mod N == g, nothing is exchanged on the frame path: the stream's throughput is what is multiplied).
+    Without args.full only the timed windows run; dump: a directory for the last timed frame's cloud (rank 0)."""
+    full = bool(getattr(args, "full", False))
     if multi and os.environ.get("LS_BENCH_DEBUG_STALL") == multi:   # (tests: what the watchdog does about a phase that hangs)
         time.sleep(1e6)
     if multi and os.environ.get("LS_BENCH_DEBUG_RAISE") == f"{multi}:{rank}":   # (tests: ... or that raises on one rank)
@@ -954,27 +1027,26 @@ def measure(args, rank, world, device, dev_index, rehearsal, multi, force_group=
             dist.barrier()
             torch.cuda.synchronize(device)
 
-    # ---- node / triangle visits per ray on this BVH (algorithmic bytes), outside the timed region
-    if engine == "bvh":   # (a big hierarchy's four-wide twins are made by the second frame that finds it unchanged: count on the walk that is timed)
-        for i in range(3):
-            frame(i)
+    # ---- node / triangle visits per ray on this BVH (algorithmic bytes), outside the timed region (--full)
+    points_sha = n_hits = None
+    if full:
+        if engine == "bvh":   # (a big hierarchy's four-wide twins are made by the second frame that finds it unchanged: count on the walk that is timed)
+            for i in range(3):
+                frame(i)
+            sync()
+        tr.setOption(capi.LS_OPT_COUNT_VISITS, 1)
+        frame(0)
         sync()
-    tr.setOption(capi.LS_OPT_COUNT_VISITS, 1)
-    frame(0)
-    sync()
-    n_node, n_tri, wave_trips, max_trips = tr.visitStats()
-    tr.setOption(capi.LS_OPT_COUNT_VISITS, 0)
+        n_node, n_tri, wave_trips, max_trips = tr.visitStats()
+        tr.setOption(capi.LS_OPT_COUNT_VISITS, 0)
+        if count_words is not None:
+            n_hits = int(count_words[0][:4].view(torch.int32).item())
+            if single:   # the frame's cloud (32-byte points, ray-index order): lsbench prints the same hash for the same scene
+                import hashlib
+                points_sha = hashlib.sha256(out_bufs[0][64:64 + 32 * n_hits].cpu().numpy().tobytes()).hexdigest()
+        else:   # C group: the slot's count word is the group's; the shard's dense result says how many of its rays hit
+            n_hits = int((tr.denseHits()[1] != 0xFFFFFFFF).sum())
     shard_rays = tr.getTotalRays()
-    points_sha = None
-    if count_words is not None:
-        n_hits = int(count_words[0][:4].view(torch.int32).item())
-        if single:   # the frame's cloud (32-byte points, ray-index order): lsbench prints the same hash for the same scene
-            import hashlib
-            points_sha = hashlib.sha256(out_bufs[0][64:64 + 32 * n_hits].cpu().numpy().tobytes()).hexdigest()
-    else:   # C group: the slot's count word is the group's; the shard's dense result says how many of its rays hit
-        n_hits = int((tr.denseHits()[1] != 0xFFFFFFFF).sum())
-    info = tr.sceneSize()
-    n_tris_total = info["n_tris"]
 
     # CPython's cyclic garbage collector runs a full (generation 2) collection some 700 frames into the run --
     # every frame allocates a few ctypes objects -- and with torch imported that pause is 30-40 ms, a thousand
@@ -1032,18 +1104,39 @@ def measure(args, rank, world, device, dev_index, rehearsal, multi, force_group=
     order = np.argsort([w[0] for w in wins])
     elapsed, enqueue_s = wins[int(order[len(order) // 2])]
     window_ms = sorted(w[0] * 1e3 for w in wins)
-    # ---- the dominant kernel's duration: the same K frames again, with hipEvents on the tracer's
-    #      stream bracketing that kernel only (recorded without synchronising, read after the loop)
-    tr.setOption(capi.LS_OPT_TIMING, 2)
-    tr.timings()
-    if stream_frames is not None:
-        stream_frames(0, args.steps)             # back to back, like the timed windows (the GPU stays busy)
-    else:
-        for i in range(args.steps):
-            frame(i)
-    sync()
-    tm = tr.timings()
-    tr.setOption(capi.LS_OPT_TIMING, 0)
+    info = tr.sceneSize()
+    n_tris_total = info["n_tris"]
+    # ---- what the last timed frame (K - 1) returned, before anything else runs on the handle
+    dumped = None
+    if dump:
+        sync()                                   # (two frames in flight: the last frame's finish + pack ride in the flush)
+        if single:
+            b = out_bufs[(args.steps - 1) % 3]
+            n_out = int(b[:4].view(torch.int32).item())
+            pts = b[64:64 + 32 * n_out].cpu().numpy()
+            hts = b[64 + 32 * cap:64 + 32 * cap + 16 * n_out].cpu().numpy()
+        elif cgroup:
+            pts, hts = grp.download(group_last_frame[0])
+            ray_order = np.argsort(hts[:, 0], kind="stable")   # (sector-major as gathered: in ray order, the one-GPU cloud's)
+            pts, hts = pts[ray_order], hts[ray_order]
+        else:   # (refused in main())
+            raise SystemExit("--dump-outputs: not available for the torch.distributed driver's sharded split")
+        if rank == 0:
+            dumped = dump_outputs(dump, pts, hts)
+    tm = None
+    if full:
+        # ---- the dominant kernel's duration: the same K frames again, with hipEvents on the tracer's
+        #      stream bracketing that kernel only (recorded without synchronising, read after the loop)
+        tr.setOption(capi.LS_OPT_TIMING, 2)
+        tr.timings()
+        if stream_frames is not None:
+            stream_frames(0, args.steps)             # back to back, like the timed windows (the GPU stays busy)
+        else:
+            for i in range(args.steps):
+                frame(i)
+        sync()
+        tm = tr.timings()
+        tr.setOption(capi.LS_OPT_TIMING, 0)
 
     def windows_of(fn, min_s=0.02):
         """median seconds per frame over windows of K frames, at least min_s timed (single rank only)"""
@@ -1066,7 +1159,7 @@ def measure(args, rank, world, device, dev_index, rehearsal, multi, force_group=
     #      launch's latency, the last frame's whole latency instead of a step, the runtime's bookkeeping inside the device-wide
     #      wait: ~70 us per window, 3.5 us per frame of a 20-frame window -- are amortised (never `value`)
     steady_s = None
-    if stream_frames is not None and world == 1:
+    if full and stream_frames is not None and world == 1:
         long_k = 1000
         res = []
         for _ in range(3):
@@ -1078,7 +1171,7 @@ def measure(args, rank, world, device, dev_index, rehearsal, multi, force_group=
         steady_s = float(np.median(res))
 
     latency_frame_s = None
-    if pipeline:
+    if full and pipeline:
         # the same K frames with one frame in flight: what a consumer that needs every frame before the next sees
         tr.setOption(capi.LS_OPT_PIPELINE, 0)
         latency_frame_s = windows_of(frame) if world == 1 else None
@@ -1092,7 +1185,7 @@ def measure(args, rank, world, device, dev_index, rehearsal, multi, force_group=
         tr.setOption(capi.LS_OPT_PIPELINE, args.pipeline)
 
     breakdown = None
-    if (args.breakdown or world == 1) and not replicas and not getattr(args, "lean", False):
+    if (args.breakdown or (full and world == 1)) and not replicas and not getattr(args, "lean", False):
         tr.setOption(capi.LS_OPT_TIMING, 1)
         tr.timings()
         for i in range(min(args.steps, 50)):
@@ -1112,7 +1205,7 @@ def measure(args, rank, world, device, dev_index, rehearsal, multi, force_group=
     #      for every mesh updateGeometry(name, translation, rotation, pcl::PolygonMesh::Ptr&) + commitScene() +
     #      traceScene(frame) filling a sensor_msgs::PointCloud2 in host memory (MeshProjector.cpp:446-464).
     dropin = None
-    if world == 1 and not replicas and engine == "projection" and not args.no_dropin and not getattr(args, "lean", False):
+    if full and world == 1 and not replicas and engine == "projection" and not args.no_dropin and not getattr(args, "lean", False):
         import tempfile
         from lidarshooter_amd import adapterapi
         cfg = synth.write_sensor_json(os.path.join(DATA, "config", "hesai-pandar-XT-32-lidar_0000.json"),
@@ -1181,91 +1274,106 @@ def measure(args, rank, world, device, dev_index, rehearsal, multi, force_group=
     total_rays = V * H * (world if independent else 1)
     ms_per_step = elapsed / args.steps * 1e3
     value = total_rays * args.steps / elapsed / 1e6
-    trace_ms = tm["trace"]
-    if engine == "bvh":
-        # k_trace: 64 B per node fetch + 48 B per triangle test + 8 B per ray written
-        kernel = "k_trace_inst" if tr.info(capi.LS_INFO_BVH_INSTANCED) else "k_trace"
-        wide_walk = bool(tr.info(capi.LS_INFO_BVH_WIDE))
-        node_bytes = 2 * NODE_BYTES if wide_walk else NODE_BYTES   # (a four-wide node is 128 bytes: four boxes + four references)
-        b_launch = RAY_OUT_BYTES * shard_rays + node_bytes * n_node + TRI_BYTES * n_tri
-        b_frame = None
-        units = {"rays_per_launch": shard_rays, "bytes_per_ray": b_launch / shard_rays,
-                 "nodes_per_ray": n_node / shard_rays, "tris_per_ray": n_tri / shard_rays, "node_bytes": node_bytes,
-                 "walk": "four-wide nodes (k_widen: a node's slots are its grandchildren)" if wide_walk else "binary nodes",
-                 "wave_trips_mean": wave_trips / max(1, (shard_rays + 63) // 64), "wave_trips_max": max_trips}
-    else:
-        # k_project: every triangle is streamed once (12 B indices + 36 B vertex gather) and every hit folds 8 B into
-        # the per-ray key; the angle tables (V+H entries) stay on chip.  With group culling in effect
-        # (LS_OPT_BLOCK_CULL; the timed stage is then k_cull + k_project) the triangles of culled groups are never read:
-        # the bytes are the bounds k_cull reads (32 B per 256-triangle block, 32 B per group of 4 inside the blocks that
-        # survive), the survivor list (4 B written + 4 B read per surviving group) and 48 B per SURVIVING triangle
-        kernel = "k_project"
-        groups_alive, group_bounds_read = int(wave_trips), int(max_trips)
-        culled = groups_alive > 0
-        if culled:
-            n_blocks = sum(((t.shape[0] + 3) // 4 + 63) // 64 for _, _, t in meshes if t.shape[0] >= 524288)
-            tris_read = min(4 * groups_alive, n_tris_total) + sum(t.shape[0] for _, _, t in meshes if t.shape[0] < 524288)
-            b_launch = 32 * n_blocks + 32 * group_bounds_read + 8 * groups_alive + 48 * tris_read + 8 * n_hits
-            kernel = "k_cull + k_project"
+    roofline = None
+    if full:
+        trace_ms = tm["trace"]
+        if engine == "bvh":
+            # k_trace: 64 B per node fetch + 48 B per triangle test + 8 B per ray written
+            kernel = "k_trace_inst" if tr.info(capi.LS_INFO_BVH_INSTANCED) else "k_trace"
+            wide_walk = bool(tr.info(capi.LS_INFO_BVH_WIDE))
+            node_bytes = 2 * NODE_BYTES if wide_walk else NODE_BYTES   # (a four-wide node is 128 bytes: four boxes + four references)
+            b_launch = RAY_OUT_BYTES * shard_rays + node_bytes * n_node + TRI_BYTES * n_tri
+            b_frame = None
+            units = {"rays_per_launch": shard_rays, "bytes_per_ray": b_launch / shard_rays,
+                     "nodes_per_ray": n_node / shard_rays, "tris_per_ray": n_tri / shard_rays, "node_bytes": node_bytes,
+                     "walk": "four-wide nodes (k_widen: a node's slots are its grandchildren)" if wide_walk else "binary nodes",
+                     "wave_trips_mean": wave_trips / max(1, (shard_rays + 63) // 64), "wave_trips_max": max_trips}
         else:
-            tris_read = n_tris_total
-            b_launch = 48 * n_tris_total + 8 * n_hits
-        # the whole frame: + k_project_finish (8 B key read per ray) + k_pack (8 B key read + 8 B re-arm per ray,
-        # 48 B point + hit record per hit)
-        b_frame = b_launch + 24 * shard_rays + 48 * n_hits
-        units = {"triangles_per_launch": n_tris_total, "triangles_read_per_launch": tris_read,
-                 "bytes_per_triangle": b_launch / max(1, n_tris_total),
-                 "candidate_tests_per_launch": n_tri, "tests_per_triangle": n_tri / max(1, n_tris_total),
-                 "rays_per_launch": shard_rays,
-                 "nominal_bytes_per_launch": 48 * n_tris_total + 8 * n_hits}
-        if culled:
-            units["cull"] = {"blocks_of_256": n_blocks, "group_bounds_read": group_bounds_read, "groups_surviving": groups_alive,
-                             "what": "bytes are priced on what the culled stage has to read: 32 B per block bound, 32 B per group bound "
-                                     "inside surviving blocks, 8 B per surviving group (list), 48 B per surviving triangle, 8 B per hit"}
-    achieved = b_launch / (trace_ms * 1e-3) / 1e9 if trace_ms > 0 else 0.0
-    # HBM bytes of that kernel from the committed rocprofv3 PMC passes (FETCH_SIZE x2 + WRITE_SIZE, KiB).  Counters cannot
-    # be collected from inside this process, so the figure is the profiled one -- and only if the profile was taken
-    # from these very kernel sources (its recorded source hash equals the current one)
-    traffic, traffic_src = None, None
-    sha = kernel_source_sha()
-    prof = os.path.join(ROOT, "profiles", f"{PROFILE_TAG}_{engine}_hbm.json")
-    if args.workload == "syn128x1m" and world == 1 and os.path.exists(prof):  # only the profiled configuration
-        try:
-            pj = json.load(open(prof))
-            if pj.get("kernel_source_sha") != sha:
-                traffic_src = f"{os.path.relpath(prof, ROOT)} is stale (taken from kernel sources {pj.get('kernel_source_sha')}, these are {sha}): not reported"
+            # k_project: every triangle is streamed once (12 B indices + 36 B vertex gather) and every hit folds 8 B into
+            # the per-ray key; the angle tables (V+H entries) stay on chip.  With group culling in effect
+            # (LS_OPT_BLOCK_CULL; the timed stage is then k_cull + k_project) the triangles of culled groups are never read:
+            # the bytes are the bounds k_cull reads (32 B per 256-triangle block, 32 B per group of 4 inside the blocks that
+            # survive), the survivor list (4 B written + 4 B read per surviving group) and 48 B per SURVIVING triangle
+            kernel = "k_project"
+            groups_alive, group_bounds_read = int(wave_trips), int(max_trips)
+            culled = groups_alive > 0
+            if culled:
+                n_blocks = sum(((t.shape[0] + 3) // 4 + 63) // 64 for _, _, t in meshes if t.shape[0] >= 524288)
+                tris_read = min(4 * groups_alive, n_tris_total) + sum(t.shape[0] for _, _, t in meshes if t.shape[0] < 524288)
+                b_launch = 32 * n_blocks + 32 * group_bounds_read + 8 * groups_alive + 48 * tris_read + 8 * n_hits
+                kernel = "k_cull + k_project"
             else:
-                k = pj["kernels"]
-                # the timed variant: template argument COUNT (the first one) is false
-                key = next((n for n in k if n.split("<")[0] == kernel and not n.split("<")[-1].startswith("true")), None)
-                if key:
-                    traffic, traffic_src = k[key]["hbm_bytes_per_launch"], os.path.relpath(prof, ROOT)
-        except Exception:
-            pass
-    # What binds the kernel besides bytes (SURVEY.md 8d "secondary ceilings"): the committed SQ / TCC counter summary of the same
-    # kernel sources (tools/sq_profile.sh -> profiles/<tag>_<engine>_sq.json), same staleness rule as `traffic`
-    secondary = None
-    sq = os.path.join(ROOT, "profiles", f"{PROFILE_TAG}_{engine}_sq.json")
-    if args.workload == "syn128x1m" and world == 1 and os.path.exists(sq):
-        try:
-            sj = json.load(open(sq))
-            if sj.get("kernel_source_sha") != sha:
-                secondary = {"source": f"{os.path.relpath(sq, ROOT)} is stale (taken from kernel sources {sj.get('kernel_source_sha')}, these are {sha}): not reported"}
-            else:
-                key = next((n for n in sj["kernels"] if n.split("<")[0] == kernel and not n.split("<")[-1].startswith("true")), None)
-                if key:
-                    d = sj["kernels"][key]["derived"]
-                    secondary = {"issue_frac": d.get("valu_issue_frac"), "lanes_active_per_valu": d.get("lanes_active_per_valu"), "l2_hit": d.get("l2_hit"),
-                                 "wave_cycles_waiting": d.get("wait"), "wave_cycles_issue_stalled": d.get("stall"), "valu_per_wave": d.get("valu_per_wave"),
-                                 "wave_life_us": d.get("wave_life_us"), "source": os.path.relpath(sq, ROOT),
-                                 "what": "issue_frac = VALU wave-instructions x 2 cycles / (1024 SIMDs x 2.3 GHz) / kernel time: the share of the kernel during which "
-                                         "the vector ALUs could have been issuing at all; lanes_active_per_valu of 64; l2_hit = TCC_HIT / (TCC_HIT + TCC_MISS); the two "
-                                         "wave_cycles shares are SQ_WAIT_ANY (parked in s_waitcnt / barrier) and SQ_WAIT_INST_ANY (issue-stalled) over SQ_WAVE_CYCLES"}
-        except Exception:
-            pass
-    one_ms = latency_frame_s * 1e3 if latency_frame_s is not None else ms_per_step
+                tris_read = n_tris_total
+                b_launch = 48 * n_tris_total + 8 * n_hits
+            # the whole frame: + k_project_finish (8 B key read per ray) + k_pack (8 B key read + 8 B re-arm per ray,
+            # 48 B point + hit record per hit)
+            b_frame = b_launch + 24 * shard_rays + 48 * n_hits
+            units = {"triangles_per_launch": n_tris_total, "triangles_read_per_launch": tris_read,
+                     "bytes_per_triangle": b_launch / max(1, n_tris_total),
+                     "candidate_tests_per_launch": n_tri, "tests_per_triangle": n_tri / max(1, n_tris_total),
+                     "rays_per_launch": shard_rays,
+                     "nominal_bytes_per_launch": 48 * n_tris_total + 8 * n_hits}
+            if culled:
+                units["cull"] = {"blocks_of_256": n_blocks, "group_bounds_read": group_bounds_read, "groups_surviving": groups_alive,
+                                 "what": "bytes are priced on what the culled stage has to read: 32 B per block bound, 32 B per group bound "
+                                         "inside surviving blocks, 8 B per surviving group (list), 48 B per surviving triangle, 8 B per hit"}
+        achieved = b_launch / (trace_ms * 1e-3) / 1e9 if trace_ms > 0 else 0.0
+        # HBM bytes of that kernel from the committed rocprofv3 PMC passes (FETCH_SIZE x2 + WRITE_SIZE, KiB).  Counters cannot
+        # be collected from inside this process, so the figure is the profiled one -- and only if the profile was taken
+        # from these very kernel sources (its recorded source hash equals the current one)
+        traffic, traffic_src = None, None
+        sha = kernel_source_sha()
+        prof = os.path.join(ROOT, "profiles", f"{PROFILE_TAG}_{engine}_hbm.json")
+        if args.workload == "syn128x1m" and world == 1 and os.path.exists(prof):  # only the profiled configuration
+            try:
+                pj = json.load(open(prof))
+                if pj.get("kernel_source_sha") != sha:
+                    traffic_src = f"{os.path.relpath(prof, ROOT)} is stale (taken from kernel sources {pj.get('kernel_source_sha')}, these are {sha}): not reported"
+                else:
+                    k = pj["kernels"]
+                    # the timed variant: template argument COUNT (the first one) is false
+                    key = next((n for n in k if n.split("<")[0] == kernel and not n.split("<")[-1].startswith("true")), None)
+                    if key:
+                        traffic, traffic_src = k[key]["hbm_bytes_per_launch"], os.path.relpath(prof, ROOT)
+            except Exception:
+                pass
+        # What binds the kernel besides bytes (SURVEY.md 8d "secondary ceilings"): the committed SQ / TCC counter summary of the same
+        # kernel sources (tools/sq_profile.sh -> profiles/<tag>_<engine>_sq.json), same staleness rule as `traffic`
+        secondary = None
+        sq = os.path.join(ROOT, "profiles", f"{PROFILE_TAG}_{engine}_sq.json")
+        if args.workload == "syn128x1m" and world == 1 and os.path.exists(sq):
+            try:
+                sj = json.load(open(sq))
+                if sj.get("kernel_source_sha") != sha:
+                    secondary = {"source": f"{os.path.relpath(sq, ROOT)} is stale (taken from kernel sources {sj.get('kernel_source_sha')}, these are {sha}): not reported"}
+                else:
+                    key = next((n for n in sj["kernels"] if n.split("<")[0] == kernel and not n.split("<")[-1].startswith("true")), None)
+                    if key:
+                        d = sj["kernels"][key]["derived"]
+                        secondary = {"issue_frac": d.get("valu_issue_frac"), "lanes_active_per_valu": d.get("lanes_active_per_valu"), "l2_hit": d.get("l2_hit"),
+                                     "wave_cycles_waiting": d.get("wait"), "wave_cycles_issue_stalled": d.get("stall"), "valu_per_wave": d.get("valu_per_wave"),
+                                     "wave_life_us": d.get("wave_life_us"), "source": os.path.relpath(sq, ROOT),
+                                     "what": "issue_frac = VALU wave-instructions x 2 cycles / (1024 SIMDs x 2.3 GHz) / kernel time: the share of the kernel during which "
+                                             "the vector ALUs could have been issuing at all; lanes_active_per_valu of 64; l2_hit = TCC_HIT / (TCC_HIT + TCC_MISS); the two "
+                                             "wave_cycles shares are SQ_WAIT_ANY (parked in s_waitcnt / barrier) and SQ_WAIT_INST_ANY (issue-stalled) over SQ_WAVE_CYCLES"}
+            except Exception:
+                pass
+        one_ms = latency_frame_s * 1e3 if latency_frame_s is not None else ms_per_step
+        roofline = dict({
+            "bound": "hbm", "kernel": kernel, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "secondary": secondary,
+            "kernel_ms": trace_ms, "kernel_launches_timed": tm["frames"],
+            "kernel_timing": "ISOLATED kernel: its own begin / end timestamps (hipEvents attached to the dispatch with hipExtLaunchKernel, what rocprofv3 reports per dispatch; events recorded around a launch add ~3 us of barrier packets) with ONE frame in flight (frames do not overlap while it is timed), in a second pass of the same K frames; compare with ms_per_step_one_frame_in_flight, not with ms_per_step (frames overlap there), and with profiles/*_kernel_isolated.json (the same figure from the rocprofv3 trace of this command)",
+            "ms_per_step_one_frame_in_flight": one_ms,
+            "algorithmic_bytes_per_launch": b_launch, "kernel_source_sha": sha,
+            # the same roofline on the frame as timed: all kernels' algorithmic bytes over the reported step time
+            "step_basis": None if b_frame is None else {
+                "algorithmic_bytes_per_frame": b_frame, "ms_per_step": ms_per_step,
+                "achieved": b_frame / (ms_per_step * 1e-3) / 1e9, "frac": b_frame / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "what": "k_project + k_project_finish + k_pack bytes of one frame / the reported (overlapped) step time"}},
+            **units)
 
-    if cgroup:   # the whole frame's cloud as this rank holds it after the gather + rebuild (the group keeps three frames)
+    if full and cgroup:   # the whole frame's cloud as this rank holds it after the gather + rebuild (the group keeps three frames)
         import hashlib
         gathered_cloud, gathered_hits = grp.download(group_last_frame[0])
         # (sector-major as gathered: rank 0's records, then rank 1's ...; hashed in ray order, the order of the one-GPU cloud)
@@ -1326,27 +1434,18 @@ def measure(args, rank, world, device, dev_index, rehearsal, multi, force_group=
         "hits_per_frame_rank0": n_hits,
         "points_sha256": points_sha,
         # N > 1: points of the whole frame as rebuilt from the gathered slots on rank 0 (= the 1-GPU hit count)
-        "gathered_points_rank0": None if single else (int(gathered_cloud.shape[0]) if cgroup else int(cloud_n[0].item())),
+        "gathered_points_rank0": None if (single or not full) else (int(gathered_cloud.shape[0]) if cgroup else int(cloud_n[0].item())),
         "rehearsal_gloo_shared_gpu": True if rehearsal else None,
         "rccl": rccl_out,
         "host_numa": HOST_NUMA,
         "library": dict(LIBRARY or {}, loaded=capi.load().ls_source_hash().decode()),
         "frame_graph": {"state": tr.info(capi.LS_INFO_FRAME_GRAPH_STATE), "captures": tr.info(capi.LS_INFO_FRAME_GRAPH_CAPTURES),
                         "replays": tr.info(capi.LS_INFO_FRAME_GRAPH_REPLAYS), "patches": tr.info(capi.LS_INFO_FRAME_GRAPH_PATCHES)},
-        "roofline": dict({
-            "bound": "hbm", "kernel": kernel, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "secondary": secondary,
-            "kernel_ms": trace_ms, "kernel_launches_timed": tm["frames"],
-            "kernel_timing": "ISOLATED kernel: its own begin / end timestamps (hipEvents attached to the dispatch with hipExtLaunchKernel, what rocprofv3 reports per dispatch; events recorded around a launch add ~3 us of barrier packets) with ONE frame in flight (frames do not overlap while it is timed), in a second pass of the same K frames; compare with ms_per_step_one_frame_in_flight, not with ms_per_step (frames overlap there), and with profiles/*_kernel_isolated.json (the same figure from the rocprofv3 trace of this command)",
-            "ms_per_step_one_frame_in_flight": one_ms,
-            "algorithmic_bytes_per_launch": b_launch, "kernel_source_sha": sha,
-            # the same roofline on the frame as timed: all kernels' algorithmic bytes over the reported step time
-            "step_basis": None if b_frame is None else {
-                "algorithmic_bytes_per_frame": b_frame, "ms_per_step": ms_per_step,
-                "achieved": b_frame / (ms_per_step * 1e-3) / 1e9, "frac": b_frame / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "what": "k_project + k_project_finish + k_pack bytes of one frame / the reported (overlapped) step time"}},
-            **units),
     }
+    if roofline is not None:
+        out["roofline"] = roofline
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if latency_frame_s is not None:
         out["ms_per_step_one_frame_in_flight"] = latency_frame_s * 1e3
     if steady_s is not None:
@@ -1363,7 +1462,7 @@ def measure(args, rank, world, device, dev_index, rehearsal, multi, force_group=
         out["copy_update_ms_per_step"] = copy_frame_s * 1e3
         out["trace_only_ms"] = trace_only_s * 1e3
         out["trace_only_mrays_per_s"] = shard_rays / trace_only_s / 1e6
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not replicas and not getattr(args, "lean", False):
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline and not replicas and not getattr(args, "lean", False):
         out["cpu_baseline"] = cpu_baseline(sensor, meshes, args.cpu_frames, total_rays)
     if cgroup:
         grp.close()

@@ -217,7 +217,7 @@ def test_bench_two_ranks_rehearsal_without_a_launcher():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["LS_BENCH_REHEARSAL"] = "1"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--workload", "xt32",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "10", "--warmup", "2", "--workload", "xt32",
                           "--no-cpu-baseline", "--min-ms", "5", "--prime-ms", "0"], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
@@ -238,7 +238,7 @@ def test_bench_every_phase_of_the_multi_rank_flow_through_a_one_rank_communicato
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["LS_BENCH_FORCE_GROUP"] = "1"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--workload", "xt32",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "2", "--workload", "xt32",
                           "--no-cpu-baseline", "--no-dropin", "--min-ms", "5", "--prime-ms", "0"], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
@@ -260,7 +260,7 @@ def test_bench_two_ranks_watchdog_reports_what_finished():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update({"LS_BENCH_REHEARSAL": "1", "LS_BENCH_DEBUG_STALL": "sharded", "LS_BENCH_WATCHDOG_S": "45"})
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--workload", "xt32",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "10", "--warmup", "2", "--workload", "xt32",
                           "--no-cpu-baseline", "--min-ms", "5", "--prime-ms", "0"], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode != 0, out.stderr[-3000:]   # (a job whose watchdog fired did not succeed: the ranks leave with 4, the launcher says so; the line is there)
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
@@ -273,7 +273,7 @@ def test_bench_two_ranks_watchdog_reports_what_finished():
     # collective fails or times out, rank 0 reports the same way
     env.pop("LS_BENCH_DEBUG_STALL")
     env["LS_BENCH_DEBUG_RAISE"] = "sharded:1"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--workload", "xt32",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "10", "--warmup", "2", "--workload", "xt32",
                           "--no-cpu-baseline", "--min-ms", "5", "--prime-ms", "0"], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode != 0, out.stderr[-3000:]   # (a job whose watchdog fired did not succeed: the ranks leave with 4, the launcher says so; the line is there)
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]

@@ -223,7 +223,7 @@ def test_bench_two_gpus_end_to_end_on_the_shim():
     the shim.  Every phase of the N > 1 flow runs against a real peer -- frames interleaved, shards + all-gather on one communicator,
     shards + per-set communicators (plain launches), and SYN-10M -- and the line says what it is: "shim": true, never a number to quote."""
     env = shim_env(LS_BENCH_SHIM=1, LS_BENCH_WATCHDOG_S=200)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "3", "--min-ms", "5",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "12", "--warmup", "3", "--min-ms", "5",
                           "--prime-ms", "5", "--no-cpu-baseline", "--no-dropin"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-4000:]
     rec = json.loads(out.stdout.strip().splitlines()[-1])

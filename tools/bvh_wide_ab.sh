@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for WIDE in 1 0; do
   for WL in syn128x1m cfg5; do
-    LS_BENCH_BVH_WIDE=$WIDE timeout -k 10 280 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${WL}_w$WIDE -o p -- python3 $REPO/bench.py --engine bvh --workload $WL --no-also --no-cpu-baseline --no-dropin --steps 50 --warmup 10 > $OUT/bench_${WL}_w$WIDE.json 2> $OUT/bench_${WL}_w$WIDE.err
+    LS_BENCH_BVH_WIDE=$WIDE timeout -k 10 280 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${WL}_w$WIDE -o p -- python3 $REPO/bench.py --full --engine bvh --workload $WL --no-also --no-cpu-baseline --no-dropin --steps 50 --warmup 10 > $OUT/bench_${WL}_w$WIDE.json 2> $OUT/bench_${WL}_w$WIDE.err
     f=$(find $OUT/prof_${WL}_w$WIDE -name "*kernel_stats.csv" | head -1)
     echo "== $WL wide=$WIDE"; python3 -c "
 import csv,sys

@@ -2,6 +2,8 @@
 # GPU box: BVH-engine headline frame for library variants "<dir>[:ENV=VAL,...]": parity subset, then bench.py --engine bvh
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $REPO/gpurun_out/exp $REPO/gpurun_out/final
+RES=${RES:-$REPO/build/exp/results}   # the bench lines
+mkdir -p "$RES"
 for spec in "$@"; do
   v=${spec%%:*}; envs=""; [ "$spec" != "$v" ] && envs=${spec#*:}
   tag=$(echo "$spec" | tr ':=,' '___')
@@ -13,8 +15,8 @@ for spec in "$@"; do
   rc=$?
   tail -1 $REPO/gpurun_out/exp/bvh_$tag.pytest.log
   if [ $rc -ne 0 ] && [ -z "$EXP_NOPARITY" ]; then echo "PARITY FAILED for $spec"; exit 0; fi
-  timeout -k 10 300 python3 $REPO/bench.py --engine bvh --no-dropin --no-cpu-baseline > $REPO/gpurun_out/exp/bvh_$tag.json 2> $REPO/gpurun_out/exp/bvh_$tag.err
-  python3 - $REPO/gpurun_out/exp/bvh_$tag.json <<'PY'
+  timeout -k 10 300 python3 $REPO/bench.py --full --engine bvh --no-dropin --no-cpu-baseline > "$RES/bvh_$tag.json" 2> "$RES/bvh_$tag.err"
+  python3 - "$RES/bvh_$tag.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d["roofline"]

@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$REPO"
 export LS_LIB_PATH=$REPO/build/exp/base/liblidarshooter_hip.so
 for mode in 0 1 2 0 1 2 0 1 2; do
-  LS_CU_MASK_MODE=$mode python bench.py --no-cpu-baseline --no-dropin --steps 200 > /tmp/o.json 2>/tmp/o.err
+  LS_CU_MASK_MODE=$mode python bench.py --full --min-ms 50 --no-cpu-baseline --no-dropin --steps 200 > /tmp/o.json 2>/tmp/o.err
   python3 - "$mode" <<'PY'
 import json, sys
 try:

@@ -10,17 +10,21 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$REPO"
 mkdir -p gpurun_out/final
 : > gpurun_out/final/bench.err
+# the bench lines (bench.py --full) and their stderr
+BENCH_OUT=${BENCH_OUT:-build/bench/$TAG}
+mkdir -p "$BENCH_OUT"
+: > "$BENCH_OUT"/bench.err
 # (the profiler's passes write their files when they end: a line a minute tells the box's watchdog that this script is alive; every
 # pass has its own time limit inside the scripts it calls, and the call as a whole gpurun's)
 ( while true; do date +"%T still measuring" >> gpurun_out/final/heartbeat.txt; sleep 60; done ) &
 HEARTBEAT=$!
 trap "kill $HEARTBEAT 2>/dev/null" EXIT
 if [ "$PART" = a ] || [ "$PART" = all ]; then
-python bench.py --no-cpu-baseline --no-dropin --no-also --pipeline 1 > gpurun_out/final/bench_${TAG}_projection_mode1.json 2>> gpurun_out/final/bench.err
-python bench.py --no-cpu-baseline --no-dropin --workload syn128x10m > gpurun_out/final/bench_${TAG}_projection_10m.json 2>> gpurun_out/final/bench.err
-python bench.py --no-cpu-baseline --no-dropin --workload syn128x10m --no-cull > gpurun_out/final/bench_${TAG}_projection_10m_nocull.json 2>> gpurun_out/final/bench.err
-python bench.py --no-cpu-baseline --no-dropin --workload cfg5 > gpurun_out/final/bench_${TAG}_projection_cfg5.json 2>> gpurun_out/final/bench.err
-python bench.py --no-cpu-baseline --workload xt32 > gpurun_out/final/bench_${TAG}_projection_xt32.json 2>> gpurun_out/final/bench.err
+python bench.py --full --no-cpu-baseline --no-dropin --no-also --pipeline 1 > "$BENCH_OUT"/bench_${TAG}_projection_mode1.json 2>> "$BENCH_OUT"/bench.err
+python bench.py --full --no-cpu-baseline --no-dropin --workload syn128x10m > "$BENCH_OUT"/bench_${TAG}_projection_10m.json 2>> "$BENCH_OUT"/bench.err
+python bench.py --full --no-cpu-baseline --no-dropin --workload syn128x10m --no-cull > "$BENCH_OUT"/bench_${TAG}_projection_10m_nocull.json 2>> "$BENCH_OUT"/bench.err
+python bench.py --full --no-cpu-baseline --no-dropin --workload cfg5 > "$BENCH_OUT"/bench_${TAG}_projection_cfg5.json 2>> "$BENCH_OUT"/bench.err
+python bench.py --full --no-cpu-baseline --workload xt32 > "$BENCH_OUT"/bench_${TAG}_projection_xt32.json 2>> "$BENCH_OUT"/bench.err
 python tools/dump_mesh.py syn1m /tmp/syn1m.lsmesh   # lsbench traces bench.py's SYN-1M bit for bit (its --grid is a look-alike)
 for p in 0 1 2; do
   lidarshooter_amd/lsbench --config tests/golden/data/config/hesai-pandar-XT-32-lidar_0000.json --syn 128 4096 --mesh-raw ground=/tmp/syn1m.lsmesh --frames 2000 --warmup 200 --pipeline $p
@@ -34,8 +38,8 @@ done >> gpurun_out/final/lsbench_${TAG}.jsonl 2>> gpurun_out/final/bench.err
 lidarshooter_amd/lsbench --config tests/golden/data/config/hesai-pandar-XT-32-lidar_0000.json --syn 128 4096 --mesh-raw ground=/tmp/syn1m.lsmesh --frames 2000 --warmup 200 --ranks 1 --group interleaved >> gpurun_out/final/lsbench_${TAG}.jsonl 2>> gpurun_out/final/bench.err
 lidarshooter_amd/lsbench --config tests/golden/data/config/hesai-pandar-XT-32-lidar_0000.json --syn 128 4096 --mesh-raw ground=/tmp/syn1m.lsmesh --frames 2000 --warmup 200 --pipeline 2 --graph 1 >> gpurun_out/final/lsbench_${TAG}.jsonl 2>> gpurun_out/final/bench.err
 # the N > 1 driver of bench.py on one GPU (every line of it: C group, one-rank communicator), and the host-cost micro-benchmark
-LS_BENCH_FORCE_GROUP=1 python bench.py --no-cpu-baseline --no-dropin > gpurun_out/final/bench_${TAG}_force_group.json 2>> gpurun_out/final/bench.err
-LS_BENCH_FORCE_GROUP=1 python bench.py --no-cpu-baseline --no-dropin --group-flags 1 > gpurun_out/final/bench_${TAG}_force_group_one_communicator.json 2>> gpurun_out/final/bench.err
+LS_BENCH_FORCE_GROUP=1 python bench.py --full --no-cpu-baseline --no-dropin > "$BENCH_OUT"/bench_${TAG}_force_group.json 2>> "$BENCH_OUT"/bench.err
+LS_BENCH_FORCE_GROUP=1 python bench.py --full --no-cpu-baseline --no-dropin --group-flags 1 > "$BENCH_OUT"/bench_${TAG}_force_group_one_communicator.json 2>> "$BENCH_OUT"/bench.err
 (cd tools/micro && ./graph_launch --rccl) > gpurun_out/final/${TAG}_graph_launch_micro.txt 2>&1
 (cd tools/micro && ./chunked_h2d) > gpurun_out/final/${TAG}_chunked_h2d_micro.txt 2>&1
 (cd tools/micro && ./loads_probe) > gpurun_out/final/${TAG}_loads_probe_micro.txt 2>&1
@@ -53,7 +57,7 @@ python tools/dropin_bench.py 50 > gpurun_out/final/dropin_${TAG}.json 2>> gpurun
 python tools/bvh_cfg5_cost.py 60 > gpurun_out/final/${TAG}_bvh_cfg5_cost.json 2>> gpurun_out/final/bench.err
 for ph in build poses refit_ben classic; do echo "== $ph"; PHASE=$ph bash tools/rocprof_kernels.sh cfg5_$ph tools/bvh_cfg5_cost.py 30 | sort -k5 -n -r | head -16; tail -1 gpurun_out/rp_cfg5_$ph/stdout.log; done > gpurun_out/final/${TAG}_bvh_cfg5_kernels.txt 2>&1
 find gpurun_out/rp_cfg5_* -name "*kernel_trace.csv" -delete
-python bench.py --workload cfg5 --engine bvh --no-cpu-baseline --no-dropin > gpurun_out/final/bench_${TAG}_bvh_cfg5.json 2>> gpurun_out/final/bench.err
+python bench.py --full --workload cfg5 --engine bvh --no-cpu-baseline --no-dropin > "$BENCH_OUT"/bench_${TAG}_bvh_cfg5.json 2>> "$BENCH_OUT"/bench.err
 fi
 if [ "$PART" = b ] || [ "$PART" = b1 ] || [ "$PART" = all ]; then
 bash tools_profile.sh ${TAG} > gpurun_out/final/profile.log 2>&1
@@ -84,9 +88,9 @@ cp gpurun_out/sq_${TAG}/*_sq.txt gpurun_out/sq_${TAG}/*_sq.json gpurun_out/final
 for f in projection projection_10m bvh shard_1m shard_10m; do [ -f gpurun_out/final/${f}_sq.txt ] && mv gpurun_out/final/${f}_sq.txt gpurun_out/final/${TAG}_${f}_sq.txt; [ -f gpurun_out/final/${f}_sq.json ] && mv gpurun_out/final/${f}_sq.json gpurun_out/final/${TAG}_${f}_sq.json; done
 # the two headline lines last: they read `roofline.traffic` and `roofline.secondary` from the profiles just taken (same kernel sources, same box)
 cp gpurun_out/final/${TAG}_projection_hbm.json gpurun_out/final/${TAG}_bvh_hbm.json gpurun_out/final/${TAG}_projection_sq.json gpurun_out/final/${TAG}_bvh_sq.json profiles/
-python bench.py > gpurun_out/final/${TAG}_projection_bench.json 2>> gpurun_out/final/bench.err
-python bench.py --engine bvh --no-dropin > gpurun_out/final/${TAG}_bvh_bench.json 2>> gpurun_out/final/bench.err
-python bench.py --engine bvh --no-dropin --no-cpu-baseline --classic-bvh > gpurun_out/final/bench_${TAG}_bvh_classic.json 2>> gpurun_out/final/bench.err
+python bench.py --full > "$BENCH_OUT"/${TAG}_projection_bench.json 2>> "$BENCH_OUT"/bench.err
+python bench.py --full --engine bvh --no-dropin > "$BENCH_OUT"/${TAG}_bvh_bench.json 2>> "$BENCH_OUT"/bench.err
+python bench.py --full --engine bvh --no-dropin --no-cpu-baseline --classic-bvh > "$BENCH_OUT"/bench_${TAG}_bvh_classic.json 2>> "$BENCH_OUT"/bench.err
 # SYN-10M: kernel averages of the culled stage (k_cull + k_project), what it reads and keeps, its HBM-side traffic
 W=syn128x10m MODES=one bash tools/rocprof_kernels.sh ${TAG}_10m tools/shard_cost.py 2 1 > gpurun_out/final/${TAG}_projection_10m_kernels.txt 2>&1   # (one frame in flight: every dispatch alone)
 cp gpurun_out/rp_${TAG}_10m/${TAG}_10m_kernel_stats.csv gpurun_out/final/${TAG}_projection_10m_kernel_stats.csv

@@ -77,9 +77,9 @@ PY
     find "$D" -name "*kernel_trace.csv" -delete; find "$D" -name "*counter_collection.csv" -size +20M -delete
 }
 cd "$REPO"
-run projection "$REPO/bench.py" --steps 10 --warmup 2 --no-cpu-baseline --no-dropin --no-also --no-pipeline
+run projection "$REPO/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline --no-dropin --no-also --no-pipeline
 W=syn128x10m MODES=one run projection_10m "$REPO/tools/shard_cost.py" 2 1
-run bvh "$REPO/bench.py" --steps 10 --warmup 2 --no-cpu-baseline --no-dropin --engine bvh
+run bvh "$REPO/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline --no-dropin --engine bvh
 W=syn128x1m MODES=one RANKS=4 run shard_1m "$REPO/tools/shard_cost.py" 2 8
 W=syn128x10m MODES=one RANKS=4 run shard_10m "$REPO/tools/shard_cost.py" 2 8
 head -50 "$OUT/projection_sq.txt"

@@ -8,7 +8,7 @@ mkdir -p $OUT
 run() {  # label, env...
   local label=$1; shift
   for i in $(seq $N); do
-    env "$@" python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-dropin --no-also 2>> $OUT/err.txt | python -c "
+    env "$@" python bench.py --full --min-ms 50 --steps 20 --warmup 5 --no-cpu-baseline --no-dropin --no-also 2>> $OUT/err.txt | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 t = d['timing']['window_ms_min_median_max']

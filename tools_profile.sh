@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 50 --warmup 10 --no-cpu-baseline --no-dropin --no-also $*"
+ARGS="--full --steps 50 --warmup 10 --no-cpu-baseline --no-dropin --no-also $*"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o "$TAG" -- python3 "$REPO/bench.py" $ARGS > "$OUT/bench_stats.json" 2> "$OUT/stats.err" || echo "stats pass failed"
 # the same frames with ONE frame in flight: every dispatch runs alone, the stats average is the isolated kernel's duration
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_one" -o "$TAG" -- python3 "$REPO/bench.py" $ARGS --no-pipeline > "$OUT/bench_stats_one.json" 2> "$OUT/stats_one.err" || echo "one-in-flight stats pass failed"
