@@ -429,6 +429,7 @@ int ls_parallel_copy(void *dst, const void *src, uint64_t bytes);
 #define LS_INFO_EMIT_POINTS 14       /* the current LS_OPT_EMIT_POINTS                                            */
 #define LS_INFO_BVH_WIDE 16                /* 1: the last trace walked the four-wide nodes (LS_OPT_BVH_WIDE, instanced mode, every geometry's made) */
 #define LS_INFO_FRAME_GRAPH_PATCH_WAITS 15 /* patches that first had to wait for the previous launch of their graph (the host ran more than three frames ahead) */
+#define LS_INFO_RAY_QUERY_BUILT 17         /* geometries whose query hierarchy the last ls_trace_rays* built or refitted (see there) */
 long ls_get_info(ls_tracer *tr, int what);
 
 /* Mean stage durations (milliseconds, hipEvents on the handle's stream) over every frame recorded
@@ -464,6 +465,33 @@ int ls_generate_rays(ls_tracer *tr, float *d_dir_x, float *d_dir_y, float *d_dir
  *            the reference; written as 0 here), intensity f32@16 = 64.0, ring i32@20 = the channel index.
  * Either pointer may be NULL (that output is skipped). */
 int ls_generate_rays_aos(ls_tracer *tr, void *d_rays, void *d_hits);
+
+/* ---- ray queries: the closest hit of each of n CALLER rays against the scene as of the last successful ls_commit_scene
+ * (the geometries' current poses, as a frame would use them) -- scan patterns that are not a uniform raster, several sensors
+ * on one scene, "what does this ray hit", "is anything between A and B" (a ray with a tmax).
+ *   d_rays: n lidarshooter::Ray records, 32 bytes each (origin xyz f32@0, tmin f32@12, direction xyz f32@16, tmax f32@28) --
+ *           the layout ls_generate_rays_aos writes -- in the handle's SENSOR frame (the frame of ls_frame.points32; a caller
+ *           whose rays are in the world frame creates the handle with Rinv = I, t = 0).  16-byte aligned.
+ *   d_out:  n ls_hit records (16-byte aligned) in ray order: ray = index, geom / prim as in ls_frame.hits, t = distance along
+ *           the direction as given (not normalised); a miss is geom = prim = 0xFFFFFFFF, t = -1.
+ * A triangle counts when the frame's exact test hits it (Embree's Moeller-Trumbore, from the ray's own origin) and
+ * tmin <= t <= tmax; equal t: the lowest (geomID, primID) wins, as in frames.  A ray with a non-finite origin or direction,
+ * a zero direction, a NaN bound or tmin > tmax is a miss (tmax = +inf is no bound).
+ * Enqueued on hip_stream (NULL: the handle's stream) after everything already issued on the handle; returns without waiting.
+ * What the handle issues afterwards on its own stream (mesh copies, commits, the next query) comes after the query; frames of
+ * the three-stream rotation (LS_OPT_PIPELINE = 2) may overlap it.
+ * Returns what ls_trace_scene returns in the same state: -1 with no commit or an empty scene (out is not written),
+ * LS_ERR_NOT_COMMITTED when a geometry was removed since the commit; LS_ERR_INVALID_ARGUMENT for NULL pointers with n > 0
+ * and while a frame graph is open; n = 0 launches nothing.
+ * The query uses hierarchies of its own, one per geometry, built at the first query after a commit that changed a
+ * geometry's vertices (a refit) or indices (a rebuild) -- a commit after which only poses changed builds nothing
+ * (LS_INFO_RAY_QUERY_BUILT = 0) -- in mesh space; a geometry whose pose has no usable inverse (scaled to zero, a scale
+ * ratio above 10^3) is kept in the sensor frame instead and rebuilt when its pose changes.  Memory: about 0.3 GB per
+ * million triangles at leaf size 1 (48-byte records, 64-byte binary and 128-byte four-wide nodes, range boxes, sorted keys;
+ * counted from those sizes, not measured), on top of the frame path's own; LS_OPT_ENGINE does not matter. */
+int ls_trace_rays(ls_tracer *tr, void *hip_stream, const void *d_rays, uint32_t n, void *d_out);
+/* The same with host memory (pageable) in and out, on the handle's stream; returns when out is filled. */
+int ls_trace_rays_host(ls_tracer *tr, const void *rays, uint32_t n, void *out);
 
 #ifdef __cplusplus
 }

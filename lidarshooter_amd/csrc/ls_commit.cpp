@@ -136,6 +136,64 @@ bool inst_possible(const ls_tracer *tr, const std::vector<Geometry *> &order)
     return true;
 }
 
+int hier_layout(ls_tracer *tr, HierSet &hs, const std::vector<Geometry *> &order, uint32_t g, uint32_t *n_nodes)
+{
+    hs.slots->assign(order.size(), ls_tracer::InstSlot());
+    uint32_t nodes = 0, recs = 0, range = 0;
+    for (size_t i = 0; i < order.size(); ++i) {
+        ls_tracer::InstSlot &sl = (*hs.slots)[i];
+        const uint32_t L = (order[i]->n_tris + g - 1) / g;
+        sl.node_first = nodes; sl.rec_first = recs; sl.n_leaves = L; sl.range_first = range;
+        std::memset(&sl.rt, 0, sizeof(sl.rt));
+        uint32_t cnt = L, off = 0, lev = 0;
+        while (true) {
+            sl.rt.count[lev] = cnt; sl.rt.offset[lev] = off;
+            off += cnt; ++lev;
+            if (cnt <= 1) break;
+            cnt = (cnt + 1) / 2;
+        }
+        sl.rt.levels = lev;
+        nodes += L; recs += L * g; range += 2 * off + 2;
+    }
+    int rc;
+    if ((rc = ensure(tr, *hs.records, (size_t)recs))) return rc;
+    if ((rc = ensure(tr, *hs.nodes, (size_t)nodes + 1))) return rc;
+    if (hs.wide && (rc = ensure(tr, *hs.wide, (size_t)nodes + 1))) return rc;
+    if ((rc = ensure(tr, *hs.range_boxes, (size_t)range + 2))) return rc;
+    *n_nodes = nodes;
+    return LS_OK;
+}
+
+// (the caller has sized verts, keys_a / keys_b / vals_b for the whole layout and sort_temp for its biggest geometry; vfirst /
+// tfirst: the geometry's first vertex / triangle in the layout, where its slices of verts and of the key arrays start)
+int hier_build(ls_tracer *tr, HierSet &hs, hipStream_t s, size_t i, const Geometry &ge, uint32_t vfirst, uint32_t tfirst, const float *A12,
+               const float *R9, const float *T3, uint32_t g, bool refit, bool widen)
+{
+    ls_tracer::InstSlot &sl = (*hs.slots)[i];
+    float *verts = hs.verts->p + 3 * (size_t)vfirst;
+    const uint32_t *tris = ge.idx();   // mesh-local indices are what a per-geometry hierarchy wants: no rebased copy
+    uint32_t *ka = hs.keys_a->p + tfirst, *kb = hs.keys_b->p + tfirst, *vb = hs.vals_b->p + tfirst;
+    ls::launch_transform(s, ge.raw(), ge.stride, ge.n_verts, A12, R9, T3, verts, hs.d_maxabs + i);
+    if (!refit) {
+        // the keys, and with them the sort's first tile histograms; the values are the triangles' positions
+        ls::launch_morton(s, verts, tris, ge.n_tris, hs.d_maxabs + i, ka, nullptr, ls::sort_first_counts(hs.sort_temp->p, ge.n_tris));
+        if (!ls::launch_sort(s, hs.sort_temp->p, hs.sort_temp->cap, ka, kb, nullptr, vb, ge.n_tris, true))
+            return fail(tr, LS_ERR_OUT_OF_RANGE, "the sort scratch is smaller than a geometry's hierarchy build needs");
+    }
+    float4 *rb = hs.range_boxes->p + sl.range_first;
+    ls::launch_leaves_tree(s, verts, tris, vb, ge.n_tris, g, hs.records->p + sl.rec_first, sl.rt, rb, true);
+    // (a refit finds the topology of these very keys in the nodes: fresh layouts and classic builds in between clear the condition)
+    if (refit) ls::launch_refit_nodes(s, sl.n_leaves, sl.rt, rb, hs.nodes->p + sl.node_first);
+    else ls::launch_hierarchy(s, kb, sl.n_leaves, g, sl.rt, rb, hs.nodes->p + sl.node_first);
+    sl.wide_made = false;
+    sl.wide_age = 0;
+    if (widen && hs.wide) {
+        ls::launch_widen(s, hs.nodes->p + sl.node_first, sl.n_leaves, hs.wide->p + sl.node_first);
+        sl.wide_made = true;
+    }
+    return LS_OK;
+}
+
 // Hierarchies of the geometries whose vertices or topology changed (all of them after a layout change), each over its
 // own slice of the shared key / record / node arrays, in MESH space: the same kernels as the classic build, fed with the
 // vertices as uploaded.  A commit after which only poses differ finds nothing to do here.
@@ -146,28 +204,11 @@ int commit_instanced(ls_tracer *tr, const std::vector<Geometry *> &order, bool r
     const bool fresh = relayout || !tr->inst_valid || tr->inst_leaf_size != g || tr->inst_layout.size() != order.size() ||
                        (tr->opt_bvh_wide != 0) != tr->wide_valid;   // (the option changed: the twins are made with the hierarchies)
     int rc;
+    HierSet hs{&tr->records, &tr->nodes, tr->opt_bvh_wide ? &tr->wide_nodes : nullptr, &tr->range_boxes, &tr->inst_layout,
+               &tr->inst_verts, &tr->keys_a, &tr->keys_b, &tr->vals_b, &tr->sort_temp, tr->d_inst_maxabs};
     if (fresh) {
-        tr->inst_layout.assign(order.size(), ls_tracer::InstSlot());
-        uint32_t nodes = 0, recs = 0, range = 0;
-        for (size_t i = 0; i < order.size(); ++i) {
-            ls_tracer::InstSlot &sl = tr->inst_layout[i];
-            const uint32_t L = (order[i]->n_tris + g - 1) / g;
-            sl.node_first = nodes; sl.rec_first = recs; sl.n_leaves = L; sl.range_first = range;
-            std::memset(&sl.rt, 0, sizeof(sl.rt));
-            uint32_t cnt = L, off = 0, lev = 0;
-            while (true) {
-                sl.rt.count[lev] = cnt; sl.rt.offset[lev] = off;
-                off += cnt; ++lev;
-                if (cnt <= 1) break;
-                cnt = (cnt + 1) / 2;
-            }
-            sl.rt.levels = lev;
-            nodes += L; recs += L * g; range += 2 * off + 2;
-        }
-        if ((rc = ensure(tr, tr->records, (size_t)recs))) return rc;
-        if ((rc = ensure(tr, tr->nodes, (size_t)nodes + 1))) return rc;
-        if (tr->opt_bvh_wide && (rc = ensure(tr, tr->wide_nodes, (size_t)nodes + 1))) return rc;
-        if ((rc = ensure(tr, tr->range_boxes, (size_t)range + 2))) return rc;
+        uint32_t nodes = 0;
+        if ((rc = hier_layout(tr, hs, order, g, &nodes))) return rc;
         tr->n_leaves = nodes;
         tr->inst_leaf_size = g;
     }
@@ -187,6 +228,7 @@ int commit_instanced(ls_tracer *tr, const std::vector<Geometry *> &order, bool r
             LS_HIP(hipMalloc(reinterpret_cast<void **>(&tr->d_inst_maxabs), ls::kGeomsPerLaunch * 4));
             LS_HIP(hipMemsetAsync(tr->d_inst_maxabs, 0, ls::kGeomsPerLaunch * 4, tr->stream));
         }
+        hs.d_maxabs = tr->d_inst_maxabs;
         tr->bvh_order_valid = false;   // the key arrays hold per-geometry slices now
         tr->classic_nodes_valid = false;
         if (fresh) ++tr->key_scratch_epoch;   // the slices moved
@@ -196,40 +238,18 @@ int commit_instanced(ls_tracer *tr, const std::vector<Geometry *> &order, bool r
         for (size_t i = 0; i < order.size(); ++i) {
             Geometry &ge = *order[i];
             if (!fresh && !ge.blas_dirty) continue;
-            const ls_tracer::LayoutEntry &le = tr->layout[i];
-            const ls_tracer::InstSlot &sl = tr->inst_layout[i];
-            float *verts = tr->inst_verts.p + 3 * (size_t)le.vfirst;
-            const uint32_t *tris = ge.idx();   // mesh-local indices are what a per-geometry hierarchy wants: no rebased copy
-            uint32_t *ka = tr->keys_a.p + le.tfirst, *kb = tr->keys_b.p + le.tfirst, *vb = tr->vals_b.p + le.tfirst;
-            // identity transform: the packed copy holds the vertices as uploaded (1 * x + 0 * y + 0 * z + 0 is x)
-            ls::launch_transform(s, ge.raw(), ge.stride, ge.n_verts, kIdA, kIdR, kZero, verts, tr->d_inst_maxabs + i);
             // vertices alone changed and the geometry's sorted keys are still in place: a refit (same order, same
             // topology, every box recomputed) -- what the classic path does with LS_OPT_BVH_REFIT
             const bool refit = tr->opt_bvh_refit && !ge.blas_topo_dirty && ge.blas_sorted_epoch == tr->key_scratch_epoch;
-            if (!refit) {
-                // the keys, and with them the sort's first tile histograms; the values are the triangles' positions
-                ls::launch_morton(s, verts, tris, ge.n_tris, tr->d_inst_maxabs + i, ka, nullptr, ls::sort_first_counts(tr->sort_temp.p, ge.n_tris));
-                if (!ls::launch_sort(s, tr->sort_temp.p, tr->sort_temp.cap, ka, kb, nullptr, vb, ge.n_tris, true))
-                    return fail(tr, LS_ERR_OUT_OF_RANGE, "the sort scratch is smaller than a geometry's hierarchy build needs");
-                ge.blas_sorted_epoch = tr->key_scratch_epoch;
-            }
-            float4 *rb = tr->range_boxes.p + sl.range_first;
-            ls::launch_leaves_tree(s, verts, tris, vb, ge.n_tris, g, tr->records.p + sl.rec_first, sl.rt, rb, true);
-            // (a refit finds the topology of these very keys in the nodes: fresh layouts and classic builds in between clear the condition)
-            if (refit) ls::launch_refit_nodes(s, sl.n_leaves, sl.rt, rb, tr->nodes.p + sl.node_first);
-            else ls::launch_hierarchy(s, kb, sl.n_leaves, g, sl.rt, rb, tr->nodes.p + sl.node_first);
             // The four-wide twins the trace walks (LS_OPT_BVH_WIDE) follow every build and every refit of this geometry -- at
             // once for a small hierarchy (a moving instance's refit: a few microseconds), LAZILY for a big one: k_widen costs 34 us
             // per million nodes, the wide walk wins ~13 us per frame there, and a hierarchy that is rebuilt or refitted every frame
             // would pay the first without ever collecting the second.  The trace makes them once a hierarchy has survived
             // kWidenAfterFrames frames (ls_trace.cpp) and walks the binary nodes until then.
-            ls_tracer::InstSlot &slw = tr->inst_layout[i];
-            slw.wide_made = false;
-            slw.wide_age = 0;
-            if (tr->opt_bvh_wide && sl.n_leaves <= kWidenAtOnceLeaves) {
-                ls::launch_widen(s, tr->nodes.p + sl.node_first, sl.n_leaves, tr->wide_nodes.p + sl.node_first);
-                slw.wide_made = true;
-            }
+            const bool widen = tr->opt_bvh_wide && tr->inst_layout[i].n_leaves <= kWidenAtOnceLeaves;
+            // identity transform: the packed copy holds the vertices as uploaded (1 * x + 0 * y + 0 * z + 0 is x)
+            if ((rc = hier_build(tr, hs, s, i, ge, tr->layout[i].vfirst, tr->layout[i].tfirst, kIdA, kIdR, kZero, g, refit, widen))) return rc;
+            if (!refit) ge.blas_sorted_epoch = tr->key_scratch_epoch;
         }
         tr->wide_valid = tr->opt_bvh_wide != 0;
         // a scene of one geometry: the top of its hierarchy for the trace grid's LDS (static with the hierarchy)

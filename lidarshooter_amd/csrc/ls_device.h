@@ -53,6 +53,29 @@ __device__ __forceinline__ bool tri_test(V3 d, V3 v0, V3 e1, V3 e2, float NgC, f
     return ok;
 }
 
+// The same test for a ray from an origin o of its own (ls_trace_rays): the oracle's tri_test (ls_oracle.c) with
+// tnear = 0, tfar = +inf, operation for operation -- C = v0 - o, R = cross(C, d), T = dot(Ng, C) -- so that t is
+// bit-equal to lso_tri_intersect.  With o = 0, C is v0 and T is tri_test's NgC: the same bits as the frame's test.
+// The caller keeps the closest hit below a running best that starts at +inf (closest_brute), so t = +inf is no hit.
+__device__ __forceinline__ bool tri_test_org(V3 o, V3 d, V3 v0, V3 e1, V3 e2, float &t)
+{
+    const V3 Ng = cross_fma(e2, e1);
+    const V3 C = sub(v0, o);
+    const V3 R = cross_fma(C, d);
+    const float den = dot_fma(Ng, d);
+    const float absDen = fabsf(den);
+    const uint32_t sgn = __float_as_uint(den) & 0x80000000u;
+    const float U = xor_sign(dot_fma(R, e2), sgn);
+    const float V = xor_sign(dot_fma(R, e1), sgn);
+    const float T = xor_sign(dot_fma(Ng, C), sgn);
+    bool ok = (den != 0.0f) & (U >= 0.0f) & (V >= 0.0f) & (U + V <= absDen) & (absDen * 0.0f < T) & (T <= absDen * INFINITY);
+    if (ok) {
+        t = T / absDen;
+        ok = t < INFINITY;
+    }
+    return ok;
+}
+
 
 // Vertex into the sensor frame: p' = Rinv * ((A * v) - t), the reference's operation order
 // (MeshTransformer.cpp:176-195 Eigen Affine3f * Vector3f, then LidarDevice.cpp:383-391).

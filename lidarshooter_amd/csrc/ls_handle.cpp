@@ -374,6 +374,7 @@ void ls_tracer_destroy(ls_tracer *tr)
     for (int i = 0; i < 3; ++i)
         if (tr->slot_stream[i]) (void)hipStreamSynchronize(tr->slot_stream[i]);
     frame_graph_destroy(tr);
+    ray_query_release(tr);
     release(tr->best_keys_b); release(tr->big_queue_b); release(tr->points_b); release(tr->hits_b); release(tr->pack_status); release(tr->pack_status_ms);
     release(tr->best_keys_c); release(tr->big_queue_c); release(tr->points_c); release(tr->hits_c);
     if (tr->d_n_points_b) (void)hipFree(tr->d_n_points_b);
@@ -491,6 +492,7 @@ long ls_get_info(ls_tracer *tr, int what)
     case LS_INFO_EMIT_POINTS: return (long)tr->opt_emit_points;
     case LS_INFO_FRAME_GRAPH_PATCH_WAITS: return (long)tr->fg_patch_waits;
     case LS_INFO_BVH_WIDE: return (tr->bvh_inst && tr->wide_valid && tr->wide_in_use) ? 1 : 0;
+    case LS_INFO_RAY_QUERY_BUILT: return tr->rq.last_built;
     default: return fail(tr, LS_ERR_INVALID_ARGUMENT, "unknown info key");
     }
 }

@@ -5,6 +5,7 @@
 //   ls_registry.cpp  ITracer's geometry bookkeeping: add / remove / update (EmbreeTracer.cpp:115-288), uploads
 //   ls_commit.cpp    commitScene: layout, group-culling data, BVH build / refit / instanced hierarchies
 //   ls_trace.cpp     traceScene: output buffers, frames in flight, the per-frame launch sequence, stage timings
+//   ls_rays.cpp      ls_trace_rays: the query set of per-geometry hierarchies (built lazily), batches of geometries per launch
 //   ls_host_pool.cpp worker threads for host-side copies, point expansion
 //   ls_debug.cpp     include/lidarshooter_hip_debug.h (tests and bench.py only)
 #pragma once
@@ -64,6 +65,9 @@ struct Geometry {
     bool blas_topo_dirty = true;   // ... the topology did (vertices alone: the sorted order stays, the hierarchy is refitted)
     uint64_t blas_sorted_epoch = 0;   // key_scratch_epoch at which this geometry's sorted keys were written (0: never)
     float mesh_maxabs = 0.0f;   // largest |coordinate| of the mesh as uploaded (read back when that hierarchy is built)
+    // which upload the vertices / indices are (ls_tracer::upload_seq at the time): the ray-query set compares them with what its
+    // hierarchies were built from (blas_dirty is the frame path's, consumed by the commit)
+    uint64_t vert_gen = 0, idx_gen = 0;
     const void *raw() const { return shared_raw ? shared_raw : d_raw; }
     const uint32_t *idx() const { return shared_idx ? shared_idx : d_idx; }
     float affine[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
@@ -252,6 +256,38 @@ struct ls_tracer {
     uint32_t last_slot = 0xFFFFFFFFu;   // the frame issued last: its stream of the three-stream rotation (none: it ran on `stream`)
     hipStream_t last_stream = nullptr;
 
+    // ls_trace_rays (ls_rays.cpp): a hierarchy set of its own -- nothing here is read or written by the frame path, so that
+    // frames issued after a query on other streams may overlap it
+    struct RayQuerySlot {
+        bool valid = false;
+        int geom_id = -1;
+        uint64_t vert_gen = 0, idx_gen = 0;   // the uploads it was built from
+        bool sensor_frame = false;            // built over the sensor-frame vertices (no usable mesh-space inverse) ...
+        float affine[12], rinv[9], t[3];      // ... for this pose
+        float maxabs = 0.0f;                  // largest |coordinate| of the vertices it was built over
+    };
+    struct RayQuery {
+        lsi::DevBuf<ls::TriRecord> records;
+        lsi::DevBuf<ls::FatNode> nodes;
+        lsi::DevBuf<ls::WideNode> wide_nodes;
+        lsi::DevBuf<float4> range_boxes;
+        std::vector<InstSlot> slots;           // per layout entry, as inst_layout
+        lsi::DevBuf<float> verts;              // build input: packed vertices (mesh space, or sensor frame)
+        lsi::DevBuf<uint32_t> keys_a, keys_b, vals_b;   // per-geometry slices; keys_b / vals_b keep each geometry's sorted order (its refit)
+        lsi::DevBuf<uint8_t> sort_temp;
+        uint32_t *d_maxabs = nullptr;          // kMaxGeoms words
+        uint32_t *d_counters = nullptr;        // ray counter of each launch (kMaxGeoms / kGeomsPerLaunch words)
+        lsi::DevBuf<uint32_t> spill;
+        lsi::DevBuf<uint8_t> io;               // ls_trace_rays_host: rays, then hit records
+        std::vector<RayQuerySlot> built;       // per layout entry
+        std::vector<int> layout_ids;           // geometry ids of the layout the slots were made for ...
+        std::vector<uint32_t> layout_firsts;   // ... and their first vertex, first triangle in it
+        uint32_t leaf = 0;
+        hipEvent_t ev_ready = nullptr, ev_done = nullptr;
+        long last_built = 0;                   // LS_INFO_RAY_QUERY_BUILT
+    } rq;
+    uint64_t upload_seq = 0;
+
     // options / measurement
     int opt_timing = 0;  // 0 off, 1 every stage, 2 only the trace kernel
     bool opt_count = false;
@@ -353,6 +389,29 @@ void expand_points_range(uint8_t *dst_points32, const uint8_t *compact16, size_t
 void expand_hits_range(uint8_t *dst_points32, const uint8_t *hits8, size_t count, const float *sin_theta, const float *cos_theta,
                        const float *cs_phi, uint32_t V, uint32_t H);
 void pool_run(size_t n, const std::function<void(size_t)> &fn);   // fn(0) .. fn(n-1) on the worker threads and the caller
+
+// A set of per-geometry hierarchies: the frame path's instanced one (records / nodes / wide_nodes / range_boxes / inst_layout,
+// ls_commit.cpp) or the ray-query set (ls_tracer::RayQuery).  hier_layout gives every geometry of `order` its slices (slot
+// i: nodes, records, range boxes) and sizes the arrays; hier_build (re)builds or refits the hierarchy of slot i from the
+// geometry's vertices through (A, R, T) -- identity for mesh space -- with the kernels of the classic build.
+struct HierSet {
+    DevBuf<ls::TriRecord> *records;
+    DevBuf<ls::FatNode> *nodes;
+    DevBuf<ls::WideNode> *wide;                 // (nullptr: no four-wide twins)
+    DevBuf<float4> *range_boxes;
+    std::vector<ls_tracer::InstSlot> *slots;
+    DevBuf<float> *verts;
+    DevBuf<uint32_t> *keys_a, *keys_b, *vals_b;
+    DevBuf<uint8_t> *sort_temp;
+    uint32_t *d_maxabs;                         // one word per slot, zero before the build
+};
+int hier_layout(ls_tracer *tr, HierSet &hs, const std::vector<Geometry *> &order, uint32_t leaf_size, uint32_t *n_nodes);
+// refit: the slot's sorted keys / values and its nodes are those of the same topology (only the vertices changed); widen: make the
+// four-wide twins now (the slot's wide_made says whether they were made)
+int hier_build(ls_tracer *tr, HierSet &hs, hipStream_t s, size_t i, const Geometry &ge, uint32_t vfirst, uint32_t tfirst, const float *A12,
+               const float *R9, const float *T3, uint32_t leaf_size, bool refit, bool widen);
+// ls_rays.cpp
+void ray_query_release(ls_tracer *tr);
 
 }  // namespace lsi
 

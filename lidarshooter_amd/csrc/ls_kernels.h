@@ -234,6 +234,30 @@ void launch_trace_instanced(hipStream_t s, uint32_t grid_blocks, const SensorTab
                             uint32_t *gid_out, uint32_t *spill, unsigned long long *visit_counts /* nullptr = do not count */);
 // the four-wide twins of a hierarchy's n_leaves - 1 binary nodes (after every build or refit of it)
 void launch_widen(hipStream_t s, const FatNode *nodes, uint32_t n_leaves, WideNode *wide);
+
+// ls_trace_rays (ls_rays.hip): closest hits of caller-supplied rays (32-byte records: origin, tmin, direction, tmax, in the
+// sensor frame) over the query set's hierarchies, one per geometry in mesh space (ls_rays.cpp).  A geometry whose mesh ->
+// sensor map has no usable inverse has its hierarchy over its SENSOR-frame vertices instead: xform 0, minv = identity, o = 0.
+struct RayGeom {
+    uint32_t node_first, rec_first;   // this geometry's nodes / records inside the query set's arrays
+    uint32_t n_leaves;                // 0: nothing to trace
+    uint32_t n_tris;                  // its last leaf may be short
+    uint32_t gid_first;               // global triangle id of its triangle 0
+    uint32_t geom_id, prim_shift;     // ls_hit.geom, and primID = local triangle >> prim_shift (quads)
+    int xform;                        // 0: records hold sensor-frame vertices, 1: full transform, 2: A is the identity
+    float o[3];                       // the sensor origin in mesh space (a ray's origin maps to minv * o_ray + o)
+    float eps;                        // box widening for a ray from the sensor origin ...
+    float eps_o;                      // ... plus eps_o per metre of the ray origin's largest |coordinate|
+    float minv[9];                    // sensor-space vector -> mesh-space vector (row-major)
+    Affine m;                         // mesh -> sensor, as everywhere else
+};
+struct RayBatch {
+    uint32_t n;
+    uint32_t first;                   // 1: the first launch of a query (no running best in `out` yet)
+    RayGeom g[kGeomsPerLaunch];
+};
+void launch_trace_rays(hipStream_t s, uint32_t grid_blocks, const void *rays, uint32_t n, const RayBatch &batch, const WideNode *wide,
+                       const TriRecord *records, uint32_t leaf_size, void *out, uint32_t *counter, uint32_t *spill);
 void launch_rowcount(hipStream_t s, const uint32_t *gid, uint32_t nrays, uint32_t *row_counts, uint32_t *queue_heads = nullptr);   // queue_heads: zeroed for the next k_trace
 // Progress of a synchronous frame whose compact points go straight to pinned host memory (ls_trace_scene_begin /
 // ls_trace_scene_expand): the device publishes, with system-scope release, (1) the frame's hit count as the pack pass

@@ -1,0 +1,253 @@
+// ls_rays.cpp -- ls_trace_rays / ls_trace_rays_host: closest hits of caller-supplied rays against the committed scene.
+//
+// The query set (ls_tracer::RayQuery) is a hierarchy set of its own -- one hierarchy per geometry, built by the kernels of
+// the instanced commit (hier_layout / hier_build, ls_commit.cpp) into buffers nothing in the frame path reads or writes,
+// its sort scratch included, so that no later commit or frame can leave it stale keys, and frames issued after a query on
+// other streams may overlap it.  It is built lazily: the first query after a commit builds what the set lacks.
+//   * mesh space when the geometry's mesh -> sensor map has a usable inverse (inst_inverse): a pose change costs nothing;
+//   * the SENSOR frame otherwise (a singular pose -- a mesh scaled to zero to hide it -- or a scale ratio above 10^3):
+//     identity direction map, rebuilt when its pose changes.
+// What a slot was built from (vertex / index upload, mode, pose) is kept per slot: a query after a commit that changed only
+// poses builds nothing; new vertices refit that geometry (its sorted order is kept in the set's own keys), new indices rebuild it.
+#include "ls_internal.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace lsi {
+
+namespace {
+
+constexpr uint32_t kMaxRayLaunches = (uint32_t)ls::kMaxGeoms / (uint32_t)ls::kGeomsPerLaunch;
+
+bool same_floats(const float *a, const float *b, size_t n) { return std::memcmp(a, b, n * sizeof(float)) == 0; }
+
+// the query set brought up to date with the committed layout and the geometries' current data (stream-ordered on s)
+int ray_query_prepare(ls_tracer *tr, hipStream_t s, std::vector<Geometry *> &order, std::vector<bool> &sensor_frame)
+{
+    ls_tracer::RayQuery &q = tr->rq;
+    const size_t n = tr->layout.size();
+    order.assign(n, nullptr);
+    sensor_frame.assign(n, false);
+    std::vector<int> ids(n);
+    std::vector<uint32_t> firsts(2 * n);   // where every geometry's vertices and triangles start in the layout
+    for (size_t i = 0; i < n; ++i) {
+        auto it = tr->geoms.find(tr->layout[i].name);
+        if (it == tr->geoms.end()) return fail(tr, LS_ERR_NOT_COMMITTED, "geometry removed since the last commit");
+        Geometry &ge = it->second;
+        if (ge.id != tr->slot_geom_ids[i] || ge.n_tris != tr->slot_tri_first[i + 1] - tr->slot_tri_first[i] || !ge.has_verts || !ge.has_idx)
+            return fail(tr, LS_ERR_NOT_COMMITTED, "the geometries changed since the last commit");
+        order[i] = &ge;
+        ids[i] = ge.id;
+        firsts[2 * i] = tr->layout[i].vfirst;
+        firsts[2 * i + 1] = tr->layout[i].tfirst;
+        double minv[9], o[3], cond;
+        sensor_frame[i] = !inst_inverse(tr, ge, minv, o, &cond);
+    }
+    const uint32_t g = tr->committed_leaf_size;
+    HierSet hs{&q.records, &q.nodes, &q.wide_nodes, &q.range_boxes, &q.slots, &q.verts, &q.keys_a, &q.keys_b, &q.vals_b, &q.sort_temp, nullptr};
+    int rc;
+    const bool fresh = q.layout_ids != ids || q.layout_firsts != firsts || q.leaf != g || q.slots.size() != n;
+    if (fresh) {
+        uint32_t nodes = 0;
+        if ((rc = hier_layout(tr, hs, order, g, &nodes))) return rc;
+        q.built.assign(n, ls_tracer::RayQuerySlot());
+        q.layout_ids = ids;
+        q.layout_firsts = firsts;
+        q.leaf = g;
+    }
+    std::vector<uint8_t> todo(n, 0);   // 1 build, 2 refit
+    long count = 0;
+    uint32_t biggest = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const Geometry &ge = *order[i];
+        const ls_tracer::RayQuerySlot &b = q.built[i];
+        const bool sf = sensor_frame[i];
+        bool same = b.valid && b.geom_id == ge.id && b.idx_gen == ge.idx_gen && b.sensor_frame == sf;
+        if (same && b.vert_gen == ge.vert_gen && (!sf || (same_floats(b.affine, ge.affine, 12) && same_floats(b.rinv, tr->rinv, 9) &&
+                                                         same_floats(b.t, tr->t, 3))))
+            continue;
+        todo[i] = same ? 2 : 1;   // (same order, same topology: the vertices moved -- a refit)
+        ++count;
+        biggest = std::max(biggest, ge.n_tris);
+    }
+    q.last_built = count;
+    if (!count) return LS_OK;
+    if ((rc = ensure(tr, q.verts, (size_t)tr->n_verts * 3))) return rc;
+    if ((rc = ensure(tr, q.keys_a, tr->n_tris))) return rc;
+    if ((rc = ensure(tr, q.keys_b, tr->n_tris))) return rc;
+    if ((rc = ensure(tr, q.vals_b, tr->n_tris))) return rc;
+    if ((rc = ensure(tr, q.sort_temp, ls::sort_temp_bytes(biggest)))) return rc;
+    if (!q.d_maxabs) LS_HIP(hipMalloc(reinterpret_cast<void **>(&q.d_maxabs), ls::kMaxGeoms * 4));
+    LS_HIP(hipMemsetAsync(q.d_maxabs, 0, n * 4, s));
+    hs.d_maxabs = q.d_maxabs;
+    static const float kIdA[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, kIdR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, kZero[3] = {0, 0, 0};
+    for (size_t i = 0; i < n; ++i) {
+        if (!todo[i]) continue;
+        const Geometry &ge = *order[i];
+        const bool sf = sensor_frame[i];
+        // mesh space: the vertices as uploaded; sensor frame: through the frame's own transform (the bits of k_transform)
+        if ((rc = hier_build(tr, hs, s, i, ge, tr->layout[i].vfirst, tr->layout[i].tfirst, sf ? ge.affine : kIdA, sf ? tr->rinv : kIdR,
+                             sf ? tr->t : kZero, g, todo[i] == 2, true)))
+            return rc;
+    }
+    LS_HIP(hipGetLastError());
+    // the extent of every rebuilt hierarchy (its box widening is scaled by it)
+    std::vector<uint32_t> bits(n, 0u);
+    LS_HIP(hipMemcpyAsync(bits.data(), q.d_maxabs, n * 4, hipMemcpyDeviceToHost, s));
+    LS_HIP(hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; ++i) {
+        if (!todo[i]) continue;
+        const Geometry &ge = *order[i];
+        ls_tracer::RayQuerySlot &b = q.built[i];
+        b.valid = true;
+        b.geom_id = ge.id;
+        b.vert_gen = ge.vert_gen;
+        b.idx_gen = ge.idx_gen;
+        b.sensor_frame = sensor_frame[i];
+        std::memcpy(b.affine, ge.affine, sizeof(b.affine));
+        std::memcpy(b.rinv, tr->rinv, sizeof(b.rinv));
+        std::memcpy(b.t, tr->t, sizeof(b.t));
+        std::memcpy(&b.maxabs, &bits[i], 4);
+    }
+    return LS_OK;
+}
+
+// the launch descriptor of layout entry i for this query
+void ray_geom(const ls_tracer *tr, size_t i, const Geometry &ge, bool sensor_frame, ls::RayGeom &rg)
+{
+    const ls_tracer::RayQuery &q = tr->rq;
+    const ls_tracer::InstSlot &sl = q.slots[i];
+    std::memset(static_cast<void *>(&rg), 0, sizeof(rg));
+    rg.node_first = sl.node_first;
+    rg.rec_first = sl.rec_first;
+    rg.n_leaves = sl.n_leaves;
+    rg.n_tris = ge.n_tris;
+    rg.gid_first = tr->layout[i].tfirst;
+    rg.geom_id = (uint32_t)ge.id;
+    rg.prim_shift = ge.quad ? 1u : 0u;
+    std::memcpy(rg.m.a, ge.affine, sizeof(rg.m.a));
+    std::memcpy(rg.m.rinv, tr->rinv, sizeof(rg.m.rinv));
+    std::memcpy(rg.m.t, tr->t, sizeof(rg.m.t));
+    const float maxabs = q.built[i].maxabs;
+    double minv[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0}, cond = 1.0;
+    if (sensor_frame) {
+        rg.xform = 0;
+    } else {
+        inst_inverse(tr, ge, minv, o, &cond);
+        static const float kIdentity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        rg.xform = std::memcmp(ge.affine, kIdentity, sizeof(kIdentity)) == 0 ? 2 : 1;
+    }
+    float omax = 0.0f, row = 0.0f;
+    for (int k = 0; k < 3; ++k) { rg.o[k] = (float)o[k]; omax = std::max(omax, std::fabs(rg.o[k])); }
+    for (int k = 0; k < 9; ++k) rg.minv[k] = (float)minv[k];
+    for (int r = 0; r < 3; ++r) row = std::max(row, std::fabs(rg.minv[3 * r]) + std::fabs(rg.minv[3 * r + 1]) + std::fabs(rg.minv[3 * r + 2]));
+    // The frame's widening (ls_trace.cpp) for a ray from the sensor origin -- the rounding of o and of minv * d along the way to
+    // any box, times the conditioning of the map, a factor of ten in hand -- plus what a ray origin o_r adds: o_m = minv * o_r
+    // + o rounds by a few ulps of ||minv|| |o_r| + |o|, and the way to a box grows by as much ("Ray queries").
+    const float c = 4e-6f * (float)std::max(1.0, cond);
+    rg.eps = c * (omax + 2.0f * maxabs);
+    rg.eps_o = 2.0f * c * row;
+}
+
+}  // namespace
+
+void ray_query_release(ls_tracer *tr)
+{
+    ls_tracer::RayQuery &q = tr->rq;
+    if (q.ev_done) (void)hipEventSynchronize(q.ev_done);
+    release(q.records); release(q.nodes); release(q.wide_nodes); release(q.range_boxes); release(q.verts);
+    release(q.keys_a); release(q.keys_b); release(q.vals_b); release(q.sort_temp); release(q.spill); release(q.io);
+    if (q.d_maxabs) (void)hipFree(q.d_maxabs);
+    if (q.d_counters) (void)hipFree(q.d_counters);
+    if (q.ev_ready) (void)hipEventDestroy(q.ev_ready);
+    if (q.ev_done) (void)hipEventDestroy(q.ev_done);
+    q.d_maxabs = q.d_counters = nullptr;
+    q.ev_ready = q.ev_done = nullptr;
+}
+
+namespace {
+
+int trace_rays_locked(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (n && (!d_rays || !d_out)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null rays or output");
+    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & 15u)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "rays and hit records must be 16-byte aligned");
+    if (n > 0xFFF00000u) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
+    ls_tracer::RayQuery &q = tr->rq;
+    q.last_built = 0;
+    if (!tr->committed || tr->n_tris == 0) return -1;   // as ls_trace_scene; nothing is written
+    if (!n) return LS_OK;
+    int rc;
+    // after everything already issued on the handle: its frames in flight, its mesh copies
+    if ((rc = flush_pipeline(tr))) return rc;
+    if (!q.ev_ready) LS_HIP(hipEventCreateWithFlags(&q.ev_ready, hipEventDisableTiming));
+    if (!q.ev_done) LS_HIP(hipEventCreateWithFlags(&q.ev_done, hipEventDisableTiming));
+    if (s != tr->stream) {
+        LS_HIP(hipEventRecord(q.ev_ready, tr->stream));
+        LS_HIP(hipStreamWaitEvent(s, q.ev_ready, 0));
+    }
+    std::vector<Geometry *> order;
+    std::vector<bool> sensor_frame;
+    if ((rc = ray_query_prepare(tr, s, order, sensor_frame))) return rc;
+    if ((rc = ensure(tr, q.spill, ls::trace_spill_bytes(tr->trace_blocks) / 4))) return rc;
+    if (!q.d_counters) LS_HIP(hipMalloc(reinterpret_cast<void **>(&q.d_counters), kMaxRayLaunches * 4));
+    const uint32_t launches = (uint32_t)((order.size() + ls::kGeomsPerLaunch - 1) / ls::kGeomsPerLaunch);
+    LS_HIP(hipMemsetAsync(q.d_counters, 0, (size_t)launches * 4, s));
+    // geometries in ascending geomID batches of kGeomsPerLaunch: each launch starts from the running best of the ones before
+    for (uint32_t b = 0; b < launches; ++b) {
+        ls::RayBatch batch;
+        std::memset(static_cast<void *>(&batch), 0, sizeof(batch));
+        const size_t first = (size_t)b * ls::kGeomsPerLaunch, last = std::min(order.size(), first + ls::kGeomsPerLaunch);
+        batch.n = (uint32_t)(last - first);
+        batch.first = b == 0 ? 1u : 0u;
+        for (size_t i = first; i < last; ++i) ray_geom(tr, i, *order[i], sensor_frame[i], batch.g[i - first]);
+        ls::launch_trace_rays(s, tr->trace_blocks, d_rays, n, batch, q.wide_nodes.p, q.records.p, q.leaf, d_out, q.d_counters + b, q.spill.p);
+    }
+    LS_HIP(hipGetLastError());
+    // what the handle issues next (mesh copies, commits, the next query) comes after this query; frames of the three-stream
+    // rotation that need none of that do not wait for it
+    if (s != tr->stream) {
+        LS_HIP(hipEventRecord(q.ev_done, s));
+        LS_HIP(hipStreamWaitEvent(tr->stream, q.ev_done, 0));
+    }
+    return LS_OK;
+}
+
+}  // namespace
+
+}  // namespace lsi
+
+using namespace lsi;
+
+extern "C" {
+
+int ls_trace_rays(ls_tracer *tr, void *hip_stream, const void *d_rays, uint32_t n, void *d_out)
+{
+    LS_ENTER(tr);
+    return trace_rays_locked(tr, hip_stream ? static_cast<hipStream_t>(hip_stream) : tr->stream, d_rays, n, d_out);
+}
+
+int ls_trace_rays_host(ls_tracer *tr, const void *rays, uint32_t n, void *out)
+{
+    LS_ENTER(tr);
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (n && (!rays || !out)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null rays or output");
+    if (n > 0xFFF00000u) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
+    tr->rq.last_built = 0;
+    if (!tr->committed || tr->n_tris == 0) return -1;   // (before n = 0: the same answer as ls_trace_rays)
+    if (!n) return LS_OK;
+    ls_tracer::RayQuery &q = tr->rq;
+    hipStream_t s = tr->stream;
+    int rc;
+    if ((rc = flush_pipeline(tr))) return rc;
+    if ((rc = ensure(tr, q.io, (size_t)n * 48))) return rc;   // (a growing buffer: the frame path's frames in flight never read it)
+    uint8_t *d_rays = q.io.p, *d_out = q.io.p + (size_t)n * 32;
+    LS_HIP(hipMemcpyAsync(d_rays, rays, (size_t)n * 32, hipMemcpyHostToDevice, s));
+    if ((rc = trace_rays_locked(tr, s, d_rays, n, d_out))) return rc;
+    LS_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, s));
+    LS_HIP(hipStreamSynchronize(s));
+    return LS_OK;
+}
+
+}  // extern "C"

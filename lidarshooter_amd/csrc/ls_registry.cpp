@@ -144,6 +144,7 @@ int update_common(ls_tracer *tr, const char *name, const float *affine, const vo
         g.has_verts = true;
         g.bounds_stale = true;   // the caller's buffer may hold anything now
         g.blas_dirty = true;
+        g.vert_gen = ++tr->upload_seq;
         if (idx && g.quad) {
             // quads are traced as triangle pairs: the caller's indices are converted into a library-owned array
             if (!g.d_idx) LS_HIP(hipMalloc(reinterpret_cast<void **>(&g.d_idx), (size_t)g.n_tris * 12 + 4));
@@ -154,7 +155,11 @@ int update_common(ls_tracer *tr, const char *name, const float *affine, const vo
             g.shared_idx = nullptr;
             if (!g.has_idx) tr->layout_dirty = true;
             g.has_idx = true; g.idx_dirty = true; tr->tris_rebased = false; g.order_stale = true; g.blas_dirty = g.blas_topo_dirty = true;
-        } else if (idx) { g.shared_idx = idx; g.has_idx = true; g.idx_dirty = true; tr->tris_rebased = false; g.order_stale = true; g.blas_dirty = g.blas_topo_dirty = true; }
+            g.idx_gen = ++tr->upload_seq;
+        } else if (idx) {
+            g.shared_idx = idx; g.has_idx = true; g.idx_dirty = true; tr->tris_rebased = false; g.order_stale = true; g.blas_dirty = g.blas_topo_dirty = true;
+            g.idx_gen = ++tr->upload_seq;
+        }
         if (idx) return check_indices_later(tr, g);   // (the caller's buffer may hold anything: every hand-over is looked at)
         return LS_OK;
     }
@@ -189,11 +194,13 @@ int update_common(ls_tracer *tr, const char *name, const float *affine, const vo
         g.has_verts = true;
         g.bounds_stale = true;
         g.blas_dirty = true;
+        g.vert_gen = ++tr->upload_seq;
     }
     if (idx) {
         g.shared_idx = nullptr;
         g.order_stale = true;
         g.blas_dirty = g.blas_topo_dirty = true;
+        g.idx_gen = ++tr->upload_seq;
         const size_t bytes = g.quad ? (size_t)g.n_elems * 16 : (size_t)g.n_tris * 12;
         if (!g.d_idx) LS_HIP(hipMalloc(reinterpret_cast<void **>(&g.d_idx), (size_t)g.n_tris * 12 + 4));
         if (g.quad && !g.d_quad_idx) LS_HIP(hipMalloc(reinterpret_cast<void **>(&g.d_quad_idx), bytes ? bytes : 4));

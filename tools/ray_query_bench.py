@@ -1,0 +1,82 @@
+"""ls_trace_rays at SYN-1M: the sensor's own 524 288 rays (SYN-128 raster) against the BVH frame's k_trace_inst on the same
+scene in the same run, 1 M incoherent rays, and the first query's lazy build.  Prints host-side event timings; for kernel
+times run it under the profiler in a run of its own:
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/ray_query_bench.py
+usage: python tools/ray_query_bench.py [--reps N]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    import torch
+
+    from lidarshooter_amd import capi, synth
+    from oracle import oracle as O
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    a = ap.parse_args()
+    base = O.load_sensor(os.path.join(ROOT, "tests", "golden", "data", "config", "hesai-pandar-XT-32-lidar_0000.json"))
+    vert = synth.syn_vertical(128)
+    verts, tris = synth.syn_1m()
+    tr = capi.Tracer(vert, 0.0, 360.0, 4096, base.Rinv, base.t, device=0)
+    tr.setOption(capi.LS_OPT_ENGINE, capi.ENGINE_BVH)
+    assert tr.addGeometry("grid", verts.shape[0], tris.shape[0]) == 0
+    tr.updateGeometry("grid", capi.IDENTITY_AFFINE, verts, tris)
+    assert tr.commitScene() == 0
+    for i in range(a.reps):   # BVH frames: k_trace_inst (the four-wide twins are made after the first frames)
+        assert tr.traceScene(i)[0] == 0
+    n = tr.getTotalRays()
+    d_rays = torch.zeros(n * 32, dtype=torch.uint8, device="cuda:0")
+    tr.generateRaysAos(d_rays.data_ptr(), None)
+    out = torch.zeros(n * 16, dtype=torch.uint8, device="cuda:0")
+    tr.synchronize()
+    t0 = time.perf_counter()
+    assert tr.traceRaysDevice(d_rays.data_ptr(), n, out.data_ptr()) == 0
+    tr.synchronize()
+    first_ms = (time.perf_counter() - t0) * 1e3
+    built = tr.info(capi.LS_INFO_RAY_QUERY_BUILT)
+
+    def timed(rays, m, reps):
+        o = torch.zeros(m * 16, dtype=torch.uint8, device="cuda:0")
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s = torch.cuda.Stream()   # (a stream of its own: 0 would mean the handle's stream)
+        tr.traceRaysDevice(rays.data_ptr(), m, o.data_ptr(), s.cuda_stream)
+        e0.record(s)
+        for _ in range(reps):
+            tr.traceRaysDevice(rays.data_ptr(), m, o.data_ptr(), s.cuda_stream)
+        e1.record(s)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps, o
+
+    own_ms, o = timed(d_rays, n, a.reps)
+    hits = int(np.count_nonzero(o.cpu().numpy().view(np.uint32).reshape(n, 4)[:, 1] != 0xFFFFFFFF))
+    # 1 M incoherent rays: origins anywhere in the scene's box (sensor frame), directions uniform on the sphere
+    rng = np.random.default_rng(1)
+    m = 1 << 20
+    r = np.zeros((m, 8), np.float32)
+    R = np.asarray(base.Rinv, np.float64).reshape(3, 3)
+    ow = np.c_[rng.uniform(-50, 50, (m, 2)), rng.uniform(0.2, 5.0, m)]
+    r[:, 0:3] = (R @ (ow - np.asarray(base.t, np.float64)).T).T
+    dw = rng.normal(size=(m, 3))
+    r[:, 4:7] = (R @ (dw / np.linalg.norm(dw, axis=1)[:, None]).T).T
+    r[:, 7] = np.inf
+    d_inc = torch.from_numpy(r.view(np.uint8).reshape(-1)).to("cuda:0")
+    inc_ms, o = timed(d_inc, m, a.reps)
+    inc_hits = int(np.count_nonzero(o.cpu().numpy().view(np.uint32).reshape(m, 4)[:, 1] != 0xFFFFFFFF))
+    print(f"first query (lazy build of {built} hierarchy + trace): {first_ms:.2f} ms host")
+    print(f"sensor's own rays: {n} rays, {hits} hits, {own_ms * 1e3:.1f} us per query")
+    print(f"incoherent rays: {m} rays, {inc_hits} hits, {inc_ms * 1e3:.1f} us per query = {m / inc_ms / 1e3:.0f} Mrays/s")
+    tr.close()
+
+
+if __name__ == "__main__":
+    main()
