@@ -429,7 +429,7 @@ int ls_parallel_copy(void *dst, const void *src, uint64_t bytes);
 #define LS_INFO_EMIT_POINTS 14       /* the current LS_OPT_EMIT_POINTS                                            */
 #define LS_INFO_BVH_WIDE 16                /* 1: the last trace walked the four-wide nodes (LS_OPT_BVH_WIDE, instanced mode, every geometry's made) */
 #define LS_INFO_FRAME_GRAPH_PATCH_WAITS 15 /* patches that first had to wait for the previous launch of their graph (the host ran more than three frames ahead) */
-#define LS_INFO_RAY_QUERY_BUILT 17         /* geometries whose query hierarchy the last ls_trace_rays* built or refitted (see there) */
+#define LS_INFO_RAY_QUERY_BUILT 17         /* geometries whose query hierarchy the last ls_trace_rays* / ls_occluded_rays* built or refitted (see there) */
 long ls_get_info(ls_tracer *tr, int what);
 
 /* Mean stage durations (milliseconds, hipEvents on the handle's stream) over every frame recorded
@@ -468,7 +468,8 @@ int ls_generate_rays_aos(ls_tracer *tr, void *d_rays, void *d_hits);
 
 /* ---- ray queries: the closest hit of each of n CALLER rays against the scene as of the last successful ls_commit_scene
  * (the geometries' current poses, as a frame would use them) -- scan patterns that are not a uniform raster, several sensors
- * on one scene, "what does this ray hit", "is anything between A and B" (a ray with a tmax).
+ * on one scene, "what does this ray hit", "is anything between A and B" (a ray with a tmax; ls_occluded_rays below answers
+ * that one without searching for the closest hit).
  *   d_rays: n lidarshooter::Ray records, 32 bytes each (origin xyz f32@0, tmin f32@12, direction xyz f32@16, tmax f32@28) --
  *           the layout ls_generate_rays_aos writes -- in the handle's SENSOR frame (the frame of ls_frame.points32; a caller
  *           whose rays are in the world frame creates the handle with Rinv = I, t = 0).  16-byte aligned.
@@ -492,6 +493,21 @@ int ls_generate_rays_aos(ls_tracer *tr, void *d_rays, void *d_hits);
 int ls_trace_rays(ls_tracer *tr, void *hip_stream, const void *d_rays, uint32_t n, void *d_out);
 /* The same with host memory (pageable) in and out, on the handle's stream; returns when out is filled. */
 int ls_trace_rays_host(ls_tracer *tr, const void *rays, uint32_t n, void *out);
+
+/* ---- occlusion queries: whether each of n CALLER rays hits anything -- the any-hit half of the ray queries (Embree's
+ * rtcOccluded, OptiX's terminate-on-first-hit): line of sight, visibility labels, multi-sensor coverage, shadow rays.
+ *   d_rays: as ls_trace_rays (n 32-byte lidarshooter::Ray records in the sensor frame, 16-byte aligned).
+ *   d_out:  n bytes in ray order, any alignment: 1 when some triangle of the committed scene passes the frame's exact test
+ *           from the ray's origin with tmin <= t <= tmax, else 0 -- by definition exactly when ls_trace_rays, in the same state,
+ *           reports a hit (geom != 0xFFFFFFFF) for that ray.  Degenerate rays (as there) give 0.
+ * The walk stops at the first triangle that passes: no closest hit is searched for, no tie broken.
+ * A segment A -> B: origin A, direction B - A, tmax = 1 - eps (B on a surface: its own triangle is hit at t ~ 1).
+ * Return codes, stream order, the frame graph and n limits, and the query hierarchies are those of ls_trace_rays; both queries
+ * share the hierarchies (what one built or refitted serves the other), and LS_INFO_RAY_QUERY_BUILT reports for whichever ran
+ * last. */
+int ls_occluded_rays(ls_tracer *tr, void *hip_stream, const void *d_rays, uint32_t n, void *d_out);
+/* The same with host memory (pageable) in and out, on the handle's stream; returns when out is filled. */
+int ls_occluded_rays_host(ls_tracer *tr, const void *rays, uint32_t n, void *out);
 
 #ifdef __cplusplus
 }

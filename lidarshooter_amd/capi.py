@@ -50,7 +50,7 @@ SYMBOLS = (
     "ls_get_visit_counts", "ls_generate_rays", "ls_generate_rays_aos", "ls_geometry_type", "ls_tracer_order_after_last_frame", "ls_tracer_wait_event", "ls_tracer_next_frame_waits", "ls_trace_scene_begin", "ls_trace_scene_expand",
     "ls_frame_graph_begin", "ls_frame_graph_stream", "ls_frame_graph_end", "ls_frame_graph_reset",
     "ls_tracer_set_sensor", "ls_tracer_set_sensor_tables", "ls_expand_gathered_hits_sized",
-    "ls_trace_rays", "ls_trace_rays_host",
+    "ls_trace_rays", "ls_trace_rays_host", "ls_occluded_rays", "ls_occluded_rays_host",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
 DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_scene_size", "ls_debug_download_scene",
@@ -174,6 +174,8 @@ def load() -> C.CDLL:
     L.ls_generate_rays_aos.argtypes = [vp, vp, vp]
     L.ls_trace_rays.argtypes = [vp, vp, vp, u32, vp]
     L.ls_trace_rays_host.argtypes = [vp, vp, u32, vp]
+    L.ls_occluded_rays.argtypes = [vp, vp, vp, u32, vp]
+    L.ls_occluded_rays_host.argtypes = [vp, vp, u32, vp]
     L.ls_geometry_type.argtypes = [vp, C.c_char_p]
     L.ls_debug_dense_hits.argtypes = [vp, f32p, u32p]
     L.ls_debug_trace_bruteforce.argtypes = [vp, f32p, u32p]
@@ -462,15 +464,20 @@ class Tracer:
     def generateRays(self, d_dx: int, d_dy: int, d_dz: int):
         return self._check(self.L.ls_generate_rays(self.h, d_dx, d_dy, d_dz), "ls_generate_rays")
 
-    def traceRays(self, rays):
-        """Closest hits of caller rays (ls_trace_rays_host): `rays` float32 (n, 8) -- origin xyz, tmin, direction xyz, tmax per
-        row, the RAY_DTYPE layout, in the sensor frame -- or a RAY_DTYPE array.  -> (rc, HIT_DTYPE[n]); rc = -1 (no commit, empty
-        scene): every record a miss."""
+    @staticmethod
+    def _ray_array(rays):
         r = np.ascontiguousarray(rays)
         if r.dtype != RAY_DTYPE:
             r = np.ascontiguousarray(r, np.float32)
             if r.ndim != 2 or r.shape[1] != 8:
                 raise ValueError("rays: float32 (n, 8) or RAY_DTYPE")
+        return r
+
+    def traceRays(self, rays):
+        """Closest hits of caller rays (ls_trace_rays_host): `rays` float32 (n, 8) -- origin xyz, tmin, direction xyz, tmax per
+        row, the RAY_DTYPE layout, in the sensor frame -- or a RAY_DTYPE array.  -> (rc, HIT_DTYPE[n]); rc = -1 (no commit, empty
+        scene): every record a miss."""
+        r = self._ray_array(rays)
         n = r.shape[0]
         out = np.zeros(n, HIT_DTYPE)
         rc = self.L.ls_trace_rays_host(self.h, r.ctypes.data if n else None, n, out.ctypes.data if n else None)
@@ -488,6 +495,25 @@ class Tracer:
         as an int, None: the handle's), no wait.  -> 0, or -1 on an empty / uncommitted scene (d_out not written)."""
         rc = self.L.ls_trace_rays(self.h, stream, d_rays, n, d_out)
         return -1 if rc == -1 else int(self._check(rc, "ls_trace_rays"))
+
+    def occludedRays(self, rays):
+        """Occlusion tests of caller rays (ls_occluded_rays_host): `rays` as traceRays takes them.  -> (rc, bool[n]): True where
+        some triangle lies in [tmin, tmax] along the ray -- exactly where traceRays reports a hit; rc = -1 (no commit, empty
+        scene): every entry False."""
+        r = self._ray_array(rays)
+        n = r.shape[0]
+        out = np.zeros(n, np.uint8)
+        rc = self.L.ls_occluded_rays_host(self.h, r.ctypes.data if n else None, n, out.ctypes.data if n else None)
+        if rc == -1:
+            return -1, np.zeros(n, np.bool_)
+        self._check(rc, "ls_occluded_rays_host")
+        return int(rc), out.view(np.bool_)
+
+    def occludedRaysDevice(self, d_rays: int, n: int, d_out: int, stream=None) -> int:
+        """ls_occluded_rays on device pointers (n 32-byte rays in, n bytes out, 1 = occluded); enqueued on `stream` (a
+        hipStream_t as an int, None: the handle's), no wait.  -> 0, or -1 on an empty / uncommitted scene (d_out not written)."""
+        rc = self.L.ls_occluded_rays(self.h, stream, d_rays, n, d_out)
+        return -1 if rc == -1 else int(self._check(rc, "ls_occluded_rays"))
 
     # ---- test hooks
     def generateRaysAos(self, d_rays: int | None, d_hits: int | None):

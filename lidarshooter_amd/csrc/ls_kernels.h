@@ -258,6 +258,10 @@ struct RayBatch {
 };
 void launch_trace_rays(hipStream_t s, uint32_t grid_blocks, const void *rays, uint32_t n, const RayBatch &batch, const WideNode *wide,
                        const TriRecord *records, uint32_t leaf_size, void *out, uint32_t *counter, uint32_t *spill);
+// ls_occluded_rays: the same walk stopping at a ray's first hit; out = n bytes, 1 = occluded (the first launch writes every byte,
+// a later one only the rays it finds occluded)
+void launch_occluded_rays(hipStream_t s, uint32_t grid_blocks, const void *rays, uint32_t n, const RayBatch &batch, const WideNode *wide,
+                          const TriRecord *records, uint32_t leaf_size, void *out, uint32_t *counter, uint32_t *spill);
 void launch_rowcount(hipStream_t s, const uint32_t *gid, uint32_t nrays, uint32_t *row_counts, uint32_t *queue_heads = nullptr);   // queue_heads: zeroed for the next k_trace
 // Progress of a synchronous frame whose compact points go straight to pinned host memory (ls_trace_scene_begin /
 // ls_trace_scene_expand): the device publishes, with system-scope release, (1) the frame's hit count as the pack pass

@@ -1,4 +1,5 @@
-// ls_rays.cpp -- ls_trace_rays / ls_trace_rays_host: closest hits of caller-supplied rays against the committed scene.
+// ls_rays.cpp -- ls_trace_rays / ls_trace_rays_host: closest hits of caller-supplied rays against the committed scene;
+// ls_occluded_rays / ls_occluded_rays_host: whether each ray hits anything (the same query set and walk, stopping at a hit).
 //
 // The query set (ls_tracer::RayQuery) is a hierarchy set of its own -- one hierarchy per geometry, built by the kernels of
 // the instanced commit (hier_layout / hier_build, ls_commit.cpp) into buffers nothing in the frame path reads or writes,
@@ -168,11 +169,21 @@ void ray_query_release(ls_tracer *tr)
 
 namespace {
 
-int trace_rays_locked(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out)
+// the two queries: what one launch over a geometry batch runs, and what it writes per ray
+struct RayQueryKind {
+    void (*launch)(hipStream_t, uint32_t, const void *, uint32_t, const ls::RayBatch &, const ls::WideNode *, const ls::TriRecord *,
+                   uint32_t, void *, uint32_t *, uint32_t *);
+    size_t out_bytes;   // per ray: an ls_hit (16-byte aligned), or one byte (any address)
+};
+const RayQueryKind kClosest = {ls::launch_trace_rays, 16};
+const RayQueryKind kOccluded = {ls::launch_occluded_rays, 1};
+
+int rays_locked(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out, const RayQueryKind &kind)
 {
     if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
     if (n && (!d_rays || !d_out)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null rays or output");
-    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & 15u)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "rays and hit records must be 16-byte aligned");
+    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & (kind.out_bytes - 1u)))
+        return fail(tr, LS_ERR_INVALID_ARGUMENT, kind.out_bytes == 16 ? "rays and hit records must be 16-byte aligned" : "rays must be 16-byte aligned");
     if (n > 0xFFF00000u) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
     ls_tracer::RayQuery &q = tr->rq;
     q.last_built = 0;
@@ -194,7 +205,7 @@ int trace_rays_locked(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t
     if (!q.d_counters) LS_HIP(hipMalloc(reinterpret_cast<void **>(&q.d_counters), kMaxRayLaunches * 4));
     const uint32_t launches = (uint32_t)((order.size() + ls::kGeomsPerLaunch - 1) / ls::kGeomsPerLaunch);
     LS_HIP(hipMemsetAsync(q.d_counters, 0, (size_t)launches * 4, s));
-    // geometries in ascending geomID batches of kGeomsPerLaunch: each launch starts from the running best of the ones before
+    // geometries in ascending geomID batches of kGeomsPerLaunch: each launch starts from what the ones before found
     for (uint32_t b = 0; b < launches; ++b) {
         ls::RayBatch batch;
         std::memset(static_cast<void *>(&batch), 0, sizeof(batch));
@@ -202,7 +213,7 @@ int trace_rays_locked(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t
         batch.n = (uint32_t)(last - first);
         batch.first = b == 0 ? 1u : 0u;
         for (size_t i = first; i < last; ++i) ray_geom(tr, i, *order[i], sensor_frame[i], batch.g[i - first]);
-        ls::launch_trace_rays(s, tr->trace_blocks, d_rays, n, batch, q.wide_nodes.p, q.records.p, q.leaf, d_out, q.d_counters + b, q.spill.p);
+        kind.launch(s, tr->trace_blocks, d_rays, n, batch, q.wide_nodes.p, q.records.p, q.leaf, d_out, q.d_counters + b, q.spill.p);
     }
     LS_HIP(hipGetLastError());
     // what the handle issues next (mesh copies, commits, the next query) comes after this query; frames of the three-stream
@@ -211,6 +222,28 @@ int trace_rays_locked(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t
         LS_HIP(hipEventRecord(q.ev_done, s));
         LS_HIP(hipStreamWaitEvent(tr->stream, q.ev_done, 0));
     }
+    return LS_OK;
+}
+
+// the host-memory variant: rays and results staged in q.io, on the handle's stream; returns when out is filled
+int rays_host_locked(ls_tracer *tr, const void *rays, uint32_t n, void *out, const RayQueryKind &kind)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (n && (!rays || !out)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null rays or output");
+    if (n > 0xFFF00000u) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
+    tr->rq.last_built = 0;
+    if (!tr->committed || tr->n_tris == 0) return -1;   // (before n = 0: the same answer as the device entry point)
+    if (!n) return LS_OK;
+    ls_tracer::RayQuery &q = tr->rq;
+    hipStream_t s = tr->stream;
+    int rc;
+    if ((rc = flush_pipeline(tr))) return rc;
+    if ((rc = ensure(tr, q.io, (size_t)n * (32 + kind.out_bytes)))) return rc;   // (a growing buffer: the frame path's frames in flight never read it)
+    uint8_t *d_rays = q.io.p, *d_out = q.io.p + (size_t)n * 32;
+    LS_HIP(hipMemcpyAsync(d_rays, rays, (size_t)n * 32, hipMemcpyHostToDevice, s));
+    if ((rc = rays_locked(tr, s, d_rays, n, d_out, kind))) return rc;
+    LS_HIP(hipMemcpyAsync(out, d_out, (size_t)n * kind.out_bytes, hipMemcpyDeviceToHost, s));
+    LS_HIP(hipStreamSynchronize(s));
     return LS_OK;
 }
 
@@ -225,29 +258,25 @@ extern "C" {
 int ls_trace_rays(ls_tracer *tr, void *hip_stream, const void *d_rays, uint32_t n, void *d_out)
 {
     LS_ENTER(tr);
-    return trace_rays_locked(tr, hip_stream ? static_cast<hipStream_t>(hip_stream) : tr->stream, d_rays, n, d_out);
+    return rays_locked(tr, hip_stream ? static_cast<hipStream_t>(hip_stream) : tr->stream, d_rays, n, d_out, kClosest);
 }
 
 int ls_trace_rays_host(ls_tracer *tr, const void *rays, uint32_t n, void *out)
 {
     LS_ENTER(tr);
-    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
-    if (n && (!rays || !out)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null rays or output");
-    if (n > 0xFFF00000u) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
-    tr->rq.last_built = 0;
-    if (!tr->committed || tr->n_tris == 0) return -1;   // (before n = 0: the same answer as ls_trace_rays)
-    if (!n) return LS_OK;
-    ls_tracer::RayQuery &q = tr->rq;
-    hipStream_t s = tr->stream;
-    int rc;
-    if ((rc = flush_pipeline(tr))) return rc;
-    if ((rc = ensure(tr, q.io, (size_t)n * 48))) return rc;   // (a growing buffer: the frame path's frames in flight never read it)
-    uint8_t *d_rays = q.io.p, *d_out = q.io.p + (size_t)n * 32;
-    LS_HIP(hipMemcpyAsync(d_rays, rays, (size_t)n * 32, hipMemcpyHostToDevice, s));
-    if ((rc = trace_rays_locked(tr, s, d_rays, n, d_out))) return rc;
-    LS_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, s));
-    LS_HIP(hipStreamSynchronize(s));
-    return LS_OK;
+    return rays_host_locked(tr, rays, n, out, kClosest);
+}
+
+int ls_occluded_rays(ls_tracer *tr, void *hip_stream, const void *d_rays, uint32_t n, void *d_out)
+{
+    LS_ENTER(tr);
+    return rays_locked(tr, hip_stream ? static_cast<hipStream_t>(hip_stream) : tr->stream, d_rays, n, d_out, kOccluded);
+}
+
+int ls_occluded_rays_host(ls_tracer *tr, const void *rays, uint32_t n, void *out)
+{
+    LS_ENTER(tr);
+    return rays_host_locked(tr, rays, n, out, kOccluded);
 }
 
 }  // extern "C"

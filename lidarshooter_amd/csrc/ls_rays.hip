@@ -1,4 +1,5 @@
-// ls_rays.hip -- k_trace_rays: closest hits of caller-supplied rays (ls_trace_rays, include/lidarshooter_hip.h).
+// ls_rays.hip -- k_trace_rays: closest hits of caller-supplied rays (ls_trace_rays, include/lidarshooter_hip.h), and
+// k_occluded_rays: whether each ray hits anything at all (ls_occluded_rays; its own comment below).
 //
 // The walk of k_trace_inst<WIDE> (ls_kernels.hip) over the query set's four-wide nodes, with three differences:
 //   * the rays come from memory -- two 16-byte loads per ray, the 32-byte lidarshooter::Ray record (origin, tmin,
@@ -200,6 +201,174 @@ __global__ __launch_bounds__(kBlock) void k_trace_rays(const float4 *__restrict_
     }
 }
 
+// k_occluded_rays (ls_occluded_rays): k_trace_rays' walk for "is there any hit in [tmin, tmax]" -- no running best, so the
+// box test's far clamp stays tmax, and the first triangle that passes ends the ray (1 stored, the lane idle for the next
+// refill): no (t, id) state, no tie-break.  out = one byte per ray.  More than kGeomsPerLaunch geometries: the first launch
+// writes every byte, a later one skips the rays already occluded and writes only the ones it occludes.
+__global__ __launch_bounds__(kBlock) void k_occluded_rays(const float4 *__restrict__ rays, uint32_t n, RayBatch batch,
+                                                          const WideNode *__restrict__ wide, const TriRecord *__restrict__ records,
+                                                          uint32_t g, uint8_t *__restrict__ out, uint32_t *__restrict__ counter,
+                                                          uint32_t *__restrict__ spill)
+{
+    __shared__ uint32_t s_stack[kStackLds][kBlock];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    uint32_t *my_spill = spill + ((size_t)blockIdx.x * kBlock + tid) * kStackSpill;
+    bool drained = false;
+
+    bool has = false, hit = false;
+    V3 o = {0.f, 0.f, 0.f}, d = {0.f, 0.f, 1.f};
+    float tmin = 0.f, far = INFINITY;   // far = tmax: the box test's clamp
+    float ix = 1.f, iy = 1.f, iz = 1.f;
+    float cxl = 0.f, cxh = 0.f, cyl = 0.f, cyh = 0.f, czl = 0.f, czh = 0.f;   // -(o_m +- eps) * inv per axis
+    uint32_t q = 0, cur = kInvalid, sp = 0, gi = 0;
+    const float4 *rec4 = reinterpret_cast<const float4 *>(records);
+
+    // the ray of this lane in geometry k's mesh space; cur = its root (kInvalid: nothing there)
+    auto enter = [&](uint32_t k) {
+        const RayGeom &ig = batch.g[k];
+        cur = kInvalid;
+        if (!ig.n_leaves) return;
+        const float dx = (ig.minv[0] * d.x + ig.minv[1] * d.y) + ig.minv[2] * d.z;
+        const float dy = (ig.minv[3] * d.x + ig.minv[4] * d.y) + ig.minv[5] * d.z;
+        const float dz = (ig.minv[6] * d.x + ig.minv[7] * d.y) + ig.minv[8] * d.z;
+        const float ox = ((ig.minv[0] * o.x + ig.minv[1] * o.y) + ig.minv[2] * o.z) + ig.o[0];
+        const float oy = ((ig.minv[3] * o.x + ig.minv[4] * o.y) + ig.minv[5] * o.z) + ig.o[1];
+        const float oz = ((ig.minv[6] * o.x + ig.minv[7] * o.y) + ig.minv[8] * o.z) + ig.o[2];
+        const float eps = ig.eps + ig.eps_o * fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
+        ix = safe_inv(dx); iy = safe_inv(dy); iz = safe_inv(dz);
+        cxl = -(ox + eps) * ix; cxh = -(ox - eps) * ix;
+        cyl = -(oy + eps) * iy; cyh = -(oy - eps) * iy;
+        czl = -(oz + eps) * iz; czh = -(oz - eps) * iz;
+        cur = ig.n_leaves > 1u ? 0u : kLeafBit;
+    };
+    // next thing to do for a lane whose current subtree is finished: the stack, else the next geometry, else done
+    auto advance = [&]() {
+        cur = kInvalid;
+        if (sp) { --sp; cur = sp < (uint32_t)kStackLds ? s_stack[sp][tid] : my_spill[sp - kStackLds]; return; }
+        while (cur == kInvalid && ++gi < batch.n) enter(gi);
+    };
+
+    while (true) {
+        unsigned long long act = __ballot(has);
+        // refill trips repeat while kRaysRefillMin lanes stay idle: a later batch skips the rays an earlier one occluded
+        while (!drained && (uint32_t)__popcll(act) <= 64u - kRaysRefillMin) {
+            const unsigned long long idle = ~act;
+            const uint32_t nidle = (uint32_t)__popcll(idle);
+            const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(counter, nidle);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (base >= n) drained = true;
+            const uint32_t sidx = base + rank;
+            if (!drained && !has && sidx < n) {
+                const float4 r0 = rays[2 * (size_t)sidx], r1 = rays[2 * (size_t)sidx + 1];
+                o = {r0.x, r0.y, r0.z};
+                d = {r1.x, r1.y, r1.z};
+                tmin = r0.w;
+                far = r1.w;
+                q = sidx;
+                hit = false; sp = 0; gi = 0;
+                // a non-finite origin or direction, a zero direction, tmin > tmax or a NaN bound: not occluded, nothing walked
+                const bool ok = finite3(o.x, o.y, o.z) && finite3(d.x, d.y, d.z) && (d.x != 0.f || d.y != 0.f || d.z != 0.f) && tmin <= far;
+                cur = kInvalid;
+                if (ok && (batch.first || !out[q])) {   // (a later batch: a ray an earlier one occluded is done)
+                    enter(0);
+                    while (cur == kInvalid && ++gi < batch.n) enter(gi);
+                }
+                has = cur != kInvalid;
+                if (!has && batch.first) out[q] = 0u;
+            }
+            act = __ballot(has);
+        }
+        if (act == 0ull) break;
+        bool leaf_phase = true;
+        // one traversal step of this lane in geometry `ig`: a four-wide node, then the leaves it leads to
+        auto step = [&](const RayGeom &ig) {
+            const uint32_t at_entry = gi;   // advance() may move the lane on to another geometry: its leaves wait for the next trip
+            if (cur != kInvalid && !(cur & kLeafBit)) {
+                const float4 *nd = wide[ig.node_first + cur].q;
+                const float4 l0 = nd[0], l1 = nd[1], l2 = nd[2], l3 = nd[3], h0 = nd[4], h1 = nd[5], h2 = nd[6], h3 = nd[7];
+                auto slab = [&](const float4 &lo, const float4 &hi, float &tn) {
+                    const float x1 = fmaf(lo.x, ix, cxl), x2 = fmaf(hi.x, ix, cxh), y1 = fmaf(lo.y, iy, cyl), y2 = fmaf(hi.y, iy, cyh),
+                                z1 = fmaf(lo.z, iz, czl), z2 = fmaf(hi.z, iz, czh);
+                    tn = fmaxf(fmaxf(fminf(x1, x2), fminf(y1, y2)), fmaxf(fminf(z1, z2), 0.0f));
+                    const float tf = fminf(fminf(fmaxf(x1, x2), fmaxf(y1, y2)), fminf(fmaxf(z1, z2), far));
+                    // (the far bound gets two ulps: the products above round once each; an empty slot's reference is kInvalid)
+                    return tn <= tf * 1.0000003f && __float_as_uint(lo.w) != kInvalid;
+                };
+                float k0, k1, k2, k3;
+                const bool b0 = slab(l0, h0, k0), b1 = slab(l1, h1, k1), b2 = slab(l2, h2, k2), b3 = slab(l3, h3, k3);
+                uint32_t r0 = __float_as_uint(l0.w), r1 = __float_as_uint(l1.w), r2 = __float_as_uint(l2.w), r3 = __float_as_uint(l3.w);
+                k0 = b0 ? k0 : INFINITY; k1 = b1 ? k1 : INFINITY; k2 = b2 ? k2 : INFINITY; k3 = b3 ? k3 : INFINITY;
+                r0 = b0 ? r0 : kInvalid; r1 = b1 ? r1 : kInvalid; r2 = b2 ? r2 : kInvalid; r3 = b3 ? r3 : kInvalid;
+                // the nearest hit child comes to the front and is walked on; the other hits are pushed as they stand
+                auto cswap = [](float &ka, uint32_t &ra, float &kb, uint32_t &rb) {
+                    const bool sw = kb < ka || (ra == kInvalid && rb != kInvalid);
+                    const float kt = sw ? kb : ka; kb = sw ? ka : kb; ka = kt;
+                    const uint32_t rt = sw ? rb : ra; rb = sw ? ra : rb; ra = rt;
+                };
+                cswap(k0, r0, k1, r1); cswap(k0, r0, k2, r2); cswap(k0, r0, k3, r3);
+                if (r0 == kInvalid) {
+                    advance();
+                } else {
+                    const uint32_t v3 = r3 != kInvalid ? 1u : 0u, v2 = r2 != kInvalid ? 1u : 0u, v1 = r1 != kInvalid ? 1u : 0u;
+                    if (sp + 3u <= (uint32_t)kStackLds) {
+                        s_stack[sp][tid] = r3;
+                        s_stack[sp + v3][tid] = r2;
+                        s_stack[sp + v3 + v2][tid] = r1;
+                        sp += v3 + v2 + v1;
+                    } else {
+                        auto push = [&](uint32_t ref) {
+                            if (sp < (uint32_t)kStackLds) s_stack[sp][tid] = ref;
+                            else if (sp < (uint32_t)(kStackLds + kStackSpill)) my_spill[sp - kStackLds] = ref;
+                            ++sp;
+                        };
+                        if (v3) push(r3);
+                        if (v2) push(r2);
+                        if (v1) push(r1);
+                    }
+                    cur = r0;
+                }
+            }
+            while (leaf_phase && cur != kInvalid && (cur & kLeafBit) && gi == at_entry) {
+                const uint32_t first = (cur & ~kLeafBit) * g;
+                const uint32_t last = min(first + g, ig.n_tris);
+                for (uint32_t s = first; s < last; ++s) {
+                    const size_t at = 3 * ((size_t)ig.rec_first + s);
+                    const float4 r0 = rec4[at], r1 = rec4[at + 1], r2 = rec4[at + 2];
+                    V3 v0 = {r0.x, r0.y, r0.z}, v1 = {r1.x, r1.y, r1.z}, v2 = {r2.x, r2.y, r2.z};
+                    if (ig.xform == 2) {
+                        v0 = xform_vertex_sensor_only(ig.m, reinterpret_cast<const uint8_t *>(&r0));
+                        v1 = xform_vertex_sensor_only(ig.m, reinterpret_cast<const uint8_t *>(&r1));
+                        v2 = xform_vertex_sensor_only(ig.m, reinterpret_cast<const uint8_t *>(&r2));
+                    } else if (ig.xform == 1) {
+                        v0 = xform_vertex(ig.m, reinterpret_cast<const uint8_t *>(&r0));
+                        v1 = xform_vertex(ig.m, reinterpret_cast<const uint8_t *>(&r1));
+                        v2 = xform_vertex(ig.m, reinterpret_cast<const uint8_t *>(&r2));
+                    }
+                    float t;
+                    if (tri_test_org(o, d, v0, sub(v0, v1), sub(v2, v0), t) && tmin <= t && t <= far) { hit = true; break; }
+                }
+                if (hit) { cur = kInvalid; break; }   // the answer: nothing more to walk
+                advance();
+            }
+        };
+        // the leaf tests run when enough lanes stand at a leaf (or nobody has a node to go to): a lane at a leaf waits
+        {
+            const unsigned long long at_leaf = __ballot(has && cur != kInvalid && (cur & kLeafBit));
+            const unsigned long long at_node = __ballot(has && cur != kInvalid && !(cur & kLeafBit));
+            leaf_phase = (uint32_t)__popcll(at_leaf) >= kRaysLeafWait || at_node == 0ull;
+        }
+        if (has) {
+            if (cur != kInvalid) step(batch.g[gi]);
+            if (cur == kInvalid) {
+                if (hit || batch.first) out[q] = hit ? 1u : 0u;
+                has = false;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 void launch_trace_rays(hipStream_t s, uint32_t grid_blocks, const void *rays, uint32_t n, const RayBatch &batch, const WideNode *wide,
@@ -209,6 +378,15 @@ void launch_trace_rays(hipStream_t s, uint32_t grid_blocks, const void *rays, ui
     const uint32_t grid = min(grid_blocks, (n + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_trace_rays, dim3(grid), dim3(kBlock), 0, s, static_cast<const float4 *>(rays), n, batch, wide, records, leaf_size,
                        static_cast<uint4 *>(out), counter, spill);
+}
+
+void launch_occluded_rays(hipStream_t s, uint32_t grid_blocks, const void *rays, uint32_t n, const RayBatch &batch, const WideNode *wide,
+                          const TriRecord *records, uint32_t leaf_size, void *out, uint32_t *counter, uint32_t *spill)
+{
+    if (!n || !batch.n) return;
+    const uint32_t grid = min(grid_blocks, (n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_occluded_rays, dim3(grid), dim3(kBlock), 0, s, static_cast<const float4 *>(rays), n, batch, wide, records, leaf_size,
+                       static_cast<uint8_t *>(out), counter, spill);
 }
 
 }  // namespace ls

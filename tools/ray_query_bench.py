@@ -1,6 +1,8 @@
 """ls_trace_rays at SYN-1M: the sensor's own 524 288 rays (SYN-128 raster) against the BVH frame's k_trace_inst on the same
-scene in the same run, 1 M incoherent rays, and the first query's lazy build.  Prints host-side event timings; for kernel
-times run it under the profiler in a run of its own:
+scene in the same run, 1 M incoherent rays, and the first query's lazy build; then ls_occluded_rays against ls_trace_rays on
+three ray sets -- the sensor's own rays, the 1 M incoherent rays, 1 M segments (origins 0.2-5 m above the ground, targets at
+random scene points, tmax = 1 - 1e-4) -- whose occluded counts must equal the hit counts.  Prints host-side event timings;
+for kernel times (k_trace_rays, k_occluded_rays) run it under the profiler in a run of its own:
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/ray_query_bench.py
 usage: python tools/ray_query_bench.py [--reps N]
 """
@@ -45,14 +47,14 @@ def main():
     first_ms = (time.perf_counter() - t0) * 1e3
     built = tr.info(capi.LS_INFO_RAY_QUERY_BUILT)
 
-    def timed(rays, m, reps):
-        o = torch.zeros(m * 16, dtype=torch.uint8, device="cuda:0")
+    def timed(rays, m, reps, query=tr.traceRaysDevice, out_bytes=16):
+        o = torch.zeros(m * out_bytes, dtype=torch.uint8, device="cuda:0")
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s = torch.cuda.Stream()   # (a stream of its own: 0 would mean the handle's stream)
-        tr.traceRaysDevice(rays.data_ptr(), m, o.data_ptr(), s.cuda_stream)
+        query(rays.data_ptr(), m, o.data_ptr(), s.cuda_stream)
         e0.record(s)
         for _ in range(reps):
-            tr.traceRaysDevice(rays.data_ptr(), m, o.data_ptr(), s.cuda_stream)
+            query(rays.data_ptr(), m, o.data_ptr(), s.cuda_stream)
         e1.record(s)
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / reps, o
@@ -75,6 +77,23 @@ def main():
     print(f"first query (lazy build of {built} hierarchy + trace): {first_ms:.2f} ms host")
     print(f"sensor's own rays: {n} rays, {hits} hits, {own_ms * 1e3:.1f} us per query")
     print(f"incoherent rays: {m} rays, {inc_hits} hits, {inc_ms * 1e3:.1f} us per query = {m / inc_ms / 1e3:.0f} Mrays/s")
+    # segments: from 0.2-5 m above the ground to random scene points (world frame, then the sensor frame as above)
+    sr = np.zeros((m, 8), np.float32)
+    ow = np.c_[rng.uniform(-50, 50, (m, 2)), rng.uniform(0.2, 5.0, m)]
+    tw = verts[rng.integers(0, verts.shape[0], m)].astype(np.float64)
+    sr[:, 0:3] = (R @ (ow - np.asarray(base.t, np.float64)).T).T
+    sr[:, 4:7] = (R @ (tw - ow).T).T
+    sr[:, 7] = 1.0 - 1e-4
+    d_seg = torch.from_numpy(sr.view(np.uint8).reshape(-1)).to("cuda:0")
+    # ls_occluded_rays against ls_trace_rays on the three sets, the same rays, the same run
+    for name, rays, k in (("sensor's own rays", d_rays, n), ("incoherent rays", d_inc, m), ("segments", d_seg, m)):
+        t_ms, o = timed(rays, k, a.reps)
+        hit = int(np.count_nonzero(o.cpu().numpy().view(np.uint32).reshape(k, 4)[:, 1] != 0xFFFFFFFF))
+        a_ms, o = timed(rays, k, a.reps, tr.occludedRaysDevice, 1)
+        occ = int(np.count_nonzero(o.cpu().numpy()))
+        assert occ == hit, (name, occ, hit)
+        print(f"occlusion, {name}: {k} rays, {occ} occluded = {hit} hits; ls_trace_rays {t_ms * 1e3:.1f} us, "
+              f"ls_occluded_rays {a_ms * 1e3:.1f} us per query ({a_ms / t_ms:.2f}x)")
     tr.close()
 
 
