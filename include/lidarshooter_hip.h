@@ -429,7 +429,7 @@ int ls_parallel_copy(void *dst, const void *src, uint64_t bytes);
 #define LS_INFO_EMIT_POINTS 14       /* the current LS_OPT_EMIT_POINTS                                            */
 #define LS_INFO_BVH_WIDE 16                /* 1: the last trace walked the four-wide nodes (LS_OPT_BVH_WIDE, instanced mode, every geometry's made) */
 #define LS_INFO_FRAME_GRAPH_PATCH_WAITS 15 /* patches that first had to wait for the previous launch of their graph (the host ran more than three frames ahead) */
-#define LS_INFO_RAY_QUERY_BUILT 17         /* geometries whose query hierarchy the last ls_trace_rays* / ls_occluded_rays* built or refitted (see there) */
+#define LS_INFO_RAY_QUERY_BUILT 17         /* geometries whose query hierarchy the last ls_trace_rays* / ls_occluded_rays* / ls_closest_points* built or refitted (see there) */
 long ls_get_info(ls_tracer *tr, int what);
 
 /* Mean stage durations (milliseconds, hipEvents on the handle's stream) over every frame recorded
@@ -508,6 +508,26 @@ int ls_trace_rays_host(ls_tracer *tr, const void *rays, uint32_t n, void *out);
 int ls_occluded_rays(ls_tracer *tr, void *hip_stream, const void *d_rays, uint32_t n, void *d_out);
 /* The same with host memory (pageable) in and out, on the handle's stream; returns when out is filled. */
 int ls_occluded_rays_host(ls_tracer *tr, const void *rays, uint32_t n, void *out);
+
+/* ---- nearest-point queries: the closest point of the scene's surface to each of n CALLER points (Embree's rtcPointQuery):
+ * cloud-to-mesh residuals of a recorded scan, labelling scan points with the (geomID, primID) they lie on, clearance of a pose.
+ *   d_points: n records of 16 bytes, 16-byte aligned: x, y, z f32@0/4/8 in the handle's SENSOR frame (as the ray queries),
+ *             radius f32@12 = the largest distance of interest (+inf: no bound).
+ *   d_out:    n records of 32 bytes, 16-byte aligned, in input order: the closest surface point qx, qy, qz f32@0/4/8 (sensor
+ *             frame), dist f32@12, geom u32@16 and prim u32@20 as in ls_hit (a quad geometry: the quad index), index u32@24 =
+ *             the position in the input, u32@28 = 0.  A miss: geom = prim = 0xFFFFFFFF, dist = -1, q = 0.
+ * Every triangle of the scene as of the last successful ls_commit_scene, corners through the frame's own transform, gives
+ * (q, d2) by ONE float32 operation sequence (Ericson's seven regions; ls_debug_closest_on_triangle in
+ * lidarshooter_hip_debug.h runs the same sequence on the host); it counts when d2 is finite and d2 <= radius * radius (the
+ * float32 product).  The answer is the triangle with the smallest d2 -- equal d2: the lowest (geomID, primID) --, dist =
+ * sqrtf(d2): bit for bit what a loop over all triangles gives.  A point with a non-finite coordinate, a NaN or negative
+ * radius: a miss.  Triangles with a non-finite corner or no area never count.
+ * Return codes, stream order, the frame graph and n limits, and the query hierarchies are those of ls_trace_rays: the three
+ * queries share the hierarchies, and LS_INFO_RAY_QUERY_BUILT reports for whichever ran last.  While a query of more than 16
+ * geometries is in flight the last word of a record holds an intermediate value. */
+int ls_closest_points(ls_tracer *tr, void *hip_stream, const void *d_points, uint32_t n, void *d_out);
+/* The same with host memory (pageable) in and out, on the handle's stream; returns when out is filled. */
+int ls_closest_points_host(ls_tracer *tr, const void *points, uint32_t n, void *out);
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,10 @@ int ls_debug_sort_pairs(ls_tracer *tr, uint32_t *keys, uint32_t *vals, uint32_t 
 int ls_debug_expand_hits(void *dst_points32, const void *hits8, uint32_t n, const float *sin_theta, const float *cos_theta,
                          const float *cs_phi, uint32_t V, uint32_t H);
 
+/* the library's point-triangle arithmetic on the host (no device, no handle): q[3], *d2 -- the float32 operation sequence
+ * k_closest_points runs per triangle (csrc/ls_closest.h); d2 = +inf, q = 0 for a triangle that never counts */
+int ls_debug_closest_on_triangle(const float p[3], const float v0[3], const float v1[3], const float v2[3], float q[3], float *d2);
+
 #ifdef __cplusplus
 }
 #endif

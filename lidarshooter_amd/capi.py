@@ -51,10 +51,11 @@ SYMBOLS = (
     "ls_frame_graph_begin", "ls_frame_graph_stream", "ls_frame_graph_end", "ls_frame_graph_reset",
     "ls_tracer_set_sensor", "ls_tracer_set_sensor_tables", "ls_expand_gathered_hits_sized",
     "ls_trace_rays", "ls_trace_rays_host", "ls_occluded_rays", "ls_occluded_rays_host",
+    "ls_closest_points", "ls_closest_points_host",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
 DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_scene_size", "ls_debug_download_scene",
-                 "ls_debug_download_bvh", "ls_debug_sort_pairs", "ls_debug_expand_hits")
+                 "ls_debug_download_bvh", "ls_debug_sort_pairs", "ls_debug_expand_hits", "ls_debug_closest_on_triangle")
 
 
 class SensorDesc(C.Structure):
@@ -76,6 +77,9 @@ class Frame(C.Structure):
 
 
 HIT_DTYPE = np.dtype([("ray", "<u4"), ("geom", "<u4"), ("prim", "<u4"), ("t", "<f4")])
+# ls_closest_points: a query point (sensor frame) with the largest distance of interest, and its answer
+POINT_QUERY_DTYPE = np.dtype([("point", "<f4", 3), ("radius", "<f4")])
+CLOSEST_DTYPE = np.dtype([("q", "<f4", 3), ("dist", "<f4"), ("geom", "<u4"), ("prim", "<u4"), ("index", "<u4"), ("pad", "<u4")])
 NODE_DTYPE = np.dtype([("llo", "<f4", 3), ("left", "<u4"), ("lhi", "<f4", 3), ("right", "<u4"),
                        ("rlo", "<f4", 3), ("pad0", "<u4"), ("rhi", "<f4", 3), ("pad1", "<u4")])
 LEAF_BIT = 0x80000000
@@ -176,6 +180,9 @@ def load() -> C.CDLL:
     L.ls_trace_rays_host.argtypes = [vp, vp, u32, vp]
     L.ls_occluded_rays.argtypes = [vp, vp, vp, u32, vp]
     L.ls_occluded_rays_host.argtypes = [vp, vp, u32, vp]
+    L.ls_closest_points.argtypes = [vp, vp, vp, u32, vp]
+    L.ls_closest_points_host.argtypes = [vp, vp, u32, vp]
+    L.ls_debug_closest_on_triangle.argtypes = [f32p, f32p, f32p, f32p, f32p, f32p]
     L.ls_geometry_type.argtypes = [vp, C.c_char_p]
     L.ls_debug_dense_hits.argtypes = [vp, f32p, u32p]
     L.ls_debug_trace_bruteforce.argtypes = [vp, f32p, u32p]
@@ -515,6 +522,33 @@ class Tracer:
         rc = self.L.ls_occluded_rays(self.h, stream, d_rays, n, d_out)
         return -1 if rc == -1 else int(self._check(rc, "ls_occluded_rays"))
 
+    def closestPoints(self, points):
+        """Nearest surface points (ls_closest_points_host): `points` float32 (n, 4) -- x, y, z in the sensor frame and the
+        largest distance of interest (inf: no bound) per row -- or a POINT_QUERY_DTYPE array.  -> (rc, CLOSEST_DTYPE[n]);
+        rc = -1 (no commit, empty scene): every record a miss."""
+        p = np.ascontiguousarray(points)
+        if p.dtype != POINT_QUERY_DTYPE:
+            p = np.ascontiguousarray(p, np.float32)
+            if p.ndim != 2 or p.shape[1] != 4:
+                raise ValueError("points: float32 (n, 4) or POINT_QUERY_DTYPE")
+        n = p.shape[0]
+        out = np.zeros(n, CLOSEST_DTYPE)
+        rc = self.L.ls_closest_points_host(self.h, p.ctypes.data if n else None, n, out.ctypes.data if n else None)
+        if rc == -1:
+            out["index"] = np.arange(n, dtype=np.uint32)
+            out["geom"] = INVALID
+            out["prim"] = INVALID
+            out["dist"] = -1.0
+            return -1, out
+        self._check(rc, "ls_closest_points_host")
+        return int(rc), out
+
+    def closestPointsDevice(self, d_points: int, n: int, d_out: int, stream=None) -> int:
+        """ls_closest_points on device pointers (n 16-byte points in, n 32-byte records out); enqueued on `stream` (a hipStream_t
+        as an int, None: the handle's), no wait.  -> 0, or -1 on an empty / uncommitted scene (d_out not written)."""
+        rc = self.L.ls_closest_points(self.h, stream, d_points, n, d_out)
+        return -1 if rc == -1 else int(self._check(rc, "ls_closest_points"))
+
     # ---- test hooks
     def generateRaysAos(self, d_rays: int | None, d_hits: int | None):
         """LidarDevice::allRaysGPU's two buffers (Ray 32 B, Hit 24 B per ray) in device memory of the caller."""
@@ -560,3 +594,15 @@ class Tracer:
         tri = np.zeros(s["n_tris"], TRI_DTYPE)
         self._check(self.L.ls_debug_download_bvh(self.h, nodes.ctypes.data, tri.ctypes.data), "ls_debug_download_bvh")
         return nodes, tri, s["leaf_size"]
+
+
+def closest_on_triangle(p, v0, v1, v2):
+    """ls_debug_closest_on_triangle: the library's float32 point-triangle arithmetic on the host -> (q float32[3], d2 float32)"""
+    L = load()
+    a = [np.ascontiguousarray(x, np.float32).reshape(3) for x in (p, v0, v1, v2)]
+    q = np.zeros(3, np.float32)
+    d2 = C.c_float()
+    rc = L.ls_debug_closest_on_triangle(_f32p(a[0]), _f32p(a[1]), _f32p(a[2]), _f32p(a[3]), _f32p(q), C.byref(d2))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_debug_closest_on_triangle: status {rc}")
+    return q, np.float32(d2.value)

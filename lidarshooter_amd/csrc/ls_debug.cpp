@@ -2,6 +2,7 @@
 // the exhaustive device checker, the committed scene and BVH arrays).  Not part of the drop-in surface.
 #include "../../include/lidarshooter_hip_debug.h"
 #include "ls_internal.h"
+#include "ls_closest.h"
 
 using namespace lsi;
 
@@ -106,6 +107,13 @@ int ls_debug_sort_pairs(ls_tracer *tr, uint32_t *keys, uint32_t *vals, uint32_t 
     (void)hipFree(d);
     (void)hipFree(temp);
     if (e != hipSuccess) return fail(tr, LS_ERR_HIP, hipGetErrorString(e));
+    return LS_OK;
+}
+
+int ls_debug_closest_on_triangle(const float p[3], const float v0[3], const float v1[3], const float v2[3], float q[3], float *d2)
+{
+    if (!p || !v0 || !v1 || !v2 || !q || !d2) return LS_ERR_INVALID_ARGUMENT;
+    ls::closest_on_triangle(p, v0, v1, v2, q, d2);
     return LS_OK;
 }
 

@@ -262,6 +262,18 @@ void launch_trace_rays(hipStream_t s, uint32_t grid_blocks, const void *rays, ui
 // a later one only the rays it finds occluded)
 void launch_occluded_rays(hipStream_t s, uint32_t grid_blocks, const void *rays, uint32_t n, const RayBatch &batch, const WideNode *wide,
                           const TriRecord *records, uint32_t leaf_size, void *out, uint32_t *counter, uint32_t *spill);
+// ls_closest_points (ls_points.hip): the nearest surface point to each of n caller points (16-byte records: x, y, z in the
+// sensor frame, radius) over the same hierarchies, described by the same RayBatch; out = n 32-byte records (qx, qy, qz, dist |
+// geom, prim, index, 0).  PointMargins is what makes a box's distance a lower bound of the exact test's float32 d2
+// (ls_rays.cpp: point_margins), per geometry of the batch.
+struct PointMargins {
+    uint32_t last;                    // 1: the last launch of a query (the running d2 kept in a record's last word is cleared)
+    float e0[kGeomsPerLaunch];        // every box is widened by e0 + e1 * |p|inf (the hierarchy's own units) ...
+    float e1[kGeomsPerLaunch];
+    float s2[kGeomsPerLaunch];        // ... and its squared distance times s2 (<= sigma_min^2 of hierarchy space -> sensor frame) is the bound
+};
+void launch_closest_points(hipStream_t s, uint32_t grid_blocks, const void *points, uint32_t n, const RayBatch &batch, const PointMargins &pm,
+                           const WideNode *wide, const TriRecord *records, uint32_t leaf_size, void *out, uint32_t *counter, uint32_t *spill);
 void launch_rowcount(hipStream_t s, const uint32_t *gid, uint32_t nrays, uint32_t *row_counts, uint32_t *queue_heads = nullptr);   // queue_heads: zeroed for the next k_trace
 // Progress of a synchronous frame whose compact points go straight to pinned host memory (ls_trace_scene_begin /
 // ls_trace_scene_expand): the device publishes, with system-scope release, (1) the frame's hit count as the pack pass

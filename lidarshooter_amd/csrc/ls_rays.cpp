@@ -1,5 +1,7 @@
 // ls_rays.cpp -- ls_trace_rays / ls_trace_rays_host: closest hits of caller-supplied rays against the committed scene;
-// ls_occluded_rays / ls_occluded_rays_host: whether each ray hits anything (the same query set and walk, stopping at a hit).
+// ls_occluded_rays / ls_occluded_rays_host: whether each ray hits anything (the same query set and walk, stopping at a hit);
+// ls_closest_points / ls_closest_points_host: the nearest surface point to each caller point (the same query set, a
+// distance-ordered walk: ls_points.hip).
 //
 // The query set (ls_tracer::RayQuery) is a hierarchy set of its own -- one hierarchy per geometry, built by the kernels of
 // the instanced commit (hier_layout / hier_build, ls_commit.cpp) into buffers nothing in the frame path reads or writes,
@@ -151,6 +153,55 @@ void ray_geom(const ls_tracer *tr, size_t i, const Geometry &ge, bool sensor_fra
     rg.eps_o = 2.0f * c * row;
 }
 
+
+// The largest eigenvalue of the symmetric 3 x 3 matrix S (row-major), closed form.
+double sym3_lambda_max(const double *S)
+{
+    const double p1 = S[1] * S[1] + S[2] * S[2] + S[5] * S[5];
+    const double qm = (S[0] + S[4] + S[8]) / 3.0;
+    if (p1 == 0.0) return std::max(S[0], std::max(S[4], S[8]));
+    const double a = S[0] - qm, b = S[4] - qm, c = S[8] - qm;
+    const double p = std::sqrt((a * a + b * b + c * c + 2.0 * p1) / 6.0);
+    const double B[9] = {a / p, S[1] / p, S[2] / p, S[1] / p, b / p, S[5] / p, S[2] / p, S[5] / p, c / p};
+    const double det = B[0] * (B[4] * B[8] - B[5] * B[7]) - B[1] * (B[3] * B[8] - B[5] * B[6]) + B[2] * (B[3] * B[7] - B[4] * B[6]);
+    const double r = std::min(1.0, std::max(-1.0, det / 2.0));
+    return qm + 2.0 * p * std::cos(std::acos(r) / 3.0);
+}
+
+// ls_closest_points: the margins that make "s2 * (squared distance of p_m to a box widened by e0 + e1 |p|inf)" a lower bound of
+// the float32 d2 closest_on_triangle gives for every triangle below the box:
+//   * the ray query's own widening (rg.eps, rg.eps_o: the rounding of p_m = minv p + o and of the corners' way through the
+//     frame's transform, in the hierarchy's units);
+//   * delta = 8e-6 (|p|inf + W) in the sensor frame, W >= every intermediate of the corners' transform: the exact test's own
+//     rounding (its q is a point of the triangle up to a few ulps of the coordinates, d2 = |p - q|^2 from that q) and the
+//     corners' rounding where translations cancel -- carried into the hierarchy's units by 1 / s;
+//   * s <= sigma_min of the linear part of hierarchy space -> sensor frame: 1 / ||minv||_2 in double, six digits kept in hand.
+void point_margins(const ls_tracer *tr, size_t i, const Geometry &ge, bool sensor_frame, const ls::RayGeom &rg, ls::PointMargins &pm, size_t k)
+{
+    const double maxabs = tr->rq.built[i].maxabs;
+    double s = 1.0, W = maxabs;
+    if (!sensor_frame) {
+        double minv[9], o[3], cond, S[9];
+        inst_inverse(tr, ge, minv, o, &cond);
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) S[3 * r + c] = minv[r] * minv[c] + minv[3 + r] * minv[3 + c] + minv[6 + r] * minv[6 + c];
+        s = (1.0 - 1e-6) / std::sqrt(sym3_lambda_max(S));
+        double arow = 0.0, rrow = 0.0, amax = 0.0, tmax = 0.0;
+        for (int r = 0; r < 3; ++r) {
+            arow = std::max(arow, std::fabs((double)ge.affine[4 * r]) + std::fabs((double)ge.affine[4 * r + 1]) + std::fabs((double)ge.affine[4 * r + 2]));
+            rrow = std::max(rrow, std::fabs((double)tr->rinv[3 * r]) + std::fabs((double)tr->rinv[3 * r + 1]) + std::fabs((double)tr->rinv[3 * r + 2]));
+            amax = std::max(amax, std::fabs((double)ge.affine[4 * r + 3]));
+            tmax = std::max(tmax, std::fabs((double)tr->t[r]));
+        }
+        W = std::max(1.0, rrow) * (arow * maxabs + amax + tmax);
+    }
+    const double kd = 8e-6;
+    // rounded up (e0, e1) and down (s2): a float conversion moves a value by less than 6e-8 of itself
+    pm.e0[k] = (float)(((double)rg.eps + kd * W / s) * (1.0 + 1e-6));
+    pm.e1[k] = (float)(((double)rg.eps_o + kd / s) * (1.0 + 1e-6));
+    pm.s2[k] = (float)(s * s * (1.0 - 1e-6));
+}
+
 }  // namespace
 
 void ray_query_release(ls_tracer *tr)
@@ -169,21 +220,35 @@ void ray_query_release(ls_tracer *tr)
 
 namespace {
 
-// the two queries: what one launch over a geometry batch runs, and what it writes per ray
+// the queries: what one launch over a geometry batch runs, what it reads per query and what it writes per result
 struct RayQueryKind {
-    void (*launch)(hipStream_t, uint32_t, const void *, uint32_t, const ls::RayBatch &, const ls::WideNode *, const ls::TriRecord *,
-                   uint32_t, void *, uint32_t *, uint32_t *);
-    size_t out_bytes;   // per ray: an ls_hit (16-byte aligned), or one byte (any address)
+    void (*launch)(hipStream_t, uint32_t, const void *, uint32_t, const ls::RayBatch &, const ls::PointMargins &, const ls::WideNode *,
+                   const ls::TriRecord *, uint32_t, void *, uint32_t *, uint32_t *);
+    size_t in_bytes;    // per query: a 32-byte ray or a 16-byte point (16-byte aligned)
+    size_t out_bytes;   // per result: an ls_hit, one byte, or an ls_closest record
+    size_t out_align;   // 16, or 1 (any address)
+    bool points;        // the launch takes PointMargins (ls_closest_points)
+    const char *misaligned;
 };
-const RayQueryKind kClosest = {ls::launch_trace_rays, 16};
-const RayQueryKind kOccluded = {ls::launch_occluded_rays, 1};
+void launch_closest_hits(hipStream_t s, uint32_t blocks, const void *in, uint32_t n, const ls::RayBatch &batch, const ls::PointMargins &,
+                         const ls::WideNode *wide, const ls::TriRecord *records, uint32_t leaf, void *out, uint32_t *counter, uint32_t *spill)
+{
+    ls::launch_trace_rays(s, blocks, in, n, batch, wide, records, leaf, out, counter, spill);
+}
+void launch_any_hits(hipStream_t s, uint32_t blocks, const void *in, uint32_t n, const ls::RayBatch &batch, const ls::PointMargins &,
+                     const ls::WideNode *wide, const ls::TriRecord *records, uint32_t leaf, void *out, uint32_t *counter, uint32_t *spill)
+{
+    ls::launch_occluded_rays(s, blocks, in, n, batch, wide, records, leaf, out, counter, spill);
+}
+const RayQueryKind kClosest = {launch_closest_hits, 32, 16, 16, false, "rays and hit records must be 16-byte aligned"};
+const RayQueryKind kOccluded = {launch_any_hits, 32, 1, 1, false, "rays must be 16-byte aligned"};
+const RayQueryKind kNearest = {ls::launch_closest_points, 16, 32, 16, true, "points and result records must be 16-byte aligned"};
 
 int rays_locked(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out, const RayQueryKind &kind)
 {
     if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
     if (n && (!d_rays || !d_out)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null rays or output");
-    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & (kind.out_bytes - 1u)))
-        return fail(tr, LS_ERR_INVALID_ARGUMENT, kind.out_bytes == 16 ? "rays and hit records must be 16-byte aligned" : "rays must be 16-byte aligned");
+    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & (kind.out_align - 1u))) return fail(tr, LS_ERR_INVALID_ARGUMENT, kind.misaligned);
     if (n > 0xFFF00000u) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
     ls_tracer::RayQuery &q = tr->rq;
     q.last_built = 0;
@@ -212,8 +277,14 @@ int rays_locked(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, vo
         const size_t first = (size_t)b * ls::kGeomsPerLaunch, last = std::min(order.size(), first + ls::kGeomsPerLaunch);
         batch.n = (uint32_t)(last - first);
         batch.first = b == 0 ? 1u : 0u;
-        for (size_t i = first; i < last; ++i) ray_geom(tr, i, *order[i], sensor_frame[i], batch.g[i - first]);
-        kind.launch(s, tr->trace_blocks, d_rays, n, batch, q.wide_nodes.p, q.records.p, q.leaf, d_out, q.d_counters + b, q.spill.p);
+        ls::PointMargins pm;
+        std::memset(static_cast<void *>(&pm), 0, sizeof(pm));
+        pm.last = b + 1 == launches ? 1u : 0u;
+        for (size_t i = first; i < last; ++i) {
+            ray_geom(tr, i, *order[i], sensor_frame[i], batch.g[i - first]);
+            if (kind.points) point_margins(tr, i, *order[i], sensor_frame[i], batch.g[i - first], pm, i - first);
+        }
+        kind.launch(s, tr->trace_blocks, d_rays, n, batch, pm, q.wide_nodes.p, q.records.p, q.leaf, d_out, q.d_counters + b, q.spill.p);
     }
     LS_HIP(hipGetLastError());
     // what the handle issues next (mesh copies, commits, the next query) comes after this query; frames of the three-stream
@@ -238,9 +309,9 @@ int rays_host_locked(ls_tracer *tr, const void *rays, uint32_t n, void *out, con
     hipStream_t s = tr->stream;
     int rc;
     if ((rc = flush_pipeline(tr))) return rc;
-    if ((rc = ensure(tr, q.io, (size_t)n * (32 + kind.out_bytes)))) return rc;   // (a growing buffer: the frame path's frames in flight never read it)
-    uint8_t *d_rays = q.io.p, *d_out = q.io.p + (size_t)n * 32;
-    LS_HIP(hipMemcpyAsync(d_rays, rays, (size_t)n * 32, hipMemcpyHostToDevice, s));
+    if ((rc = ensure(tr, q.io, (size_t)n * (kind.in_bytes + kind.out_bytes)))) return rc;   // (a growing buffer: the frame path's frames in flight never read it)
+    uint8_t *d_rays = q.io.p, *d_out = q.io.p + (size_t)n * kind.in_bytes;
+    LS_HIP(hipMemcpyAsync(d_rays, rays, (size_t)n * kind.in_bytes, hipMemcpyHostToDevice, s));
     if ((rc = rays_locked(tr, s, d_rays, n, d_out, kind))) return rc;
     LS_HIP(hipMemcpyAsync(out, d_out, (size_t)n * kind.out_bytes, hipMemcpyDeviceToHost, s));
     LS_HIP(hipStreamSynchronize(s));
@@ -277,6 +348,18 @@ int ls_occluded_rays_host(ls_tracer *tr, const void *rays, uint32_t n, void *out
 {
     LS_ENTER(tr);
     return rays_host_locked(tr, rays, n, out, kOccluded);
+}
+
+int ls_closest_points(ls_tracer *tr, void *hip_stream, const void *d_points, uint32_t n, void *d_out)
+{
+    LS_ENTER(tr);
+    return rays_locked(tr, hip_stream ? static_cast<hipStream_t>(hip_stream) : tr->stream, d_points, n, d_out, kNearest);
+}
+
+int ls_closest_points_host(ls_tracer *tr, const void *points, uint32_t n, void *out)
+{
+    LS_ENTER(tr);
+    return rays_host_locked(tr, points, n, out, kNearest);
 }
 
 }  // extern "C"

@@ -1,8 +1,11 @@
 """ls_trace_rays at SYN-1M: the sensor's own 524 288 rays (SYN-128 raster) against the BVH frame's k_trace_inst on the same
 scene in the same run, 1 M incoherent rays, and the first query's lazy build; then ls_occluded_rays against ls_trace_rays on
 three ray sets -- the sensor's own rays, the 1 M incoherent rays, 1 M segments (origins 0.2-5 m above the ground, targets at
-random scene points, tmax = 1 - 1e-4) -- whose occluded counts must equal the hit counts.  Prints host-side event timings;
-for kernel times (k_trace_rays, k_occluded_rays) run it under the profiler in a run of its own:
+random scene points, tmax = 1 - 1e-4) -- whose occluded counts must equal the hit counts; then ls_closest_points on three point sets -- the frame's own cloud with
+every point jittered by a few centimetres (cloud to mesh), 1 M points uniform in the scene's box, the same with a 0.5 m
+radius -- next to ls_trace_rays on the incoherent rays.  Prints host-side event timings;
+for kernel times (k_trace_rays, k_occluded_rays, k_closest_points: its launches come in the order of the sets, 1 + reps
+each) run it under the profiler in a run of its own:
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/ray_query_bench.py
 usage: python tools/ray_query_bench.py [--reps N]
 """
@@ -94,6 +97,30 @@ def main():
         assert occ == hit, (name, occ, hit)
         print(f"occlusion, {name}: {k} rays, {occ} occluded = {hit} hits; ls_trace_rays {t_ms * 1e3:.1f} us, "
               f"ls_occluded_rays {a_ms * 1e3:.1f} us per query ({a_ms / t_ms:.2f}x)")
+    # ls_closest_points: the frame's own cloud jittered, points uniform in the scene's box, the same within 0.5 m
+    rc, pts32, _ = tr.traceScene(0)
+    assert rc == 0
+    cloud = np.ascontiguousarray(pts32[:, :12]).view(np.float32).reshape(-1, 3)
+    jit = np.zeros((cloud.shape[0], 4), np.float32)
+    jit[:, :3] = cloud + rng.normal(scale=0.03, size=cloud.shape).astype(np.float32)
+    jit[:, 3] = np.inf
+    uni = np.zeros((m, 4), np.float32)
+    pw = np.c_[rng.uniform(-50, 50, (m, 2)), rng.uniform(-0.5, 5.0, m)]
+    uni[:, :3] = (R @ (pw - np.asarray(base.t, np.float64)).T).T
+    uni[:, 3] = np.inf
+    ball = uni.copy()
+    ball[:, 3] = 0.5
+    inc_ms, _ = timed(d_inc, m, a.reps)
+    print(f"incoherent rays again: {inc_ms * 1e3:.1f} us per query")
+    for name, pts in (("jittered cloud", jit), ("uniform in the box", uni), ("uniform, radius 0.5 m", ball)):
+        k = pts.shape[0]
+        d_pts = torch.from_numpy(pts.view(np.uint8).reshape(-1)).to("cuda:0")
+        p_ms, o = timed(d_pts, k, a.reps, tr.closestPointsDevice, 32)
+        rec = o.cpu().numpy().view(np.uint32).reshape(k, 8)
+        found = rec[:, 4] != 0xFFFFFFFF
+        dist = rec[found, 3].view(np.float32)
+        print(f"closest points, {name}: {k} points, {int(np.count_nonzero(found))} found, mean dist {float(dist.mean()) if dist.size else 0:.4f} m; "
+              f"ls_closest_points {p_ms * 1e3:.1f} us per query ({p_ms / inc_ms:.2f}x ls_trace_rays on {m} incoherent rays)")
     tr.close()
 
 
