@@ -529,6 +529,41 @@ int ls_closest_points(ls_tracer *tr, void *hip_stream, const void *d_points, uin
 /* The same with host memory (pageable) in and out, on the handle's stream; returns when out is filled. */
 int ls_closest_points_host(ls_tracer *tr, const void *points, uint32_t n, void *out);
 
+/* ---- hit attributes: what RTCHit carries beyond (geomID, primID, t) -- the geometric normal Ng and the barycentrics u, v --
+ * plus the incidence cosine and which half of a quad was hit, for hit records of the frame (ls_frame.d_hits / hits) or of
+ * ls_trace_rays: incidence for intensity / drop-out models, labelled normals, point-to-plane residuals, interpolation of
+ * per-vertex data.  No hierarchy is built or walked: a gather over the records.
+ *   d_hits:  n ls_hit records, 16-byte aligned, in any order, a subset is fine; hit.ray indexes the rays.
+ *   d_rays:  non-NULL: the n_rays 32-byte lidarshooter::Ray records (sensor frame, 16-byte aligned) that were given to
+ *            ls_trace_rays; a hit with ray >= n_rays is invalid.  NULL: the handle's own sensor rays -- hit.ray is the global
+ *            ray index v * H + h of the full raster whatever the shard, origin 0, direction the factor-table products the
+ *            trace kernels form; n_rays is ignored, the bound is V * H.
+ *   d_count: NULL, or a device word: min(n, *d_count) records are handled and nothing is written beyond them (the records
+ *            of ls_trace_scene_async: d_hits, d_n_points, n = the capacity -- no host read-back).
+ *   d_out:   one 48-byte record per handled hit, 16-byte aligned, in input order:
+ *              nx, ny, nz f32@0   unit geometric normal in the sensor frame, along (v1 - v0) x (v2 - v0): Embree's Ng direction
+ *              cos_inc f32@12     -(n . d) / |d| clamped to [-1, 1]; positive: the ray meets the front face
+ *              u, v f32@16        Embree's barycentrics: hit point = (1 - u - v) v0 + u v1 + v v2
+ *              tri u32@24         triangle inside the geometry: prim, or 2 prim / 2 prim + 1 of a quad (Embree's split
+ *                                 (v0,v1,v3), (v2,v3,v1))
+ *              flags u32@28       bit 0 = valid, the other bits 0
+ *              px, py, pz f32@32  o + t d per axis (one product, one sum); a sensor ray: t d, the bits of the frame's points32 xyz
+ *              ray u32@44         hit.ray
+ * A record is valid when geom names a geometry of the committed scene, prim < its element count, the ray index is in range
+ * and the library's exact test from the ray's origin against the named triangle -- corners through the frame's own transform
+ * as of the geometries' current poses, like the other queries -- passes with t bit-equal to hit.t; a quad: the first of its
+ * two triangles for which that holds.  Anything else -- a miss record, a stale hit of a geometry moved since, a wrong or
+ * removed id, a t that is one ulp off or NaN -- gets flags = 0 and zeros everywhere but `ray`.  Every index is checked
+ * before an address is formed from it.  The values are ONE float32 operation sequence (csrc/ls_hit_attr.h), which
+ * ls_debug_hit_attributes_on_triangle in lidarshooter_hip_debug.h runs on the host.
+ * Return codes, argument checks, stream order and the frame graph rule are those of ls_trace_rays (d_count must be 4-byte
+ * aligned); LS_INFO_RAY_QUERY_BUILT is left as it is. */
+int ls_hit_attributes(ls_tracer *tr, void *hip_stream, const void *d_rays, uint32_t n_rays,
+                      const void *d_hits, const uint32_t *d_count, uint32_t n, void *d_out);
+/* The same with host memory (pageable) in and out and no count word, on the handle's stream; returns when out is filled. */
+int ls_hit_attributes_host(ls_tracer *tr, const void *rays, uint32_t n_rays,
+                           const void *hits, uint32_t n, void *out);
+
 #ifdef __cplusplus
 }
 #endif

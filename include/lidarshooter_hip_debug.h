@@ -54,6 +54,11 @@ int ls_debug_expand_hits(void *dst_points32, const void *hits8, uint32_t n, cons
  * k_closest_points runs per triangle (csrc/ls_closest.h); d2 = +inf, q = 0 for a triangle that never counts */
 int ls_debug_closest_on_triangle(const float p[3], const float v0[3], const float v1[3], const float v2[3], float q[3], float *d2);
 
+/* the library's hit-attribute arithmetic on the host (no device, no handle): the float32 operation sequence k_hit_attributes
+ * runs per triangle (csrc/ls_hit_attr.h) -- the exact ray / triangle test from the origin o, then normal, incidence cosine,
+ * barycentrics and hit point.  Returns 1 when the test passes (*t and out9 written), 0 when it does not (nothing written). */
+int ls_debug_hit_attributes_on_triangle(const float o[3], const float d[3], const float v0[3], const float v1[3], const float v2[3], float *t, float out9[9] /* n, cos_inc, u, v, p */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,10 +52,12 @@ SYMBOLS = (
     "ls_tracer_set_sensor", "ls_tracer_set_sensor_tables", "ls_expand_gathered_hits_sized",
     "ls_trace_rays", "ls_trace_rays_host", "ls_occluded_rays", "ls_occluded_rays_host",
     "ls_closest_points", "ls_closest_points_host",
+    "ls_hit_attributes", "ls_hit_attributes_host",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
 DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_scene_size", "ls_debug_download_scene",
-                 "ls_debug_download_bvh", "ls_debug_sort_pairs", "ls_debug_expand_hits", "ls_debug_closest_on_triangle")
+                 "ls_debug_download_bvh", "ls_debug_sort_pairs", "ls_debug_expand_hits", "ls_debug_closest_on_triangle",
+                 "ls_debug_hit_attributes_on_triangle")
 
 
 class SensorDesc(C.Structure):
@@ -80,6 +82,9 @@ HIT_DTYPE = np.dtype([("ray", "<u4"), ("geom", "<u4"), ("prim", "<u4"), ("t", "<
 # ls_closest_points: a query point (sensor frame) with the largest distance of interest, and its answer
 POINT_QUERY_DTYPE = np.dtype([("point", "<f4", 3), ("radius", "<f4")])
 CLOSEST_DTYPE = np.dtype([("q", "<f4", 3), ("dist", "<f4"), ("geom", "<u4"), ("prim", "<u4"), ("index", "<u4"), ("pad", "<u4")])
+# ls_hit_attributes: surface attributes of one ls_hit (flags bit 0: valid; an invalid record is zeros but for `ray`)
+HIT_ATTR_DTYPE = np.dtype([("n", "<f4", 3), ("cos_inc", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4"), ("flags", "<u4"),
+                           ("p", "<f4", 3), ("ray", "<u4")])
 NODE_DTYPE = np.dtype([("llo", "<f4", 3), ("left", "<u4"), ("lhi", "<f4", 3), ("right", "<u4"),
                        ("rlo", "<f4", 3), ("pad0", "<u4"), ("rhi", "<f4", 3), ("pad1", "<u4")])
 LEAF_BIT = 0x80000000
@@ -183,6 +188,9 @@ def load() -> C.CDLL:
     L.ls_closest_points.argtypes = [vp, vp, vp, u32, vp]
     L.ls_closest_points_host.argtypes = [vp, vp, u32, vp]
     L.ls_debug_closest_on_triangle.argtypes = [f32p, f32p, f32p, f32p, f32p, f32p]
+    L.ls_hit_attributes.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp]
+    L.ls_hit_attributes_host.argtypes = [vp, vp, u32, vp, u32, vp]
+    L.ls_debug_hit_attributes_on_triangle.argtypes = [f32p, f32p, f32p, f32p, f32p, f32p, f32p]
     L.ls_geometry_type.argtypes = [vp, C.c_char_p]
     L.ls_debug_dense_hits.argtypes = [vp, f32p, u32p]
     L.ls_debug_trace_bruteforce.argtypes = [vp, f32p, u32p]
@@ -549,6 +557,33 @@ class Tracer:
         rc = self.L.ls_closest_points(self.h, stream, d_points, n, d_out)
         return -1 if rc == -1 else int(self._check(rc, "ls_closest_points"))
 
+    def hitAttributes(self, hits, rays=None):
+        """Surface attributes of hit records (ls_hit_attributes_host): `hits` a HIT_DTYPE array (a frame's, or traceRays'), `rays`
+        None -- the handle's own sensor rays, hit.ray the global ray index -- or the rays given to traceRays (float32 (n, 8) or
+        RAY_DTYPE).  -> (rc, HIT_ATTR_DTYPE[n]); rc = -1 (no commit, empty scene): every record invalid."""
+        h = np.ascontiguousarray(hits)
+        if h.dtype != HIT_DTYPE:
+            h = np.ascontiguousarray(h, np.uint32)
+            if h.ndim != 2 or h.shape[1] != 4:
+                raise ValueError("hits: HIT_DTYPE or uint32 (n, 4)")
+        n = h.shape[0]
+        r = None if rays is None else self._ray_array(rays)
+        out = np.zeros(n, HIT_ATTR_DTYPE)
+        rc = self.L.ls_hit_attributes_host(self.h, None if r is None else (r.ctypes.data if r.shape[0] else h.ctypes.data),
+                                           0 if r is None else r.shape[0], h.ctypes.data if n else None, n, out.ctypes.data if n else None)
+        if rc == -1:
+            out["ray"] = h["ray"] if h.dtype == HIT_DTYPE else h[:, 0]
+            return -1, out
+        self._check(rc, "ls_hit_attributes_host")
+        return int(rc), out
+
+    def hitAttributesDevice(self, d_hits: int, n: int, d_out: int, d_rays: int = 0, n_rays: int = 0, d_count: int = 0, stream=None) -> int:
+        """ls_hit_attributes on device pointers (n 16-byte ls_hit records in, 48-byte records out; d_rays = 0: the handle's sensor
+        rays; d_count != 0: a device word, min(n, *d_count) records are handled); enqueued on `stream` (a hipStream_t as an int,
+        None: the handle's), no wait.  -> 0, or -1 on an empty / uncommitted scene (d_out not written)."""
+        rc = self.L.ls_hit_attributes(self.h, stream, d_rays or None, n_rays, d_hits or None, d_count or None, n, d_out or None)
+        return -1 if rc == -1 else int(self._check(rc, "ls_hit_attributes"))
+
     # ---- test hooks
     def generateRaysAos(self, d_rays: int | None, d_hits: int | None):
         """LidarDevice::allRaysGPU's two buffers (Ray 32 B, Hit 24 B per ray) in device memory of the caller."""
@@ -606,3 +641,16 @@ def closest_on_triangle(p, v0, v1, v2):
     if rc != 0:
         raise LidarShooterHipError(f"ls_debug_closest_on_triangle: status {rc}")
     return q, np.float32(d2.value)
+
+
+def hit_attributes_on_triangle(o, d, v0, v1, v2):
+    """ls_debug_hit_attributes_on_triangle: the library's float32 hit-attribute arithmetic on the host -> None when the exact test
+    fails, else (t float32, out float32[9] = n, cos_inc, u, v, p)"""
+    L = load()
+    a = [np.ascontiguousarray(x, np.float32).reshape(3) for x in (o, d, v0, v1, v2)]
+    out = np.zeros(9, np.float32)
+    t = C.c_float()
+    rc = L.ls_debug_hit_attributes_on_triangle(*[_f32p(x) for x in a], C.byref(t), _f32p(out))
+    if rc < 0:
+        raise LidarShooterHipError(f"ls_debug_hit_attributes_on_triangle: status {rc}")
+    return (np.float32(t.value), out) if rc == 1 else None

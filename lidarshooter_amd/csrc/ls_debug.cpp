@@ -3,6 +3,7 @@
 #include "../../include/lidarshooter_hip_debug.h"
 #include "ls_internal.h"
 #include "ls_closest.h"
+#include "ls_hit_attr.h"
 
 using namespace lsi;
 
@@ -115,6 +116,13 @@ int ls_debug_closest_on_triangle(const float p[3], const float v0[3], const floa
     if (!p || !v0 || !v1 || !v2 || !q || !d2) return LS_ERR_INVALID_ARGUMENT;
     ls::closest_on_triangle(p, v0, v1, v2, q, d2);
     return LS_OK;
+}
+
+int ls_debug_hit_attributes_on_triangle(const float o[3], const float d[3], const float v0[3], const float v1[3], const float v2[3], float *t,
+                                        float out9[9])
+{
+    if (!o || !d || !v0 || !v1 || !v2 || !t || !out9) return LS_ERR_INVALID_ARGUMENT;
+    return ls::hit_attributes_on_triangle(o, d, v0, v1, v2, t, out9) ? 1 : 0;
 }
 
 }  // extern "C"

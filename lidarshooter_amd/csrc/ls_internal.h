@@ -5,7 +5,8 @@
 //   ls_registry.cpp  ITracer's geometry bookkeeping: add / remove / update (EmbreeTracer.cpp:115-288), uploads
 //   ls_commit.cpp    commitScene: layout, group-culling data, BVH build / refit / instanced hierarchies
 //   ls_trace.cpp     traceScene: output buffers, frames in flight, the per-frame launch sequence, stage timings
-//   ls_rays.cpp      ls_trace_rays: the query set of per-geometry hierarchies (built lazily), batches of geometries per launch
+//   ls_rays.cpp      ls_trace_rays: the query set of per-geometry hierarchies (built lazily), batches of geometries per launch;
+//                    ls_hit_attributes: the per-geomID table of its gather kernel
 //   ls_host_pool.cpp worker threads for host-side copies, point expansion
 //   ls_debug.cpp     include/lidarshooter_hip_debug.h (tests and bench.py only)
 #pragma once
@@ -286,6 +287,15 @@ struct ls_tracer {
         hipEvent_t ev_ready = nullptr, ev_done = nullptr;
         long last_built = 0;                   // LS_INFO_RAY_QUERY_BUILT
     } rq;
+    // ls_hit_attributes (ls_rays.cpp): the per-geomID table k_hit_attributes reads, refreshed by the call that finds it out of
+    // date (a pose, a vertex or index buffer, the registry or the sensor pose changed)
+    struct HitAttr {
+        lsi::DevBuf<ls::AttrGeom> table;       // device, indexed by geomID
+        std::vector<ls::AttrGeom> current;     // what it holds
+        ls::AttrGeom *h_stage = nullptr;       // pinned staging of the upload ...
+        size_t stage_cap = 0;
+        hipEvent_t ev_stage = nullptr;         // ... recorded behind the last copy that reads it
+    } ha;
     uint64_t upload_seq = 0;
 
     // options / measurement
@@ -412,6 +422,7 @@ int hier_build(ls_tracer *tr, HierSet &hs, hipStream_t s, size_t i, const Geomet
                const float *R9, const float *T3, uint32_t leaf_size, bool refit, bool widen);
 // ls_rays.cpp
 void ray_query_release(ls_tracer *tr);
+void hit_attr_release(ls_tracer *tr);
 
 }  // namespace lsi
 

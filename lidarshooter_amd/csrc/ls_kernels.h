@@ -274,6 +274,19 @@ struct PointMargins {
 };
 void launch_closest_points(hipStream_t s, uint32_t grid_blocks, const void *points, uint32_t n, const RayBatch &batch, const PointMargins &pm,
                            const WideNode *wide, const TriRecord *records, uint32_t leaf_size, void *out, uint32_t *counter, uint32_t *spill);
+// ls_hit_attributes (ls_attr.hip): surface attributes of n ls_hit records (min(n, *d_count) with a device count), 48 bytes out
+// per record.  The table is indexed by geomID (ids are sparse after removals: a free id has verts = nullptr), in device memory;
+// rays = nullptr: hit.ray indexes the handle's full raster (tb), else n_rays 32-byte caller rays.
+struct alignas(16) AttrGeom {
+    const uint8_t *verts;             // vertex records as uploaded (Geometry::raw()); nullptr: no such geometry
+    const uint32_t *idx;              // 3 * n_tris triangle indices (Geometry::idx(): a quad's two triangles at 2q, 2q + 1)
+    uint32_t stride, n_elems, n_verts;
+    uint32_t quad;                    // 1: ls_hit.prim is the quad index
+    Affine m;                         // mesh -> sensor, as everywhere else
+};
+static_assert(sizeof(AttrGeom) == 128, "one table entry is 128 bytes");
+void launch_hit_attributes(hipStream_t s, const void *hits, const uint32_t *d_count, uint32_t n, const void *rays, uint32_t n_rays,
+                           const SensorTables &tb, const AttrGeom *table, uint32_t n_table, void *out);
 void launch_rowcount(hipStream_t s, const uint32_t *gid, uint32_t nrays, uint32_t *row_counts, uint32_t *queue_heads = nullptr);   // queue_heads: zeroed for the next k_trace
 // Progress of a synchronous frame whose compact points go straight to pinned host memory (ls_trace_scene_begin /
 // ls_trace_scene_expand): the device publishes, with system-scope release, (1) the frame's hit count as the pack pass

@@ -1,7 +1,8 @@
 // ls_rays.cpp -- ls_trace_rays / ls_trace_rays_host: closest hits of caller-supplied rays against the committed scene;
 // ls_occluded_rays / ls_occluded_rays_host: whether each ray hits anything (the same query set and walk, stopping at a hit);
 // ls_closest_points / ls_closest_points_host: the nearest surface point to each caller point (the same query set, a
-// distance-ordered walk: ls_points.hip).
+// distance-ordered walk: ls_points.hip);
+// ls_hit_attributes / ls_hit_attributes_host: surface attributes of hit records (no hierarchy: a gather, ls_attr.hip; at the end).
 //
 // The query set (ls_tracer::RayQuery) is a hierarchy set of its own -- one hierarchy per geometry, built by the kernels of
 // the instanced commit (hier_layout / hier_build, ls_commit.cpp) into buffers nothing in the frame path reads or writes,
@@ -25,6 +26,18 @@ constexpr uint32_t kMaxRayLaunches = (uint32_t)ls::kMaxGeoms / (uint32_t)ls::kGe
 
 bool same_floats(const float *a, const float *b, size_t n) { return std::memcmp(a, b, n * sizeof(float)) == 0; }
 
+// the registry's geometry of layout entry i, provided it still is what the last commit laid out (every query's check)
+int committed_geometry(ls_tracer *tr, size_t i, Geometry **out)
+{
+    auto it = tr->geoms.find(tr->layout[i].name);
+    if (it == tr->geoms.end()) return fail(tr, LS_ERR_NOT_COMMITTED, "geometry removed since the last commit");
+    Geometry &ge = it->second;
+    if (ge.id != tr->slot_geom_ids[i] || ge.n_tris != tr->slot_tri_first[i + 1] - tr->slot_tri_first[i] || !ge.has_verts || !ge.has_idx)
+        return fail(tr, LS_ERR_NOT_COMMITTED, "the geometries changed since the last commit");
+    *out = &ge;
+    return LS_OK;
+}
+
 // the query set brought up to date with the committed layout and the geometries' current data (stream-ordered on s)
 int ray_query_prepare(ls_tracer *tr, hipStream_t s, std::vector<Geometry *> &order, std::vector<bool> &sensor_frame)
 {
@@ -35,12 +48,9 @@ int ray_query_prepare(ls_tracer *tr, hipStream_t s, std::vector<Geometry *> &ord
     std::vector<int> ids(n);
     std::vector<uint32_t> firsts(2 * n);   // where every geometry's vertices and triangles start in the layout
     for (size_t i = 0; i < n; ++i) {
-        auto it = tr->geoms.find(tr->layout[i].name);
-        if (it == tr->geoms.end()) return fail(tr, LS_ERR_NOT_COMMITTED, "geometry removed since the last commit");
-        Geometry &ge = it->second;
-        if (ge.id != tr->slot_geom_ids[i] || ge.n_tris != tr->slot_tri_first[i + 1] - tr->slot_tri_first[i] || !ge.has_verts || !ge.has_idx)
-            return fail(tr, LS_ERR_NOT_COMMITTED, "the geometries changed since the last commit");
-        order[i] = &ge;
+        int rc0;
+        if ((rc0 = committed_geometry(tr, i, &order[i]))) return rc0;
+        Geometry &ge = *order[i];
         ids[i] = ge.id;
         firsts[2 * i] = tr->layout[i].vfirst;
         firsts[2 * i + 1] = tr->layout[i].tfirst;
@@ -318,7 +328,123 @@ int rays_host_locked(ls_tracer *tr, const void *rays, uint32_t n, void *out, con
     return LS_OK;
 }
 
+// ---- ls_hit_attributes: no hierarchy, a gather over hit records (ls_attr.hip) -------------------------------------------
+
+// the table k_hit_attributes reads, one entry per geomID up to the highest committed one (free ids stay zero), from the committed
+// layout and the geometries' current buffers and poses (committed_geometry's checks); uploaded on s when it differs from what
+// the device holds
+int attr_table_prepare(ls_tracer *tr, hipStream_t s)
+{
+    ls_tracer::HitAttr &a = tr->ha;
+    const size_t n = tr->layout.size();
+    int max_id = -1;
+    for (size_t i = 0; i < n; ++i) max_id = std::max(max_id, tr->slot_geom_ids[i]);
+    std::vector<ls::AttrGeom> tab((size_t)(max_id + 1));
+    if (!tab.empty()) std::memset(static_cast<void *>(tab.data()), 0, tab.size() * sizeof(ls::AttrGeom));
+    for (size_t i = 0; i < n; ++i) {
+        Geometry *gp = nullptr;
+        int rc0;
+        if ((rc0 = committed_geometry(tr, i, &gp))) return rc0;
+        const Geometry &ge = *gp;
+        ls::AttrGeom &e = tab[(size_t)ge.id];
+        e.verts = static_cast<const uint8_t *>(ge.raw());
+        e.idx = ge.idx();
+        e.stride = ge.stride;
+        e.n_elems = ge.n_elems;
+        e.n_verts = ge.n_verts;
+        e.quad = ge.quad ? 1u : 0u;
+        std::memcpy(e.m.a, ge.affine, sizeof(e.m.a));
+        std::memcpy(e.m.rinv, tr->rinv, sizeof(e.m.rinv));
+        std::memcpy(e.m.t, tr->t, sizeof(e.m.t));
+    }
+    const size_t bytes = tab.size() * sizeof(ls::AttrGeom);
+    if (tab.size() == a.current.size() && (!bytes || std::memcmp(tab.data(), a.current.data(), bytes) == 0)) return LS_OK;
+    a.current.clear();   // (whatever fails from here on, the next call refreshes: ensure may give the table another buffer)
+    int rc;
+    if ((rc = ensure(tr, a.table, tab.size()))) return rc;
+    if (!a.ev_stage) LS_HIP(hipEventCreateWithFlags(&a.ev_stage, hipEventDisableTiming));
+    LS_HIP(hipEventSynchronize(a.ev_stage));   // (the copy of an earlier refresh may still be reading the staging buffer)
+    if (a.stage_cap < tab.size()) {
+        if (a.h_stage) LS_HIP(hipHostFree(a.h_stage));
+        a.h_stage = nullptr;
+        a.stage_cap = 0;
+        LS_HIP(hipHostMalloc(reinterpret_cast<void **>(&a.h_stage), bytes + bytes / 8, hipHostMallocDefault));
+        a.stage_cap = (bytes + bytes / 8) / sizeof(ls::AttrGeom);
+    }
+    std::memcpy(static_cast<void *>(a.h_stage), tab.data(), bytes);
+    LS_HIP(hipMemcpyAsync(a.table.p, a.h_stage, bytes, hipMemcpyHostToDevice, s));
+    LS_HIP(hipEventRecord(a.ev_stage, s));
+    a.current.swap(tab);
+    return LS_OK;
+}
+
+// argument checks, return codes and stream order of rays_locked; LS_INFO_RAY_QUERY_BUILT is left as it is
+int attr_locked(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n_rays, const void *d_hits, const uint32_t *d_count, uint32_t n,
+                void *d_out)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (n && (!d_hits || !d_out)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null hit records or output");
+    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_hits & 15u) || ((uintptr_t)d_out & 15u) || ((uintptr_t)d_count & 3u))
+        return fail(tr, LS_ERR_INVALID_ARGUMENT, "rays, hit records and attribute records must be 16-byte aligned, the count 4-byte aligned");
+    if (n > 0xFFF00000u) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many hit records in one call");
+    if (!tr->committed || tr->n_tris == 0) return -1;   // as ls_trace_scene; nothing is written
+    if (!n) return LS_OK;
+    int rc;
+    // after everything already issued on the handle: its frames in flight (whose hit records these may be), its mesh copies
+    if ((rc = flush_pipeline(tr))) return rc;
+    ls_tracer::RayQuery &q = tr->rq;
+    if (!q.ev_ready) LS_HIP(hipEventCreateWithFlags(&q.ev_ready, hipEventDisableTiming));
+    if (!q.ev_done) LS_HIP(hipEventCreateWithFlags(&q.ev_done, hipEventDisableTiming));
+    if (s != tr->stream) {
+        LS_HIP(hipEventRecord(q.ev_ready, tr->stream));
+        LS_HIP(hipStreamWaitEvent(s, q.ev_ready, 0));
+    }
+    if ((rc = attr_table_prepare(tr, s))) return rc;
+    ls::launch_hit_attributes(s, d_hits, d_count, n, d_rays, n_rays, tables(tr), tr->ha.table.p, (uint32_t)tr->ha.current.size(), d_out);
+    LS_HIP(hipGetLastError());
+    if (s != tr->stream) {
+        LS_HIP(hipEventRecord(q.ev_done, s));
+        LS_HIP(hipStreamWaitEvent(tr->stream, q.ev_done, 0));
+    }
+    return LS_OK;
+}
+
+// the host-memory variant: hit records, rays and results staged in q.io, on the handle's stream; returns when out is filled
+int attr_host_locked(ls_tracer *tr, const void *rays, uint32_t n_rays, const void *hits, uint32_t n, void *out)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (n && (!hits || !out)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null hit records or output");
+    if (n > 0xFFF00000u || (rays && n_rays > 0xFFF00000u)) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many records in one call");
+    if (!tr->committed || tr->n_tris == 0) return -1;   // (before n = 0: the same answer as the device entry point)
+    if (!n) return LS_OK;
+    ls_tracer::RayQuery &q = tr->rq;
+    hipStream_t s = tr->stream;
+    int rc;
+    if ((rc = flush_pipeline(tr))) return rc;
+    const size_t hit_bytes = (size_t)n * 16, ray_bytes = rays ? (size_t)n_rays * 32 : 0, out_bytes = (size_t)n * 48;
+    if ((rc = ensure(tr, q.io, hit_bytes + ray_bytes + out_bytes))) return rc;
+    uint8_t *d_hits = q.io.p, *d_rays = q.io.p + hit_bytes, *d_out = d_rays + ray_bytes;
+    LS_HIP(hipMemcpyAsync(d_hits, hits, hit_bytes, hipMemcpyHostToDevice, s));
+    if (ray_bytes) LS_HIP(hipMemcpyAsync(d_rays, rays, ray_bytes, hipMemcpyHostToDevice, s));
+    if ((rc = attr_locked(tr, s, rays ? d_rays : nullptr, n_rays, d_hits, nullptr, n, d_out))) return rc;
+    LS_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    LS_HIP(hipStreamSynchronize(s));
+    return LS_OK;
+}
+
 }  // namespace
+
+void hit_attr_release(ls_tracer *tr)
+{
+    ls_tracer::HitAttr &a = tr->ha;
+    if (a.ev_stage) { (void)hipEventSynchronize(a.ev_stage); (void)hipEventDestroy(a.ev_stage); }
+    if (a.h_stage) (void)hipHostFree(a.h_stage);
+    release(a.table);
+    a.ev_stage = nullptr;
+    a.h_stage = nullptr;
+    a.stage_cap = 0;
+    a.current.clear();
+}
 
 }  // namespace lsi
 
@@ -360,6 +486,19 @@ int ls_closest_points_host(ls_tracer *tr, const void *points, uint32_t n, void *
 {
     LS_ENTER(tr);
     return rays_host_locked(tr, points, n, out, kNearest);
+}
+
+int ls_hit_attributes(ls_tracer *tr, void *hip_stream, const void *d_rays, uint32_t n_rays, const void *d_hits, const uint32_t *d_count, uint32_t n,
+                      void *d_out)
+{
+    LS_ENTER(tr);
+    return attr_locked(tr, hip_stream ? static_cast<hipStream_t>(hip_stream) : tr->stream, d_rays, n_rays, d_hits, d_count, n, d_out);
+}
+
+int ls_hit_attributes_host(ls_tracer *tr, const void *rays, uint32_t n_rays, const void *hits, uint32_t n, void *out)
+{
+    LS_ENTER(tr);
+    return attr_host_locked(tr, rays, n_rays, hits, n, out);
 }
 
 }  // extern "C"

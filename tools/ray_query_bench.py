@@ -3,9 +3,10 @@ scene in the same run, 1 M incoherent rays, and the first query's lazy build; th
 three ray sets -- the sensor's own rays, the 1 M incoherent rays, 1 M segments (origins 0.2-5 m above the ground, targets at
 random scene points, tmax = 1 - 1e-4) -- whose occluded counts must equal the hit counts; then ls_closest_points on three point sets -- the frame's own cloud with
 every point jittered by a few centimetres (cloud to mesh), 1 M points uniform in the scene's box, the same with a 0.5 m
-radius -- next to ls_trace_rays on the incoherent rays.  Prints host-side event timings;
-for kernel times (k_trace_rays, k_occluded_rays, k_closest_points: its launches come in the order of the sets, 1 + reps
-each) run it under the profiler in a run of its own:
+radius -- next to ls_trace_rays on the incoherent rays; then ls_hit_attributes on the frame's own hit records (sensor-ray mode) and
+on the hits of the 1 M incoherent rays, next to ls_trace_rays on those rays.  Prints host-side event timings;
+for kernel times (k_trace_rays, k_occluded_rays, k_closest_points, k_hit_attributes: its launches come in the order of the
+sets, 1 + reps each) run it under the profiler in a run of its own:
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/ray_query_bench.py
 usage: python tools/ray_query_bench.py [--reps N]
 """
@@ -121,6 +122,19 @@ def main():
         dist = rec[found, 3].view(np.float32)
         print(f"closest points, {name}: {k} points, {int(np.count_nonzero(found))} found, mean dist {float(dist.mean()) if dist.size else 0:.4f} m; "
               f"ls_closest_points {p_ms * 1e3:.1f} us per query ({p_ms / inc_ms:.2f}x ls_trace_rays on {m} incoherent rays)")
+    # ls_hit_attributes: the frame's hit records against the sensor's own rays, the incoherent rays' hits against those rays
+    rc, _, fh = tr.traceScene(0)
+    assert rc == 0
+    d_fh = torch.from_numpy(np.ascontiguousarray(fh).view(np.uint8).reshape(-1)).to("cuda:0")
+    inc_ms, o = timed(d_inc, m, a.reps)
+    d_ih = o   # the incoherent rays' ls_hit records, misses included
+    for name, d_h, k, rays, n_rays in (("frame hits, sensor rays", d_fh, fh.shape[0], 0, 0), ("incoherent rays' hits", d_ih, m, d_inc.data_ptr(), m)):
+        q = lambda h, cnt, out_ptr, stream: tr.hitAttributesDevice(h, cnt, out_ptr, d_rays=rays, n_rays=n_rays, stream=stream)   # noqa: E731
+        a_ms, o = timed(d_h, k, a.reps, q, 48)
+        rec = o.cpu().numpy().view(capi.HIT_ATTR_DTYPE)
+        valid = rec["flags"] == 1
+        print(f"hit attributes, {name}: {k} records, {int(np.count_nonzero(valid))} valid, mean cos_inc {float(rec['cos_inc'][valid].mean()):.3f}; "
+              f"ls_hit_attributes {a_ms * 1e3:.1f} us per query ({a_ms / inc_ms:.3f}x ls_trace_rays on {m} incoherent rays, {inc_ms * 1e3:.1f} us)")
     tr.close()
 
 
