@@ -564,6 +564,67 @@ int ls_hit_attributes(ls_tracer *tr, void *hip_stream, const void *d_rays, uint3
 int ls_hit_attributes_host(ls_tracer *tr, const void *rays, uint32_t n_rays,
                            const void *hits, uint32_t n, void *out);
 
+/* ---- sensor returns: from exact hit records to what a LiDAR delivers -- intensity that falls with incidence and range, a
+ * range gate, returns too weak to detect dropping out, Gaussian range noise, random drop-out -- for hit records of the frame
+ * (ls_frame.d_hits / hits) or of ls_trace_rays.  The kept returns are compacted IN INPUT ORDER into a ready points32 / ls_hit
+ * pair in device memory, with their count: no host read-back, no 48-byte attribute record in between. */
+#define LS_RETURN_LAMBERT   1u  /* intensity carries the incidence term */
+#define LS_RETURN_TWO_SIDED 2u  /* with LAMBERT: |cos_inc| instead of max(cos_inc, 0) */
+
+typedef struct ls_return_model {   /* 64 bytes, no pointers */
+    float range_min, range_max;        /* keep when range_min <= r <= range_max, r = t * |d| (true range); 0 / +inf: no gate */
+    float intensity_scale;             /* I0; 64.0 with flags = 0 and ref_range = 0 reproduces the frame's constant */
+    float ref_range;                   /* r0 > 0: falloff (r0 / max(r, r0))^2; 0: none */
+    float intensity_floor;             /* returns with I < floor are lost (0: none) */
+    float intensity_max;               /* saturation (+inf: none) */
+    float noise_sigma0, noise_sigma1;  /* sigma = sigma0 + sigma1 * r, metres along the ray */
+    float dropout;                     /* probability in [0, 1] of losing a return at random */
+    uint32_t seed;
+    uint32_t flags;
+    uint32_t reserved[5];              /* must be 0 */
+} ls_return_model;
+
+/*   d_rays, n_rays, d_hits, d_count, n: exactly as ls_hit_attributes (d_rays = NULL: the handle's own sensor rays, hit.ray the
+ *            global ray index whatever the shard; d_count: NULL or the device word of ls_trace_scene_async, min(n, *d_count)
+ *            records are handled).
+ *   d_reflectivity: NULL, or n_reflectivity floats in device memory indexed by geomID; NULL or geom >= n_reflectivity: 1.0.
+ *   frame_index: part of the random numbers' counter -- another frame, other noise; the same frame, the same noise.
+ *   d_points32: NULL, or room for n 32-byte points in the ls_frame.points32 layout (x, y, z f32@0, 0@12, intensity f32@16,
+ *            ring i32@20, 0@24..31), 16-byte aligned; ring = hit.ray / H for sensor rays, 0 for caller rays.
+ *   d_hits_out: NULL, or room for n ls_hit records, 16-byte aligned: the kept records with t replaced by the noisy t'.
+ *   d_n_out: a device word (not NULL): the count of kept returns.  Nothing is written past record *d_n_out.
+ * The outputs must not overlap the inputs.  Per handled record, ONE float32 operation sequence (csrc/ls_return_model.h;
+ * ls_debug_return_model in lidarshooter_hip_debug.h runs it on the host):
+ *   1. the record counts when ls_hit_attributes calls it valid (the exact test on the named triangle, t bit-equal to hit.t);
+ *      an invalid record is lost;
+ *   2. len = sqrtf((dx dx + dy dy) + dz dz), r = t * len;
+ *   3. c = 1; with LAMBERT max(cos_inc, 0); with LAMBERT | TWO_SIDED |cos_inc|;
+ *   4. ref_range > 0: f = q q, q = ref_range / max(r, ref_range); else f = 1;
+ *   5. I = ((intensity_scale * rho) * c) * f, and I = intensity_max where it is larger;
+ *   6. Philox4x32-10 with key (seed, 0) and counters (hit.ray, frame_index, j, 0), j = 0, 1 -> words a0..a3, b0..b3 -- keyed by
+ *      the RAY index, not the record's position: any subset, order or azimuth shard sees the noise of the full turn;
+ *      the return is dropped when dropout > 0 and (float)(b2 >> 8) * 2^-24 < dropout; z = (float)((int)S - 393210) * 2^-16 with
+ *      S the sum of the twelve 16-bit halves of a0, a1, a2, a3, b0, b1 (standard deviation 1, tails to +-6);
+ *   7. both sigmas 0: t' = t; else sigma = noise_sigma0 + noise_sigma1 * r, t' = t + (sigma * z) / len; the point is o + t' d
+ *      per axis, t' d with no sum for a sensor ray (the frame's bits);
+ *   8. kept when valid, range_min <= r <= range_max, I >= intensity_floor (a NaN intensity is lost), not dropped, t' > 0.
+ * LS_ERR_INVALID_ARGUMENT before any device call: a NULL handle or model, a NaN field, range_min > range_max, a negative
+ * scale, floor, sigma, ref_range or range_min, dropout outside [0, 1], unknown flag bits, non-zero reserved words,
+ * n_reflectivity > 0 with a NULL pointer.  The other return codes, the alignment checks (points and records 16 bytes, the
+ * words and the reflectivities 4), stream order and the frame graph rule are those of ls_hit_attributes; -1 writes nothing;
+ * n = 0 gives *d_n_out = 0; LS_INFO_RAY_QUERY_BUILT is left as it is.  Calls on one handle use a scratch buffer of the handle
+ * (32 bytes per record) one after the other. */
+int ls_apply_return_model(ls_tracer *tr, void *hip_stream, const ls_return_model *model, uint32_t frame_index,
+                          const void *d_rays, uint32_t n_rays, const void *d_hits, const uint32_t *d_count, uint32_t n,
+                          const float *d_reflectivity, uint32_t n_reflectivity,
+                          void *d_points32, void *d_hits_out, uint32_t *d_n_out);
+/* The same with host memory (pageable) in and out and no count word, on the handle's stream; returns when the outputs are
+ * filled (*n_out records of each). */
+int ls_apply_return_model_host(ls_tracer *tr, const ls_return_model *model, uint32_t frame_index,
+                               const void *rays, uint32_t n_rays, const void *hits, uint32_t n,
+                               const float *reflectivity, uint32_t n_reflectivity,
+                               void *points32, void *hits_out, uint32_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,15 @@ int ls_debug_closest_on_triangle(const float p[3], const float v0[3], const floa
  * barycentrics and hit point.  Returns 1 when the test passes (*t and out9 written), 0 when it does not (nothing written). */
 int ls_debug_hit_attributes_on_triangle(const float o[3], const float d[3], const float v0[3], const float v1[3], const float v2[3], float *t, float out9[9] /* n, cos_inc, u, v, p */);
 
+/* Philox4x32-10 as ls_apply_return_model draws it (csrc/ls_return_model.h), on the host: no device, no handle */
+int ls_debug_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+/* the library's return model on the host (no device, no handle): steps 2-8 of ls_apply_return_model for one valid hit of ray
+ * `ray` -- t, len = |d|, the incidence cosine, the reflectivity rho --, the float32 operation sequence k_returns_eval runs.
+ * Returns 1 when the return is kept, 0 when it is lost (*t_out = t', *intensity = I either way), a negative status for NULL
+ * pointers or a model ls_apply_return_model refuses. */
+int ls_debug_return_model(const ls_return_model *m, uint32_t ray, uint32_t frame_index, float t, float len, float cos_inc, float rho,
+                          float *t_out, float *intensity);
+
 #ifdef __cplusplus
 }
 #endif

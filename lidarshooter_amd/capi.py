@@ -53,11 +53,12 @@ SYMBOLS = (
     "ls_trace_rays", "ls_trace_rays_host", "ls_occluded_rays", "ls_occluded_rays_host",
     "ls_closest_points", "ls_closest_points_host",
     "ls_hit_attributes", "ls_hit_attributes_host",
+    "ls_apply_return_model", "ls_apply_return_model_host",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
 DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_scene_size", "ls_debug_download_scene",
                  "ls_debug_download_bvh", "ls_debug_sort_pairs", "ls_debug_expand_hits", "ls_debug_closest_on_triangle",
-                 "ls_debug_hit_attributes_on_triangle")
+                 "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model")
 
 
 class SensorDesc(C.Structure):
@@ -70,6 +71,27 @@ class SensorTables(C.Structure):
                 ("elevation_deg", C.POINTER(C.c_float)), ("n_vertical", C.c_uint32),
                 ("sin_phi", C.POINTER(C.c_float)), ("cos_phi", C.POINTER(C.c_float)), ("h_count", C.c_uint32),
                 ("h_begin_deg", C.c_float), ("h_step_deg", C.c_float), ("Rinv", C.c_float * 9), ("t", C.c_float * 3)]
+
+
+LS_RETURN_LAMBERT = 1
+LS_RETURN_TWO_SIDED = 2
+
+
+class ReturnModel(C.Structure):
+    """ls_return_model (64 bytes): the defaults change nothing -- no gate, no floor, no saturation, no noise, no drop-out, the
+    frame's constant intensity 64.0"""
+    _fields_ = [("range_min", C.c_float), ("range_max", C.c_float), ("intensity_scale", C.c_float), ("ref_range", C.c_float),
+                ("intensity_floor", C.c_float), ("intensity_max", C.c_float), ("noise_sigma0", C.c_float), ("noise_sigma1", C.c_float),
+                ("dropout", C.c_float), ("seed", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.range_max = self.intensity_max = float("inf")
+        self.intensity_scale = 64.0
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError(f"ls_return_model has no field {k}")
+            setattr(self, k, v)
 
 
 class Frame(C.Structure):
@@ -191,6 +213,10 @@ def load() -> C.CDLL:
     L.ls_hit_attributes.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp]
     L.ls_hit_attributes_host.argtypes = [vp, vp, u32, vp, u32, vp]
     L.ls_debug_hit_attributes_on_triangle.argtypes = [f32p, f32p, f32p, f32p, f32p, f32p, f32p]
+    L.ls_apply_return_model.argtypes = [vp, vp, C.POINTER(ReturnModel), u32, vp, u32, vp, vp, u32, vp, u32, vp, vp, vp]
+    L.ls_apply_return_model_host.argtypes = [vp, C.POINTER(ReturnModel), u32, vp, u32, vp, u32, vp, u32, vp, vp, u32p]
+    L.ls_debug_philox4x32.argtypes = [u32p, u32p, u32p]
+    L.ls_debug_return_model.argtypes = [C.POINTER(ReturnModel), u32, u32, C.c_float, C.c_float, C.c_float, C.c_float, f32p, f32p]
     L.ls_geometry_type.argtypes = [vp, C.c_char_p]
     L.ls_debug_dense_hits.argtypes = [vp, f32p, u32p]
     L.ls_debug_trace_bruteforce.argtypes = [vp, f32p, u32p]
@@ -584,6 +610,39 @@ class Tracer:
         rc = self.L.ls_hit_attributes(self.h, stream, d_rays or None, n_rays, d_hits or None, d_count or None, n, d_out or None)
         return -1 if rc == -1 else int(self._check(rc, "ls_hit_attributes"))
 
+    def applyReturnModel(self, model: ReturnModel, hits, rays=None, reflectivity=None, frame_index: int = 0):
+        """Sensor returns from hit records (ls_apply_return_model_host): `hits` and `rays` as hitAttributes takes them, `reflectivity`
+        None or float32 per geomID.  -> (rc, points uint8[k, 32], hits HIT_DTYPE[k] with the noisy t): the kept returns in input
+        order; rc = -1 (no commit, empty scene): none."""
+        h = np.ascontiguousarray(hits)
+        if h.dtype != HIT_DTYPE:
+            h = np.ascontiguousarray(h, np.uint32)
+            if h.ndim != 2 or h.shape[1] != 4:
+                raise ValueError("hits: HIT_DTYPE or uint32 (n, 4)")
+        n = h.shape[0]
+        r = None if rays is None else self._ray_array(rays)
+        rho = None if reflectivity is None else np.ascontiguousarray(reflectivity, np.float32).reshape(-1)
+        pts, out, k = np.zeros((n, 32), np.uint8), np.zeros(n, HIT_DTYPE), C.c_uint32(0)
+        rc = self.L.ls_apply_return_model_host(self.h, C.byref(model), frame_index,
+                                               None if r is None else (r.ctypes.data if r.shape[0] else h.ctypes.data), 0 if r is None else r.shape[0],
+                                               h.ctypes.data if n else None, n, rho.ctypes.data if rho is not None and rho.size else None,
+                                               0 if rho is None else rho.size, pts.ctypes.data if n else None, out.ctypes.data if n else None, C.byref(k))
+        if rc == -1:
+            return -1, pts[:0], out[:0]
+        self._check(rc, "ls_apply_return_model_host")
+        return int(rc), pts[:k.value].copy(), out[:k.value].copy()
+
+    def applyReturnModelDevice(self, model: ReturnModel, d_hits: int, n: int, d_n_out: int, d_points32: int = 0, d_hits_out: int = 0, d_rays: int = 0,
+                               n_rays: int = 0, d_count: int = 0, d_reflectivity: int = 0, n_reflectivity: int = 0, frame_index: int = 0,
+                               stream=None) -> int:
+        """ls_apply_return_model on device pointers (n ls_hit records in; up to n 32-byte points and n ls_hit records out, either may
+        be 0; the count in the device word d_n_out; d_rays = 0: the handle's sensor rays; d_count != 0: a device word, min(n, *d_count)
+        records are handled); enqueued on `stream` (a hipStream_t as an int, None: the handle's), no wait.  -> 0, or -1 on an empty
+        / uncommitted scene (nothing written)."""
+        rc = self.L.ls_apply_return_model(self.h, stream, C.byref(model), frame_index, d_rays or None, n_rays, d_hits or None, d_count or None, n,
+                                          d_reflectivity or None, n_reflectivity, d_points32 or None, d_hits_out or None, d_n_out or None)
+        return -1 if rc == -1 else int(self._check(rc, "ls_apply_return_model"))
+
     # ---- test hooks
     def generateRaysAos(self, d_rays: int | None, d_hits: int | None):
         """LidarDevice::allRaysGPU's two buffers (Ray 32 B, Hit 24 B per ray) in device memory of the caller."""
@@ -654,3 +713,26 @@ def hit_attributes_on_triangle(o, d, v0, v1, v2):
     if rc < 0:
         raise LidarShooterHipError(f"ls_debug_hit_attributes_on_triangle: status {rc}")
     return (np.float32(t.value), out) if rc == 1 else None
+
+
+def philox4x32(ctr, key):
+    """ls_debug_philox4x32: Philox4x32-10 of a 4-word counter under a 2-word key -> uint32[4]"""
+    L = load()
+    c, k, out = np.ascontiguousarray(ctr, np.uint32).reshape(4), np.ascontiguousarray(key, np.uint32).reshape(2), np.zeros(4, np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    rc = L.ls_debug_philox4x32(c.ctypes.data_as(u32p), k.ctypes.data_as(u32p), out.ctypes.data_as(u32p))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_debug_philox4x32: status {rc}")
+    return out
+
+
+def return_model(model: ReturnModel, ray, frame_index, t, length, cos_inc, rho):
+    """ls_debug_return_model: the library's float32 return model on the host for one valid hit -> (kept bool, t' float32,
+    intensity float32)"""
+    L = load()
+    t_out, inten = C.c_float(), C.c_float()
+    rc = L.ls_debug_return_model(C.byref(model), int(ray), int(frame_index), float(t), float(length), float(cos_inc), float(rho),
+                                 C.byref(t_out), C.byref(inten))
+    if rc < 0:
+        raise LidarShooterHipError(f"ls_debug_return_model: status {rc}")
+    return rc == 1, np.float32(t_out.value), np.float32(inten.value)

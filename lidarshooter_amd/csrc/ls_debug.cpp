@@ -4,6 +4,7 @@
 #include "ls_internal.h"
 #include "ls_closest.h"
 #include "ls_hit_attr.h"
+#include "ls_return_model.h"
 
 using namespace lsi;
 
@@ -123,6 +124,20 @@ int ls_debug_hit_attributes_on_triangle(const float o[3], const float d[3], cons
 {
     if (!o || !d || !v0 || !v1 || !v2 || !t || !out9) return LS_ERR_INVALID_ARGUMENT;
     return ls::hit_attributes_on_triangle(o, d, v0, v1, v2, t, out9) ? 1 : 0;
+}
+
+int ls_debug_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4])
+{
+    if (!ctr || !key || !out) return LS_ERR_INVALID_ARGUMENT;
+    ls::philox4x32_10(ctr, key, out);
+    return LS_OK;
+}
+
+int ls_debug_return_model(const ls_return_model *m, uint32_t ray, uint32_t frame_index, float t, float len, float cos_inc, float rho, float *t_out,
+                          float *intensity)
+{
+    if (!t_out || !intensity || ls::return_model_invalid(m)) return LS_ERR_INVALID_ARGUMENT;
+    return ls::return_model_eval(*m, ray, frame_index, t, len, cos_inc, rho, t_out, intensity) ? 1 : 0;
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 //   ls_commit.cpp    commitScene: layout, group-culling data, BVH build / refit / instanced hierarchies
 //   ls_trace.cpp     traceScene: output buffers, frames in flight, the per-frame launch sequence, stage timings
 //   ls_rays.cpp      ls_trace_rays: the query set of per-geometry hierarchies (built lazily), batches of geometries per launch;
-//                    ls_hit_attributes: the per-geomID table of its gather kernel
+//                    ls_hit_attributes: the per-geomID table of its gather kernel; ls_apply_return_model: the same table, its scratch
 //   ls_host_pool.cpp worker threads for host-side copies, point expansion
 //   ls_debug.cpp     include/lidarshooter_hip_debug.h (tests and bench.py only)
 #pragma once
@@ -295,6 +295,10 @@ struct ls_tracer {
         ls::AttrGeom *h_stage = nullptr;       // pinned staging of the upload ...
         size_t stage_cap = 0;
         hipEvent_t ev_stage = nullptr;         // ... recorded behind the last copy that reads it
+        // ls_apply_return_model: the evaluated records between its two kernels (2 x 16 bytes each) and the kept count of every
+        // 256 (every call is ordered through the handle's stream: one call uses them at a time)
+        lsi::DevBuf<uint4> park;
+        lsi::DevBuf<uint32_t> block_counts;
     } ha;
     uint64_t upload_seq = 0;
 

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct ls_return_model;   // include/lidarshooter_hip.h
+
 namespace ls {
 
 constexpr uint32_t kInvalid = 0xFFFFFFFFu;
@@ -287,6 +289,15 @@ struct alignas(16) AttrGeom {
 static_assert(sizeof(AttrGeom) == 128, "one table entry is 128 bytes");
 void launch_hit_attributes(hipStream_t s, const void *hits, const uint32_t *d_count, uint32_t n, const void *rays, uint32_t n_rays,
                            const SensorTables &tb, const AttrGeom *table, uint32_t n_table, void *out);
+// ls_apply_return_model (ls_returns.hip): the sensor return model (ls_return_model.h) on n ls_hit records (min(n, *d_count) with a
+// device count) -- k_hit_attributes' gather and validity test per record, then the model --, and the kept ones compacted in
+// input order: 32-byte points, 16-byte ls_hit records with the noisy t (either may be nullptr), the count in *n_out.  park: 2 n
+// 16-byte records of scratch; block_counts: returns_block_count(n) words.  refl: per-geomID reflectivities (nullptr, or geom >=
+// n_refl: 1.0).  Rays, table and sensor tables as launch_hit_attributes.
+size_t returns_block_count(uint32_t n);
+void launch_returns(hipStream_t s, const void *hits, const uint32_t *d_count, uint32_t n, const void *rays, uint32_t n_rays, const SensorTables &tb,
+                    const AttrGeom *table, uint32_t n_table, const ls_return_model &model, uint32_t frame_index, const float *refl,
+                    uint32_t n_refl, void *park, uint32_t *block_counts, void *points32, void *hits_out, uint32_t *n_out);
 void launch_rowcount(hipStream_t s, const uint32_t *gid, uint32_t nrays, uint32_t *row_counts, uint32_t *queue_heads = nullptr);   // queue_heads: zeroed for the next k_trace
 // Progress of a synchronous frame whose compact points go straight to pinned host memory (ls_trace_scene_begin /
 // ls_trace_scene_expand): the device publishes, with system-scope release, (1) the frame's hit count as the pack pass

@@ -2,7 +2,9 @@
 // ls_occluded_rays / ls_occluded_rays_host: whether each ray hits anything (the same query set and walk, stopping at a hit);
 // ls_closest_points / ls_closest_points_host: the nearest surface point to each caller point (the same query set, a
 // distance-ordered walk: ls_points.hip);
-// ls_hit_attributes / ls_hit_attributes_host: surface attributes of hit records (no hierarchy: a gather, ls_attr.hip; at the end).
+// ls_hit_attributes / ls_hit_attributes_host: surface attributes of hit records (no hierarchy: a gather, ls_attr.hip; at the end);
+// ls_apply_return_model / ls_apply_return_model_host: sensor returns from hit records (the same gather, a model on top of it and
+// an ordered compaction: ls_returns.hip; after them).
 //
 // The query set (ls_tracer::RayQuery) is a hierarchy set of its own -- one hierarchy per geometry, built by the kernels of
 // the instanced commit (hier_layout / hier_build, ls_commit.cpp) into buffers nothing in the frame path reads or writes,
@@ -14,6 +16,7 @@
 // What a slot was built from (vertex / index upload, mode, pose) is kept per slot: a query after a commit that changed only
 // poses builds nothing; new vertices refit that geometry (its sorted order is kept in the set's own keys), new indices rebuild it.
 #include "ls_internal.h"
+#include "ls_return_model.h"
 
 #include <algorithm>
 #include <cmath>
@@ -432,6 +435,86 @@ int attr_host_locked(ls_tracer *tr, const void *rays, uint32_t n_rays, const voi
     return LS_OK;
 }
 
+// ---- ls_apply_return_model: the gather again, the return model on top, an ordered compaction (ls_returns.hip) ---------------
+
+// argument checks, return codes and stream order of attr_locked (the model itself was checked before the handle was entered)
+int returns_locked(ls_tracer *tr, hipStream_t s, const ls_return_model *model, uint32_t frame_index, const void *d_rays, uint32_t n_rays,
+                   const void *d_hits, const uint32_t *d_count, uint32_t n, const float *d_refl, uint32_t n_refl, void *d_points32,
+                   void *d_hits_out, uint32_t *d_n_out)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (!d_n_out || (n && !d_hits)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null hit records or count output");
+    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_hits & 15u) || ((uintptr_t)d_points32 & 15u) || ((uintptr_t)d_hits_out & 15u) ||
+        ((uintptr_t)d_count & 3u) || ((uintptr_t)d_n_out & 3u) || ((uintptr_t)d_refl & 3u))
+        return fail(tr, LS_ERR_INVALID_ARGUMENT, "rays, hit records and points must be 16-byte aligned, counts and reflectivities 4-byte aligned");
+    if (n > 0xFFF00000u) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many hit records in one call");
+    if (!tr->committed || tr->n_tris == 0) return -1;   // as ls_trace_scene; nothing is written
+    int rc;
+    if ((rc = flush_pipeline(tr))) return rc;
+    ls_tracer::RayQuery &q = tr->rq;
+    ls_tracer::HitAttr &a = tr->ha;
+    if (!q.ev_ready) LS_HIP(hipEventCreateWithFlags(&q.ev_ready, hipEventDisableTiming));
+    if (!q.ev_done) LS_HIP(hipEventCreateWithFlags(&q.ev_done, hipEventDisableTiming));
+    if (s != tr->stream) {
+        LS_HIP(hipEventRecord(q.ev_ready, tr->stream));
+        LS_HIP(hipStreamWaitEvent(s, q.ev_ready, 0));
+    }
+    if (!n) {
+        LS_HIP(hipMemsetAsync(d_n_out, 0, 4, s));   // no record: no return
+    } else {
+        if ((rc = attr_table_prepare(tr, s))) return rc;
+        if ((rc = ensure(tr, a.park, 2 * (size_t)n))) return rc;
+        if ((rc = ensure(tr, a.block_counts, ls::returns_block_count(n)))) return rc;
+        ls::launch_returns(s, d_hits, d_count, n, d_rays, n_rays, tables(tr), a.table.p, (uint32_t)a.current.size(), *model, frame_index,
+                           n_refl ? d_refl : nullptr, n_refl, a.park.p, a.block_counts.p, d_points32, d_hits_out, d_n_out);
+        LS_HIP(hipGetLastError());
+    }
+    if (s != tr->stream) {
+        LS_HIP(hipEventRecord(q.ev_done, s));
+        LS_HIP(hipStreamWaitEvent(tr->stream, q.ev_done, 0));
+    }
+    return LS_OK;
+}
+
+// the host-memory variant: inputs and results staged in q.io, on the handle's stream; the count comes back first, then as many
+// records; returns when the outputs are filled
+int returns_host_locked(ls_tracer *tr, const ls_return_model *model, uint32_t frame_index, const void *rays, uint32_t n_rays, const void *hits,
+                        uint32_t n, const float *refl, uint32_t n_refl, void *points32, void *hits_out, uint32_t *n_out)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (!n_out || (n && !hits)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null hit records or count output");
+    if (n > 0xFFF00000u || (rays && n_rays > 0xFFF00000u)) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many records in one call");
+    if (!tr->committed || tr->n_tris == 0) return -1;   // (before n = 0: the same answer as the device entry point)
+    if (!n) {
+        *n_out = 0;
+        return LS_OK;
+    }
+    ls_tracer::RayQuery &q = tr->rq;
+    hipStream_t s = tr->stream;
+    int rc;
+    if ((rc = flush_pipeline(tr))) return rc;
+    const size_t hit_bytes = (size_t)n * 16, ray_bytes = rays ? (size_t)n_rays * 32 : 0, point_bytes = points32 ? (size_t)n * 32 : 0,
+                 out_bytes = hits_out ? hit_bytes : 0, refl_bytes = ((size_t)n_refl * 4 + 15) & ~(size_t)15;
+    if ((rc = ensure(tr, q.io, hit_bytes + ray_bytes + point_bytes + out_bytes + refl_bytes + 16))) return rc;
+    uint8_t *d_hits = q.io.p, *d_rays = d_hits + hit_bytes, *d_points = d_rays + ray_bytes, *d_out = d_points + point_bytes,
+            *d_refl = d_out + out_bytes, *d_n = d_refl + refl_bytes;
+    LS_HIP(hipMemcpyAsync(d_hits, hits, hit_bytes, hipMemcpyHostToDevice, s));
+    if (ray_bytes) LS_HIP(hipMemcpyAsync(d_rays, rays, ray_bytes, hipMemcpyHostToDevice, s));
+    if (n_refl) LS_HIP(hipMemcpyAsync(d_refl, refl, (size_t)n_refl * 4, hipMemcpyHostToDevice, s));
+    if ((rc = returns_locked(tr, s, model, frame_index, rays ? d_rays : nullptr, n_rays, d_hits, nullptr, n, reinterpret_cast<const float *>(d_refl),
+                             n_refl, points32 ? d_points : nullptr, hits_out ? d_out : nullptr, reinterpret_cast<uint32_t *>(d_n))))
+        return rc;
+    uint32_t kept = 0;
+    LS_HIP(hipMemcpyAsync(&kept, d_n, 4, hipMemcpyDeviceToHost, s));
+    LS_HIP(hipStreamSynchronize(s));
+    if (kept > n) return fail(tr, LS_ERR_HIP, "ls_apply_return_model: more returns than records");
+    if (kept && points32) LS_HIP(hipMemcpyAsync(points32, d_points, (size_t)kept * 32, hipMemcpyDeviceToHost, s));
+    if (kept && hits_out) LS_HIP(hipMemcpyAsync(hits_out, d_out, (size_t)kept * 16, hipMemcpyDeviceToHost, s));
+    LS_HIP(hipStreamSynchronize(s));
+    *n_out = kept;
+    return LS_OK;
+}
+
 }  // namespace
 
 void hit_attr_release(ls_tracer *tr)
@@ -439,7 +522,7 @@ void hit_attr_release(ls_tracer *tr)
     ls_tracer::HitAttr &a = tr->ha;
     if (a.ev_stage) { (void)hipEventSynchronize(a.ev_stage); (void)hipEventDestroy(a.ev_stage); }
     if (a.h_stage) (void)hipHostFree(a.h_stage);
-    release(a.table);
+    release(a.table); release(a.park); release(a.block_counts);
     a.ev_stage = nullptr;
     a.h_stage = nullptr;
     a.stage_cap = 0;
@@ -499,6 +582,33 @@ int ls_hit_attributes_host(ls_tracer *tr, const void *rays, uint32_t n_rays, con
 {
     LS_ENTER(tr);
     return attr_host_locked(tr, rays, n_rays, hits, n, out);
+}
+
+// the model and the reflectivity arguments are checked before anything touches the device (the handle's included)
+#define LS_RETURN_MODEL_CHECK(tr, model, refl, n_refl)                                                                   \
+    if (!(tr)) return LS_ERR_INVALID_ARGUMENT;                                                                           \
+    if (const char *why_ = (n_refl) && !(refl) ? "null reflectivities" : ls::return_model_invalid(model)) {              \
+        std::lock_guard<std::mutex> lock_((tr)->mu);                                                                     \
+        return lsi::fail((tr), LS_ERR_INVALID_ARGUMENT, why_);                                                           \
+    }
+
+int ls_apply_return_model(ls_tracer *tr, void *hip_stream, const ls_return_model *model, uint32_t frame_index, const void *d_rays, uint32_t n_rays,
+                          const void *d_hits, const uint32_t *d_count, uint32_t n, const float *d_reflectivity, uint32_t n_reflectivity,
+                          void *d_points32, void *d_hits_out, uint32_t *d_n_out)
+{
+    LS_RETURN_MODEL_CHECK(tr, model, d_reflectivity, n_reflectivity)
+    LS_ENTER(tr);
+    return returns_locked(tr, hip_stream ? static_cast<hipStream_t>(hip_stream) : tr->stream, model, frame_index, d_rays, n_rays, d_hits, d_count, n,
+                          d_reflectivity, n_reflectivity, d_points32, d_hits_out, d_n_out);
+}
+
+int ls_apply_return_model_host(ls_tracer *tr, const ls_return_model *model, uint32_t frame_index, const void *rays, uint32_t n_rays,
+                               const void *hits, uint32_t n, const float *reflectivity, uint32_t n_reflectivity, void *points32, void *hits_out,
+                               uint32_t *n_out)
+{
+    LS_RETURN_MODEL_CHECK(tr, model, reflectivity, n_reflectivity)
+    LS_ENTER(tr);
+    return returns_host_locked(tr, model, frame_index, rays, n_rays, hits, n, reflectivity, n_reflectivity, points32, hits_out, n_out);
 }
 
 }  // extern "C"

@@ -4,9 +4,10 @@ three ray sets -- the sensor's own rays, the 1 M incoherent rays, 1 M segments (
 random scene points, tmax = 1 - 1e-4) -- whose occluded counts must equal the hit counts; then ls_closest_points on three point sets -- the frame's own cloud with
 every point jittered by a few centimetres (cloud to mesh), 1 M points uniform in the scene's box, the same with a 0.5 m
 radius -- next to ls_trace_rays on the incoherent rays; then ls_hit_attributes on the frame's own hit records (sensor-ray mode) and
-on the hits of the 1 M incoherent rays, next to ls_trace_rays on those rays.  Prints host-side event timings;
-for kernel times (k_trace_rays, k_occluded_rays, k_closest_points, k_hit_attributes: its launches come in the order of the
-sets, 1 + reps each) run it under the profiler in a run of its own:
+on the hits of the 1 M incoherent rays, next to ls_trace_rays on those rays; then ls_apply_return_model on the same two record
+sets.  Prints host-side event timings;
+for kernel times (k_trace_rays, k_occluded_rays, k_closest_points, k_hit_attributes, k_returns_eval + k_returns_pack: their
+launches come in the order of the sets, 1 + reps each) run it under the profiler in a run of its own:
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/ray_query_bench.py
 usage: python tools/ray_query_bench.py [--reps N]
 """
@@ -135,6 +136,20 @@ def main():
         valid = rec["flags"] == 1
         print(f"hit attributes, {name}: {k} records, {int(np.count_nonzero(valid))} valid, mean cos_inc {float(rec['cos_inc'][valid].mean()):.3f}; "
               f"ls_hit_attributes {a_ms * 1e3:.1f} us per query ({a_ms / inc_ms:.3f}x ls_trace_rays on {m} incoherent rays, {inc_ms * 1e3:.1f} us)")
+    # ls_apply_return_model on the same two record sets: the gather again, the return model, the ordered compaction (k_returns_eval
+    # + k_returns_pack, 1 + reps launches of each per set) -- to be read next to k_hit_attributes on those records, above
+    model = capi.ReturnModel(flags=capi.LS_RETURN_LAMBERT, ref_range=10.0, intensity_floor=0.5, range_max=150.0, noise_sigma0=0.01,
+                             noise_sigma1=0.001, dropout=0.05, seed=1)
+    for name, d_h, k, rays, n_rays in (("frame hits, sensor rays", d_fh, fh.shape[0], 0, 0), ("incoherent rays' hits", d_ih, m, d_inc.data_ptr(), m)):
+        d_ho = torch.zeros(k * 16, dtype=torch.uint8, device="cuda:0")
+        d_no = torch.zeros(4, dtype=torch.int32, device="cuda:0")
+        q = lambda h, cnt, out_ptr, stream: tr.applyReturnModelDevice(model, h, cnt, d_no.data_ptr(), d_points32=out_ptr, d_hits_out=d_ho.data_ptr(),   # noqa: E731
+                                                                      d_rays=rays, n_rays=n_rays, stream=stream)
+        r_ms, o = timed(d_h, k, a.reps, q, 32)
+        kept = int(d_no[0].item())
+        inten = o.cpu().numpy().view(np.float32).reshape(-1, 8)[:kept, 4]
+        print(f"return model, {name}: {k} records, {kept} kept, mean intensity {float(inten.mean()) if kept else 0:.2f}; "
+              f"ls_apply_return_model {r_ms * 1e3:.1f} us per query ({r_ms / inc_ms:.3f}x ls_trace_rays on {m} incoherent rays, {inc_ms * 1e3:.1f} us)")
     tr.close()
 
 
