@@ -625,6 +625,57 @@ int ls_apply_return_model_host(ls_tracer *tr, const ls_return_model *model, uint
                                const float *reflectivity, uint32_t n_reflectivity,
                                void *points32, void *hits_out, uint32_t *n_out);
 
+/* ---- sweep frames: a frame whose SENSOR moves during the turn.  A spinning LiDAR fires azimuth column after column while its
+ * carrier drives on, and the cloud it delivers is skewed by that motion: what odometry, deskewing and mapping work against.  The
+ * scene is the committed one (no geometry pose is interpolated, no hierarchy touched); every azimuth column has a sensor pose of
+ * its own.  One call: the shard's rays through their columns' poses, their closest hits, and the hits compacted into a frame's
+ * points32 / ls_hit pair with the count, all in device memory. */
+#define LS_SWEEP_DESKEW 1u   /* points in the frame-start sensor frame instead of the instantaneous one */
+
+/*   d_col_pose: n_cols records of 12 floats in device memory, 4-byte aligned, row-major [R_h | o_h] (R[i][j] at 4 i + j, o[i] at
+ *            4 i + 3): the sensor's pose at the moment azimuth column h fires, expressed in the handle's sensor frame as the scene
+ *            was committed (the frame-start frame; identity records: an ordinary frame).  Indexed by the GLOBAL column whatever the
+ *            shard; n_cols must equal LS_INFO_AZIMUTH_COUNT.  Nothing on the host reads the table.
+ *   rays:    only the rays of the handle's shard are cast (ls_tracer_set_shard); ray indices stay global, r = v * H + h.  With d
+ *            the nominal direction -- the factor-table products the frame kernels and ls_generate_rays_aos form -- ray r has origin
+ *            o_h, direction d'_i = (R[i][0] dx + R[i][1] dy) + R[i][2] dz in float32 with no fused multiply-add, tmin 0 and tmax
+ *            1e16: ONE operation sequence (csrc/ls_sweep.h; ls_debug_sweep_ray in lidarshooter_hip_debug.h runs it on the host).
+ *            An identity record gives d' = d and o = 0 exactly.
+ *   hits:    the hit of a ray is by definition what ls_trace_rays returns for that ray record in the same state: the same test,
+ *            the same tie-break, the same treatment of degenerate rays -- a column whose pose holds a non-finite value yields
+ *            misses.
+ *   d_hits:  NULL, or room for `capacity` ls_hit records, 16-byte aligned: {ray, geom, prim, t} of the hits in ascending ray
+ *            index, as in a frame.
+ *   d_points32: NULL, or room for `capacity` 32-byte points in the ls_frame.points32 layout, 16-byte aligned, intensity 64.0, ring
+ *            v.  By default xyz = t * d with no sum, the frame's bits: what the moving sensor reports, each point in the sensor
+ *            frame of its own instant.  With LS_SWEEP_DESKEW xyz = o_h + t * d' per axis (one product, one sum): the point in
+ *            the frame-start sensor frame -- the bits ls_hit_attributes gives as px, py, pz for that ray.
+ *   d_n_points: a device word (not NULL, 4-byte aligned): the count.  Nothing is written past record *d_n_points.
+ *   capacity: at least the shard's ls_total_rays(), else LS_ERR_INVALID_ARGUMENT.
+ *   d_rays_out: NULL, or room for V * H 32-byte lidarshooter::Ray records, 16-byte aligned: the records of the shard's rays are
+ *            written at their global index, the others are left alone.  With them the frame's hit records feed ls_hit_attributes
+ *            and ls_apply_return_model as caller rays with n_rays = V * H (the return model then writes ring 0, as it does for all
+ *            caller rays).
+ * Return codes, stream order, the frame graph rule and the query hierarchies are those of ls_trace_rays (-1 with no commit or an
+ * empty scene writes nothing, the count included); LS_INFO_RAY_QUERY_BUILT reports for it; LS_OPT_ENGINE does not matter.
+ * LS_ERR_INVALID_ARGUMENT also for a NULL table or count, n_cols != H, unknown flag bits and misaligned pointers.  Frames of
+ * ls_trace_scene* are unaffected.  The sweep uses scratch of its own on the handle -- the shard's rays x 32 bytes of contiguous ray
+ * records and x 16 bytes of dense hit records, grown on demand and released with the query state --; calls on one handle use it
+ * one after the other. */
+int ls_trace_scene_sweep(ls_tracer *tr, void *hip_stream, const float *d_col_pose, uint32_t n_cols, uint32_t flags,
+                         void *d_points32, void *d_hits, uint32_t *d_n_points, uint32_t capacity, void *d_rays_out);
+/* The same with host memory (pageable) in and out, on the handle's stream; returns when the outputs are filled (*n_points
+ * records of each; of rays_out the shard's records). */
+int ls_trace_scene_sweep_host(ls_tracer *tr, const float *col_pose, uint32_t n_cols, uint32_t flags,
+                              void *points32, void *hits, uint32_t *n_points, uint32_t capacity, void *rays_out);
+
+/* Pose table of a sensor moving at a constant twist (host only, no handle, no device): tau_h = t0 + h * dt; R_h = Rodrigues'
+ * formula for the rotation ang_vel * tau_h (exactly the identity when |ang_vel| * tau_h == 0), o_h = lin_vel * tau_h -- a constant
+ * velocity in the frame-start sensor frame; evaluated in double, rounded once to float32.  col_pose: n_cols records of 12
+ * floats.  LS_ERR_INVALID_ARGUMENT for NULL pointers or non-finite inputs. */
+int ls_sweep_poses_constant_twist(const float lin_vel[3], const float ang_vel[3], double t0, double dt,
+                                  uint32_t n_cols, float *col_pose);
+
 #ifdef __cplusplus
 }
 #endif

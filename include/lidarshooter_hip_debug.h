@@ -68,6 +68,11 @@ int ls_debug_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t o
 int ls_debug_return_model(const ls_return_model *m, uint32_t ray, uint32_t frame_index, float t, float len, float cos_inc, float rho,
                           float *t_out, float *intensity);
 
+/* the ray ls_trace_scene_sweep casts for a nominal direction d under one column's pose record (12 floats, [R | o] row-major), on
+ * the host (no device, no handle): the float32 operation sequence k_sweep_rays runs (csrc/ls_sweep.h) -> the 32-byte
+ * lidarshooter::Ray record: origin o, tmin 0, d'_i = (R[i][0] dx + R[i][1] dy) + R[i][2] dz, tmax 1e16 */
+int ls_debug_sweep_ray(const float d[3], const float pose12[12], float ray8[8]);
+
 #ifdef __cplusplus
 }
 #endif

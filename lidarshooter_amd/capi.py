@@ -54,11 +54,12 @@ SYMBOLS = (
     "ls_closest_points", "ls_closest_points_host",
     "ls_hit_attributes", "ls_hit_attributes_host",
     "ls_apply_return_model", "ls_apply_return_model_host",
+    "ls_trace_scene_sweep", "ls_trace_scene_sweep_host", "ls_sweep_poses_constant_twist",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
 DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_scene_size", "ls_debug_download_scene",
                  "ls_debug_download_bvh", "ls_debug_sort_pairs", "ls_debug_expand_hits", "ls_debug_closest_on_triangle",
-                 "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model")
+                 "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model", "ls_debug_sweep_ray")
 
 
 class SensorDesc(C.Structure):
@@ -75,6 +76,7 @@ class SensorTables(C.Structure):
 
 LS_RETURN_LAMBERT = 1
 LS_RETURN_TWO_SIDED = 2
+LS_SWEEP_DESKEW = 1   # ls_trace_scene_sweep: points in the frame-start sensor frame instead of the instantaneous one
 
 
 class ReturnModel(C.Structure):
@@ -217,6 +219,10 @@ def load() -> C.CDLL:
     L.ls_apply_return_model_host.argtypes = [vp, C.POINTER(ReturnModel), u32, vp, u32, vp, u32, vp, u32, vp, vp, u32p]
     L.ls_debug_philox4x32.argtypes = [u32p, u32p, u32p]
     L.ls_debug_return_model.argtypes = [C.POINTER(ReturnModel), u32, u32, C.c_float, C.c_float, C.c_float, C.c_float, f32p, f32p]
+    L.ls_trace_scene_sweep.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, u32, vp]
+    L.ls_trace_scene_sweep_host.argtypes = [vp, vp, u32, u32, vp, vp, u32p, u32, vp]
+    L.ls_sweep_poses_constant_twist.argtypes = [f32p, f32p, C.c_double, C.c_double, u32, f32p]
+    L.ls_debug_sweep_ray.argtypes = [f32p, f32p, f32p]
     L.ls_geometry_type.argtypes = [vp, C.c_char_p]
     L.ls_debug_dense_hits.argtypes = [vp, f32p, u32p]
     L.ls_debug_trace_bruteforce.argtypes = [vp, f32p, u32p]
@@ -643,6 +649,40 @@ class Tracer:
                                           d_reflectivity or None, n_reflectivity, d_points32 or None, d_hits_out or None, d_n_out or None)
         return -1 if rc == -1 else int(self._check(rc, "ls_apply_return_model"))
 
+    def traceSweep(self, col_pose, flags: int = 0, points: bool = True, hits: bool = True, rays_out=None):
+        """A frame whose sensor moves during the turn (ls_trace_scene_sweep_host): `col_pose` float32 (H, 12) -- [R | o] row-major,
+        the sensor's pose when azimuth column h fires, in the frame-start sensor frame -- for the FULL raster whatever the shard.
+        `points` / `hits` False: that output is not asked for (None comes back); `rays_out` None, or a RAY_DTYPE / float32 (V * H, 8)
+        array of the full raster whose shard records are overwritten in place.  -> (rc, k, points uint8[k, 32] or None, hits
+        HIT_DTYPE[k] or None); rc = -1 (no commit, empty scene): no record."""
+        pose = np.ascontiguousarray(col_pose, np.float32)
+        if pose.ndim != 2 or pose.shape[1] != 12:
+            raise ValueError("col_pose: float32 (H, 12)")
+        if rays_out is not None and not (isinstance(rays_out, np.ndarray) and rays_out.flags.c_contiguous and rays_out.flags.writeable and
+                                         rays_out.nbytes == 32 * int(self.L.ls_total_channels(self.h)) * self.info(LS_INFO_AZIMUTH_COUNT)):
+            raise ValueError("rays_out: a writable contiguous array of V * H 32-byte records")
+        n = self.getTotalRays()
+        pts = np.zeros((n, 32), np.uint8) if points else None
+        out = np.zeros(n, HIT_DTYPE) if hits else None
+        k = C.c_uint32(0)
+        rc = self.L.ls_trace_scene_sweep_host(self.h, pose.ctypes.data if pose.size else None, pose.shape[0], flags,
+                                              pts.ctypes.data if points else None, out.ctypes.data if hits else None, C.byref(k), n,
+                                              None if rays_out is None else rays_out.ctypes.data)
+        if rc == -1:
+            return -1, 0, (pts[:0] if points else None), (out[:0] if hits else None)
+        self._check(rc, "ls_trace_scene_sweep_host")
+        return int(rc), int(k.value), (pts[:k.value].copy() if points else None), (out[:k.value].copy() if hits else None)
+
+    def traceSweepDevice(self, d_col_pose: int, n_cols: int, d_n_points: int, capacity: int, d_points32: int = 0, d_hits: int = 0,
+                         d_rays_out: int = 0, flags: int = 0, stream=None) -> int:
+        """ls_trace_scene_sweep on device pointers (n_cols 48-byte pose records in; up to `capacity` 32-byte points and ls_hit
+        records out, either may be 0; the count in the device word d_n_points; d_rays_out: 0, or V * H 32-byte ray records);
+        enqueued on `stream` (a hipStream_t as an int, None: the handle's), no wait.  -> 0, or -1 on an empty / uncommitted scene
+        (nothing written)."""
+        rc = self.L.ls_trace_scene_sweep(self.h, stream, d_col_pose or None, n_cols, flags, d_points32 or None, d_hits or None, d_n_points or None,
+                                         capacity, d_rays_out or None)
+        return -1 if rc == -1 else int(self._check(rc, "ls_trace_scene_sweep"))
+
     # ---- test hooks
     def generateRaysAos(self, d_rays: int | None, d_hits: int | None):
         """LidarDevice::allRaysGPU's two buffers (Ray 32 B, Hit 24 B per ray) in device memory of the caller."""
@@ -736,3 +776,27 @@ def return_model(model: ReturnModel, ray, frame_index, t, length, cos_inc, rho):
     if rc < 0:
         raise LidarShooterHipError(f"ls_debug_return_model: status {rc}")
     return rc == 1, np.float32(t_out.value), np.float32(inten.value)
+
+
+def sweep_poses_constant_twist(lin_vel, ang_vel, t0: float, dt: float, n_cols: int):
+    """ls_sweep_poses_constant_twist: the pose table of a sensor moving at a constant twist -> float32 (n_cols, 12), [R | o]
+    row-major, tau_h = t0 + h dt"""
+    L = load()
+    lin, ang = (np.ascontiguousarray(x, np.float32).reshape(3) for x in (lin_vel, ang_vel))
+    out = np.zeros((int(n_cols), 12), np.float32)
+    rc = L.ls_sweep_poses_constant_twist(_f32p(lin), _f32p(ang), float(t0), float(dt), int(n_cols), _f32p(out))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_sweep_poses_constant_twist: status {rc}")
+    return out
+
+
+def sweep_ray(d, pose12):
+    """ls_debug_sweep_ray: the ray ls_trace_scene_sweep casts for the nominal direction d under one pose record, on the host ->
+    float32[8] (origin, tmin, direction, tmax)"""
+    L = load()
+    dd, p = np.ascontiguousarray(d, np.float32).reshape(3), np.ascontiguousarray(pose12, np.float32).reshape(12)
+    out = np.zeros(8, np.float32)
+    rc = L.ls_debug_sweep_ray(_f32p(dd), _f32p(p), _f32p(out))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_debug_sweep_ray: status {rc}")
+    return out

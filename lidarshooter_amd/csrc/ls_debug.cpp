@@ -5,6 +5,7 @@
 #include "ls_closest.h"
 #include "ls_hit_attr.h"
 #include "ls_return_model.h"
+#include "ls_sweep.h"
 
 using namespace lsi;
 
@@ -138,6 +139,13 @@ int ls_debug_return_model(const ls_return_model *m, uint32_t ray, uint32_t frame
 {
     if (!t_out || !intensity || ls::return_model_invalid(m)) return LS_ERR_INVALID_ARGUMENT;
     return ls::return_model_eval(*m, ray, frame_index, t, len, cos_inc, rho, t_out, intensity) ? 1 : 0;
+}
+
+int ls_debug_sweep_ray(const float d[3], const float pose12[12], float ray8[8])
+{
+    if (!d || !pose12 || !ray8) return LS_ERR_INVALID_ARGUMENT;
+    ls::sweep_ray(pose12, d[0], d[1], d[2], ray8);
+    return LS_OK;
 }
 
 }  // extern "C"

@@ -6,7 +6,8 @@
 //   ls_commit.cpp    commitScene: layout, group-culling data, BVH build / refit / instanced hierarchies
 //   ls_trace.cpp     traceScene: output buffers, frames in flight, the per-frame launch sequence, stage timings
 //   ls_rays.cpp      ls_trace_rays: the query set of per-geometry hierarchies (built lazily), batches of geometries per launch;
-//                    ls_hit_attributes: the per-geomID table of its gather kernel; ls_apply_return_model: the same table, its scratch
+//                    ls_hit_attributes: the per-geomID table of its gather kernel; ls_apply_return_model: the same table, its scratch;
+//                    ls_trace_scene_sweep: its scratch around the same walk (ls_sweep.hip, ls_sweep.h)
 //   ls_host_pool.cpp worker threads for host-side copies, point expansion
 //   ls_debug.cpp     include/lidarshooter_hip_debug.h (tests and bench.py only)
 #pragma once
@@ -280,6 +281,10 @@ struct ls_tracer {
         uint32_t *d_counters = nullptr;        // ray counter of each launch (kMaxGeoms / kGeomsPerLaunch words)
         lsi::DevBuf<uint32_t> spill;
         lsi::DevBuf<uint8_t> io;               // ls_trace_rays_host: rays, then hit records
+        // ls_trace_scene_sweep: the shard's ray records (32 bytes each, ascending ray index), the walk's dense hit records (16
+        // bytes each) and the hit count of every 256 of them (every call is ordered through the handle's stream: one at a time)
+        lsi::DevBuf<uint8_t> sweep_rays, sweep_hits;
+        lsi::DevBuf<uint32_t> sweep_counts;
         std::vector<RayQuerySlot> built;       // per layout entry
         std::vector<int> layout_ids;           // geometry ids of the layout the slots were made for ...
         std::vector<uint32_t> layout_firsts;   // ... and their first vertex, first triangle in it

@@ -298,6 +298,15 @@ size_t returns_block_count(uint32_t n);
 void launch_returns(hipStream_t s, const void *hits, const uint32_t *d_count, uint32_t n, const void *rays, uint32_t n_rays, const SensorTables &tb,
                     const AttrGeom *table, uint32_t n_table, const ls_return_model &model, uint32_t frame_index, const float *refl,
                     uint32_t n_refl, void *park, uint32_t *block_counts, void *points32, void *hits_out, uint32_t *n_out);
+// ls_trace_scene_sweep (ls_sweep.hip): the shard's rays through the per-column pose table (H records of 12 floats, [R | o] row-major,
+// indexed by the global column) as 32-byte records -- shard-local order in `rays` (what launch_trace_rays reads), and at their
+// global index in rays_out (nullable); then, over the walk's dense ls_hit records of those rays, the ordered pack: 32-byte
+// points (t * d from the factor tables, or o + t * d' with deskew), ls_hit records with the global ray index (either may be
+// nullptr), the count in *n_points.  block_counts: sweep_block_count(rays of the shard) words.
+size_t sweep_block_count(uint32_t nq);
+void launch_sweep_rays(hipStream_t s, const SensorTables &tb, const float *pose, void *rays, void *rays_out);
+void launch_sweep_pack(hipStream_t s, const SensorTables &tb, const void *dense, uint32_t *block_counts, const float *pose, bool deskew,
+                       void *points32, void *hits, uint32_t *n_points);
 void launch_rowcount(hipStream_t s, const uint32_t *gid, uint32_t nrays, uint32_t *row_counts, uint32_t *queue_heads = nullptr);   // queue_heads: zeroed for the next k_trace
 // Progress of a synchronous frame whose compact points go straight to pinned host memory (ls_trace_scene_begin /
 // ls_trace_scene_expand): the device publishes, with system-scope release, (1) the frame's hit count as the pack pass

@@ -5,6 +5,8 @@
 // ls_hit_attributes / ls_hit_attributes_host: surface attributes of hit records (no hierarchy: a gather, ls_attr.hip; at the end);
 // ls_apply_return_model / ls_apply_return_model_host: sensor returns from hit records (the same gather, a model on top of it and
 // an ordered compaction: ls_returns.hip; after them).
+// ls_trace_scene_sweep / ls_trace_scene_sweep_host: a frame whose sensor moves during the turn -- the shard's rays through per-column
+// poses, the closest-hit walk over them, an ordered pack (ls_sweep.hip; at the end); ls_sweep_poses_constant_twist: a pose table.
 //
 // The query set (ls_tracer::RayQuery) is a hierarchy set of its own -- one hierarchy per geometry, built by the kernels of
 // the instanced commit (hier_layout / hier_build, ls_commit.cpp) into buffers nothing in the frame path reads or writes,
@@ -223,6 +225,7 @@ void ray_query_release(ls_tracer *tr)
     if (q.ev_done) (void)hipEventSynchronize(q.ev_done);
     release(q.records); release(q.nodes); release(q.wide_nodes); release(q.range_boxes); release(q.verts);
     release(q.keys_a); release(q.keys_b); release(q.vals_b); release(q.sort_temp); release(q.spill); release(q.io);
+    release(q.sweep_rays); release(q.sweep_hits); release(q.sweep_counts);
     if (q.d_maxabs) (void)hipFree(q.d_maxabs);
     if (q.d_counters) (void)hipFree(q.d_counters);
     if (q.ev_ready) (void)hipEventDestroy(q.ev_ready);
@@ -257,18 +260,16 @@ const RayQueryKind kClosest = {launch_closest_hits, 32, 16, 16, false, "rays and
 const RayQueryKind kOccluded = {launch_any_hits, 32, 1, 1, false, "rays must be 16-byte aligned"};
 const RayQueryKind kNearest = {ls::launch_closest_points, 16, 32, 16, true, "points and result records must be 16-byte aligned"};
 
-int rays_locked(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out, const RayQueryKind &kind)
+// What every query on the hierarchies does around and in its walk (ls_trace_rays and its siblings; ls_trace_scene_sweep, which
+// puts a pass of its own on either side of the walk):
+//   query_enter  after everything already issued on the handle -- its frames in flight, its mesh copies -- on stream s;
+//   query_walk   the query set brought up to date, the counters, one launch per batch of kGeomsPerLaunch geometries;
+//   query_leave  what the handle issues next (mesh copies, commits, the next query) comes after this query; frames of the
+//                three-stream rotation that need none of that do not wait for it.
+int query_enter(ls_tracer *tr, hipStream_t s)
 {
-    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
-    if (n && (!d_rays || !d_out)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null rays or output");
-    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & (kind.out_align - 1u))) return fail(tr, LS_ERR_INVALID_ARGUMENT, kind.misaligned);
-    if (n > 0xFFF00000u) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
     ls_tracer::RayQuery &q = tr->rq;
-    q.last_built = 0;
-    if (!tr->committed || tr->n_tris == 0) return -1;   // as ls_trace_scene; nothing is written
-    if (!n) return LS_OK;
     int rc;
-    // after everything already issued on the handle: its frames in flight, its mesh copies
     if ((rc = flush_pipeline(tr))) return rc;
     if (!q.ev_ready) LS_HIP(hipEventCreateWithFlags(&q.ev_ready, hipEventDisableTiming));
     if (!q.ev_done) LS_HIP(hipEventCreateWithFlags(&q.ev_done, hipEventDisableTiming));
@@ -276,6 +277,13 @@ int rays_locked(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, vo
         LS_HIP(hipEventRecord(q.ev_ready, tr->stream));
         LS_HIP(hipStreamWaitEvent(s, q.ev_ready, 0));
     }
+    return LS_OK;
+}
+
+int query_walk(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out, const RayQueryKind &kind)
+{
+    ls_tracer::RayQuery &q = tr->rq;
+    int rc;
     std::vector<Geometry *> order;
     std::vector<bool> sensor_frame;
     if ((rc = ray_query_prepare(tr, s, order, sensor_frame))) return rc;
@@ -300,13 +308,32 @@ int rays_locked(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, vo
         kind.launch(s, tr->trace_blocks, d_rays, n, batch, pm, q.wide_nodes.p, q.records.p, q.leaf, d_out, q.d_counters + b, q.spill.p);
     }
     LS_HIP(hipGetLastError());
-    // what the handle issues next (mesh copies, commits, the next query) comes after this query; frames of the three-stream
-    // rotation that need none of that do not wait for it
+    return LS_OK;
+}
+
+int query_leave(ls_tracer *tr, hipStream_t s)
+{
+    ls_tracer::RayQuery &q = tr->rq;
     if (s != tr->stream) {
         LS_HIP(hipEventRecord(q.ev_done, s));
         LS_HIP(hipStreamWaitEvent(tr->stream, q.ev_done, 0));
     }
     return LS_OK;
+}
+
+int rays_locked(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out, const RayQueryKind &kind)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (n && (!d_rays || !d_out)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null rays or output");
+    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & (kind.out_align - 1u))) return fail(tr, LS_ERR_INVALID_ARGUMENT, kind.misaligned);
+    if (n > 0xFFF00000u) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
+    tr->rq.last_built = 0;
+    if (!tr->committed || tr->n_tris == 0) return -1;   // as ls_trace_scene; nothing is written
+    if (!n) return LS_OK;
+    int rc;
+    if ((rc = query_enter(tr, s))) return rc;
+    if ((rc = query_walk(tr, s, d_rays, n, d_out, kind))) return rc;
+    return query_leave(tr, s);
 }
 
 // the host-memory variant: rays and results staged in q.io, on the handle's stream; returns when out is filled
@@ -515,6 +542,79 @@ int returns_host_locked(ls_tracer *tr, const ls_return_model *model, uint32_t fr
     return LS_OK;
 }
 
+// ---- ls_trace_scene_sweep: a frame whose sensor moves during the turn (ls_sweep.hip around the ray queries' walk) ----------
+
+// argument checks first (none of them needs a commit), then the return codes, stream order and hierarchies of rays_locked
+int sweep_locked(ls_tracer *tr, hipStream_t s, const float *d_col_pose, uint32_t n_cols, uint32_t flags, void *d_points32, void *d_hits,
+                 uint32_t *d_n_points, uint32_t capacity, void *d_rays_out)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (!d_col_pose || !d_n_points) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null pose table or count output");
+    if (n_cols != tr->H) return fail(tr, LS_ERR_INVALID_ARGUMENT, "one pose per azimuth column of the full raster (LS_INFO_AZIMUTH_COUNT)");
+    if (flags & ~(uint32_t)LS_SWEEP_DESKEW) return fail(tr, LS_ERR_INVALID_ARGUMENT, "unknown sweep flags");
+    if (((uintptr_t)d_col_pose & 3u) || ((uintptr_t)d_n_points & 3u) || ((uintptr_t)d_points32 & 15u) || ((uintptr_t)d_hits & 15u) ||
+        ((uintptr_t)d_rays_out & 15u))
+        return fail(tr, LS_ERR_INVALID_ARGUMENT, "points, hit records and rays must be 16-byte aligned, the poses and the count 4-byte aligned");
+    const uint32_t nq = shard_rays(tr);
+    if (capacity < nq) return fail(tr, LS_ERR_INVALID_ARGUMENT, "capacity below the shard's ray count");
+    if (nq > 0xFFF00000u) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
+    ls_tracer::RayQuery &q = tr->rq;
+    q.last_built = 0;
+    if (!tr->committed || tr->n_tris == 0) return -1;   // as ls_trace_scene; nothing is written, the count included
+    int rc;
+    if ((rc = query_enter(tr, s))) return rc;
+    if ((rc = ensure(tr, q.sweep_rays, (size_t)nq * 32))) return rc;
+    if ((rc = ensure(tr, q.sweep_hits, (size_t)nq * 16))) return rc;
+    if ((rc = ensure(tr, q.sweep_counts, ls::sweep_block_count(nq)))) return rc;
+    const ls::SensorTables tb = tables(tr);
+    ls::launch_sweep_rays(s, tb, d_col_pose, q.sweep_rays.p, d_rays_out);
+    if ((rc = query_walk(tr, s, q.sweep_rays.p, nq, q.sweep_hits.p, kClosest))) return rc;
+    ls::launch_sweep_pack(s, tb, q.sweep_hits.p, q.sweep_counts.p, d_col_pose, (flags & LS_SWEEP_DESKEW) != 0, d_points32, d_hits, d_n_points);
+    LS_HIP(hipGetLastError());
+    return query_leave(tr, s);
+}
+
+// the host-memory variant: the poses, the outputs and the optional ray records staged in q.io, on the handle's stream; the count
+// comes back first, then as many records; of rays_out only the shard's columns are written
+int sweep_host_locked(ls_tracer *tr, const float *col_pose, uint32_t n_cols, uint32_t flags, void *points32, void *hits, uint32_t *n_points,
+                      uint32_t capacity, void *rays_out)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (!col_pose || !n_points) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null pose table or count output");
+    if (n_cols != tr->H) return fail(tr, LS_ERR_INVALID_ARGUMENT, "one pose per azimuth column of the full raster (LS_INFO_AZIMUTH_COUNT)");
+    if (flags & ~(uint32_t)LS_SWEEP_DESKEW) return fail(tr, LS_ERR_INVALID_ARGUMENT, "unknown sweep flags");
+    const uint32_t nq = shard_rays(tr);
+    if (capacity < nq) return fail(tr, LS_ERR_INVALID_ARGUMENT, "capacity below the shard's ray count");
+    if (nq > 0xFFF00000u) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
+    tr->rq.last_built = 0;
+    if (!tr->committed || tr->n_tris == 0) return -1;
+    ls_tracer::RayQuery &q = tr->rq;
+    hipStream_t s = tr->stream;
+    int rc;
+    if ((rc = flush_pipeline(tr))) return rc;
+    const size_t point_bytes = points32 ? (size_t)nq * 32 : 0, hit_bytes = hits ? (size_t)nq * 16 : 0, row_bytes = (size_t)tr->H * 32,
+                 ray_bytes = rays_out ? (size_t)tr->V * row_bytes : 0, pose_bytes = (size_t)n_cols * 48;
+    if ((rc = ensure(tr, q.io, point_bytes + hit_bytes + ray_bytes + pose_bytes + 16))) return rc;
+    uint8_t *d_points = q.io.p, *d_hits = d_points + point_bytes, *d_rays = d_hits + hit_bytes, *d_pose = d_rays + ray_bytes,
+            *d_n = d_pose + pose_bytes;
+    LS_HIP(hipMemcpyAsync(d_pose, col_pose, pose_bytes, hipMemcpyHostToDevice, s));
+    if ((rc = sweep_locked(tr, s, reinterpret_cast<const float *>(d_pose), n_cols, flags, points32 ? d_points : nullptr, hits ? d_hits : nullptr,
+                           reinterpret_cast<uint32_t *>(d_n), nq, rays_out ? d_rays : nullptr)))
+        return rc;
+    uint32_t count = 0;
+    LS_HIP(hipMemcpyAsync(&count, d_n, 4, hipMemcpyDeviceToHost, s));
+    LS_HIP(hipStreamSynchronize(s));
+    if (count > nq) return fail(tr, LS_ERR_HIP, "ls_trace_scene_sweep: more points than rays");
+    if (count && points32) LS_HIP(hipMemcpyAsync(points32, d_points, (size_t)count * 32, hipMemcpyDeviceToHost, s));
+    if (count && hits) LS_HIP(hipMemcpyAsync(hits, d_hits, (size_t)count * 16, hipMemcpyDeviceToHost, s));
+    if (rays_out)   // V rows of the shard's naz records, at their place in the rows of H
+        LS_HIP(hipMemcpy2DAsync(static_cast<uint8_t *>(rays_out) + (size_t)tr->az0 * 32, row_bytes, d_rays + (size_t)tr->az0 * 32, row_bytes,
+                                (size_t)tr->naz * 32, tr->V, hipMemcpyDeviceToHost, s));
+    LS_HIP(hipStreamSynchronize(s));
+    *n_points = count;
+    return LS_OK;
+}
+
 }  // namespace
 
 void hit_attr_release(ls_tracer *tr)
@@ -609,6 +709,52 @@ int ls_apply_return_model_host(ls_tracer *tr, const ls_return_model *model, uint
     LS_RETURN_MODEL_CHECK(tr, model, reflectivity, n_reflectivity)
     LS_ENTER(tr);
     return returns_host_locked(tr, model, frame_index, rays, n_rays, hits, n, reflectivity, n_reflectivity, points32, hits_out, n_out);
+}
+
+int ls_trace_scene_sweep(ls_tracer *tr, void *hip_stream, const float *d_col_pose, uint32_t n_cols, uint32_t flags, void *d_points32, void *d_hits,
+                         uint32_t *d_n_points, uint32_t capacity, void *d_rays_out)
+{
+    LS_ENTER(tr);
+    return sweep_locked(tr, hip_stream ? static_cast<hipStream_t>(hip_stream) : tr->stream, d_col_pose, n_cols, flags, d_points32, d_hits, d_n_points,
+                        capacity, d_rays_out);
+}
+
+int ls_trace_scene_sweep_host(ls_tracer *tr, const float *col_pose, uint32_t n_cols, uint32_t flags, void *points32, void *hits, uint32_t *n_points,
+                              uint32_t capacity, void *rays_out)
+{
+    LS_ENTER(tr);
+    return sweep_host_locked(tr, col_pose, n_cols, flags, points32, hits, n_points, capacity, rays_out);
+}
+
+// host only: tau_h = t0 + h dt; R_h = Rodrigues' rotation by ang_vel * tau_h, o_h = lin_vel * tau_h; double throughout, one rounding
+int ls_sweep_poses_constant_twist(const float lin_vel[3], const float ang_vel[3], double t0, double dt, uint32_t n_cols, float *col_pose)
+{
+    if (!lin_vel || !ang_vel || (n_cols && !col_pose)) return LS_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(t0) || !std::isfinite(dt)) return LS_ERR_INVALID_ARGUMENT;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(lin_vel[k]) || !std::isfinite(ang_vel[k])) return LS_ERR_INVALID_ARGUMENT;
+    const double w[3] = {ang_vel[0], ang_vel[1], ang_vel[2]};
+    const double wn = std::sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+    for (uint32_t h = 0; h < n_cols; ++h) {
+        const double tau = t0 + (double)h * dt, angle = wn * tau;
+        double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        if (angle != 0.0) {
+            const double k[3] = {w[0] / wn, w[1] / wn, w[2] / wn}, sn = std::sin(angle), c1 = 1.0 - std::cos(angle);
+            // R = I + sin(a) K + (1 - cos(a)) K^2, K the cross-product matrix of the unit axis k
+            const double K[9] = {0, -k[2], k[1], k[2], 0, -k[0], -k[1], k[0], 0};
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    const double K2 = k[i] * k[j] - (i == j ? 1.0 : 0.0);   // (k k^T - I: |k| = 1)
+                    R[3 * i + j] = (i == j ? 1.0 : 0.0) + sn * K[3 * i + j] + c1 * K2;
+                }
+        }
+        float *p = col_pose + 12 * (size_t)h;
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) p[4 * i + j] = (float)R[3 * i + j];
+            p[4 * i + 3] = (float)((double)lin_vel[i] * tau);
+        }
+    }
+    return LS_OK;
 }
 
 }  // extern "C"
