@@ -676,6 +676,76 @@ int ls_trace_scene_sweep_host(ls_tracer *tr, const float *col_pose, uint32_t n_c
 int ls_sweep_poses_constant_twist(const float lin_vel[3], const float ang_vel[3], double t0, double dt,
                                   uint32_t n_cols, float *col_pose);
 
+/* ---- beam frames: a frame whose rays are diverging BEAMS with multi-echo returns.  Every other path casts one infinitely thin ray
+ * per raster cell; a real LiDAR beam diverges by 1 - 3 mrad: at a silhouette its footprint covers a near and a far surface, on
+ * grazing ground it smears over metres of range, and the sensor reports echoes -- the first, the last or the strongest return,
+ * often two per beam.  One call: S sub-rays per ray of the shard, their closest hits, the echoes of every beam, and the selected
+ * returns compacted into a frame's points32 / ls_hit pair with an echo word per record and the count, all in device memory. */
+#define LS_BEAM_FIRST     1u
+#define LS_BEAM_LAST      2u
+#define LS_BEAM_STRONGEST 4u
+typedef struct ls_beam_model {
+    const float *pattern;     /* HOST memory: n_samples records of 3 floats (a, b, k) */
+    uint32_t n_samples;       /* S, 1..64 */
+    uint32_t returns;         /* LS_BEAM_* mask, at least one bit; K = popcount */
+    uint32_t min_count;       /* an echo is detectable with >= min_count sub-hits; 1..S */
+    float echo_separation;    /* metres, >= 0; +inf: one echo per beam */
+    uint32_t reserved[4];     /* must be 0 */
+} ls_beam_model;
+
+/*   pattern: the library reads and validates it on the host during the call, and hands it to the kernels by value (768 bytes of
+ *            kernel arguments at most): no copy from caller memory outlives the call, and the call does not wait for the device.
+ *            Sample s = (a_s, b_s, k_s): tangent offsets along the ring and towards higher elevation (radians for small ones), and
+ *            the factor that turns the distance along the sub-ray into the range the sensor reports along its axis.
+ *   sub-rays: for ray (v, h) of the shard, with the factor-table entries st = sin_theta[v], ct = cos_theta[v], (cphi, sphi) of
+ *            column h: the nominal direction d = (st cphi, st sphi, ct), the tangents u = (-sphi, cphi, 0) and w = (-(ct cphi),
+ *            -(ct sphi), st).  Sample s casts origin 0, tmin 0, tmax 1e16, direction d_s,i = (d_i + a_s u_i) + b_s w_i in float32
+ *            with no fused multiply-add: ONE operation sequence (csrc/ls_beam.h; ls_debug_beam_ray in lidarshooter_hip_debug.h
+ *            runs it on the host).  The sample (0, 0, 1) gives d exactly; a component -0 becomes +0.  The sub-hit of a sub-ray
+ *            is by definition what ls_trace_rays returns for that record in the same state.  Sub-ray index: q * S + s, q the
+ *            shard-local ray index.
+ *   echoes:  r_s = t_s * k_s, one float32 product.  With the sub-hits of a beam ordered by (r ascending, s ascending), an echo
+ *            starts at the first of them and at every sub-hit j with r_j - r_{j-1} > echo_separation (a float32 difference).  An
+ *            echo carries the range, sample, geom and prim of its nearest member (leading edge: no sums) and its member count
+ *            n_e; it is detectable when n_e >= min_count.  Among the detectable echoes FIRST is the nearest, LAST the farthest,
+ *            STRONGEST the one with the largest n_e (the nearer of equals).  The distinct selected echoes are the beam's
+ *            returns, in ascending range: 0..K per beam.
+ *   outputs: device memory, in ascending global ray index and, within a beam, ascending range; any of the three arrays may be
+ *            NULL.
+ *     d_points32: room for `capacity` 32-byte points in the ls_frame.points32 layout, 16-byte aligned: xyz = r_e * d per axis
+ *            with the nominal d and no sum (the range the sensor reports along its axis), intensity = (64.0f * (float)n_e) /
+ *            (float)S, ring = v.
+ *     d_hits: room for `capacity` ls_hit records, 16-byte aligned: {ray = v * H + h, geom, prim, t = r_e}.
+ *     d_echo: room for `capacity` words, 4-byte aligned: bits 0-2 which of FIRST / LAST / STRONGEST the record is, bits 8-14
+ *            n_e, bits 16-21 the nearest member's sample, every other bit 0.
+ *     d_n_points: a device word (not NULL, 4-byte aligned): the count.  Nothing is written past record *d_n_points.
+ *   capacity: at least K times the shard's ls_total_rays().
+ * With S = 1, the pattern (0, 0, 1), FIRST and min_count 1 the call returns ls_trace_scene's points, records and count byte for
+ * byte.  LS_ERR_INVALID_ARGUMENT before any device call: a NULL handle, model, pattern or count; S outside 1..64; no return bit
+ * or unknown ones; min_count outside 1..S; a NaN or negative separation; a non-finite pattern entry or k <= 0; non-zero reserved
+ * words; a capacity too small; misaligned pointers.  LS_ERR_OUT_OF_RANGE: the shard's rays times S above 2^27.  The other
+ * return codes, stream order, the frame graph rule, the shard handling and the query hierarchies are those of
+ * ls_trace_scene_sweep (-1 with no commit or an empty scene writes nothing, the count included); LS_INFO_RAY_QUERY_BUILT reports
+ * for it.  Frames of ls_trace_scene* are unaffected.  The call uses scratch of its own on the handle, grown on demand and released
+ * with the query state: the shard's rays x S x (32 bytes of ray record + 16 of dense hit record), 48 + 4 bytes per ray for its
+ * returns, one word per 256 rays; calls on one handle use it one after the other.
+ * Not offered: per-sample weights (every sub-hit counts once); beams under the per-column poses of ls_trace_scene_sweep; a call of
+ * the ITracer adapter.  ls_apply_return_model refuses these records (ls_hit_attributes calls them invalid): their t is the
+ * reported range r_e, not the distance along the sub-ray that the exact test needs. */
+int ls_trace_scene_beams(ls_tracer *tr, void *hip_stream, const ls_beam_model *model,
+                         void *d_points32, void *d_hits, uint32_t *d_echo, uint32_t *d_n_points, uint32_t capacity);
+/* The same with host memory (pageable) out, on the handle's stream; returns when the outputs are filled (*n_points records of
+ * each). */
+int ls_trace_scene_beams_host(ls_tracer *tr, const ls_beam_model *model,
+                              void *points32, void *hits, uint32_t *echo, uint32_t *n_points, uint32_t capacity);
+
+/* A pattern of concentric rings (host only, no handle, no device): S = 1 + n_rings * per_ring samples, at most 64.  Sample 0 is
+ * (0, 0, 1); ring j = 1..n_rings, i = 0..per_ring - 1: rho = j / n_rings, phi = 2 pi (i + 0.5 (j - 1)) / per_ring, a =
+ * half_angle_az * rho * cos(phi), b = half_angle_el * rho * sin(phi), evaluated in double and rounded once; k = sqrt(1 + (a^2 +
+ * b^2)), evaluated in double from the ROUNDED a and b, then rounded once.  pattern: S records of 3 floats.
+ * LS_ERR_INVALID_ARGUMENT for a NULL pointer, more than 64 samples or non-finite angles. */
+int ls_beam_pattern_rings(float half_angle_az, float half_angle_el, uint32_t n_rings, uint32_t per_ring, float *pattern);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,20 @@ int ls_debug_return_model(const ls_return_model *m, uint32_t ray, uint32_t frame
  * lidarshooter::Ray record: origin o, tmin 0, d'_i = (R[i][0] dx + R[i][1] dy) + R[i][2] dz, tmax 1e16 */
 int ls_debug_sweep_ray(const float d[3], const float pose12[12], float ray8[8]);
 
+/* the sub-ray ls_trace_scene_beams casts for sample abk = (a, b, k) of the ray with the factor-table entries sin_theta, cos_theta,
+ * (cos_phi, sin_phi), on the host (no device, no handle): the float32 operation sequence k_beam_rays runs (csrc/ls_beam.h) -> the
+ * 32-byte lidarshooter::Ray record: origin 0, tmin 0, d_i = (d_i + a u_i) + b w_i, tmax 1e16 */
+int ls_debug_beam_ray(float sin_theta, float cos_theta, float cos_phi, float sin_phi, const float abk[3], float ray8[8]);
+/* the echoes of one beam on the host (no device, no handle; the model's pattern is not read): r and hit hold the reported range
+ * r_s = t_s * k_s and a hit flag (0: a miss) of each of the model's n_samples sub-rays; the keys, the echo starts and the selection
+ * k_beam_reduce runs (csrc/ls_beam.h) -> *n_out returns, 0..3, in ascending range, two words each in out: the bits of r_e and the
+ * echo word of ls_trace_scene_beams' d_echo.  LS_ERR_INVALID_ARGUMENT for NULL pointers, n_samples outside 1..64, no or unknown
+ * return bits, min_count outside 1..n_samples, a NaN or negative separation. */
+int ls_debug_beam_echoes(const ls_beam_model *model, const float *r, const uint8_t *hit, uint32_t *out /* up to 3 x {r bits, echo word} */, uint32_t *n_out);
+/* the status ls_trace_scene_beams would return for this model on a handle whose shard has shard_rays rays, with this capacity and
+ * otherwise valid arguments (no device, no handle): LS_OK, LS_ERR_INVALID_ARGUMENT or LS_ERR_OUT_OF_RANGE */
+int ls_debug_beam_model_check(const ls_beam_model *model, uint32_t shard_rays, uint32_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,11 +55,13 @@ SYMBOLS = (
     "ls_hit_attributes", "ls_hit_attributes_host",
     "ls_apply_return_model", "ls_apply_return_model_host",
     "ls_trace_scene_sweep", "ls_trace_scene_sweep_host", "ls_sweep_poses_constant_twist",
+    "ls_trace_scene_beams", "ls_trace_scene_beams_host", "ls_beam_pattern_rings",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
 DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_scene_size", "ls_debug_download_scene",
                  "ls_debug_download_bvh", "ls_debug_sort_pairs", "ls_debug_expand_hits", "ls_debug_closest_on_triangle",
-                 "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model", "ls_debug_sweep_ray")
+                 "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model", "ls_debug_sweep_ray",
+                 "ls_debug_beam_ray", "ls_debug_beam_echoes", "ls_debug_beam_model_check")
 
 
 class SensorDesc(C.Structure):
@@ -77,6 +79,26 @@ class SensorTables(C.Structure):
 LS_RETURN_LAMBERT = 1
 LS_RETURN_TWO_SIDED = 2
 LS_SWEEP_DESKEW = 1   # ls_trace_scene_sweep: points in the frame-start sensor frame instead of the instantaneous one
+
+
+LS_BEAM_FIRST, LS_BEAM_LAST, LS_BEAM_STRONGEST = 1, 2, 4   # ls_trace_scene_beams: which echoes of a beam are returned
+
+
+class BeamModel(C.Structure):
+    """ls_beam_model: `pattern` float32 (S, 3) records (a, b, k) -- kept alive by this object --, the LS_BEAM_* mask of the returns,
+    the member count that makes an echo detectable, the range gap (metres) that separates two echoes"""
+    _fields_ = [("pattern", C.POINTER(C.c_float)), ("n_samples", C.c_uint32), ("returns", C.c_uint32), ("min_count", C.c_uint32),
+                ("echo_separation", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+    def __init__(self, pattern=((0.0, 0.0, 1.0),), returns: int = LS_BEAM_FIRST, min_count: int = 1, echo_separation: float = float("inf")):
+        super().__init__()
+        self._pattern = np.ascontiguousarray(pattern, np.float32).reshape(-1, 3)
+        self.pattern = self._pattern.ctypes.data_as(C.POINTER(C.c_float))
+        self.n_samples, self.returns, self.min_count, self.echo_separation = self._pattern.shape[0], returns, min_count, echo_separation
+
+    @property
+    def n_returns(self) -> int:
+        return bin(self.returns & 7).count("1")
 
 
 class ReturnModel(C.Structure):
@@ -223,6 +245,12 @@ def load() -> C.CDLL:
     L.ls_trace_scene_sweep_host.argtypes = [vp, vp, u32, u32, vp, vp, u32p, u32, vp]
     L.ls_sweep_poses_constant_twist.argtypes = [f32p, f32p, C.c_double, C.c_double, u32, f32p]
     L.ls_debug_sweep_ray.argtypes = [f32p, f32p, f32p]
+    L.ls_trace_scene_beams.argtypes = [vp, vp, C.POINTER(BeamModel), vp, vp, vp, vp, u32]
+    L.ls_trace_scene_beams_host.argtypes = [vp, C.POINTER(BeamModel), vp, vp, vp, u32p, u32]
+    L.ls_beam_pattern_rings.argtypes = [C.c_float, C.c_float, u32, u32, f32p]
+    L.ls_debug_beam_ray.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, f32p, f32p]
+    L.ls_debug_beam_echoes.argtypes = [C.POINTER(BeamModel), f32p, vp, u32p, u32p]
+    L.ls_debug_beam_model_check.argtypes = [C.POINTER(BeamModel), u32, u32]
     L.ls_geometry_type.argtypes = [vp, C.c_char_p]
     L.ls_debug_dense_hits.argtypes = [vp, f32p, u32p]
     L.ls_debug_trace_bruteforce.argtypes = [vp, f32p, u32p]
@@ -683,6 +711,33 @@ class Tracer:
                                          capacity, d_rays_out or None)
         return -1 if rc == -1 else int(self._check(rc, "ls_trace_scene_sweep"))
 
+    def traceBeamsHost(self, model: BeamModel, points: bool = True, hits: bool = True, echo: bool = True):
+        """A frame of diverging beams with multi-echo returns (ls_trace_scene_beams_host): model.n_samples sub-rays per ray of the
+        shard, the returns of every beam in ascending ray index and range.  An output asked for with False comes back None.
+        -> (rc, k, points uint8[k, 32] or None, hits HIT_DTYPE[k] or None -- t the reported range --, echo words uint32[k] or
+        None); rc = -1 (no commit, empty scene): no record."""
+        cap = model.n_returns * self.getTotalRays()
+        pts = np.zeros((cap, 32), np.uint8) if points else None
+        out = np.zeros(cap, HIT_DTYPE) if hits else None
+        ew = np.zeros(cap, np.uint32) if echo else None
+        k = C.c_uint32(0)
+        rc = self.L.ls_trace_scene_beams_host(self.h, C.byref(model), pts.ctypes.data if points else None, out.ctypes.data if hits else None,
+                                              ew.ctypes.data if echo else None, C.byref(k), cap)
+        if rc == -1:
+            return -1, 0, (pts[:0] if points else None), (out[:0] if hits else None), (ew[:0] if echo else None)
+        self._check(rc, "ls_trace_scene_beams_host")
+        n = int(k.value)
+        return int(rc), n, (pts[:n].copy() if points else None), (out[:n].copy() if hits else None), (ew[:n].copy() if echo else None)
+
+    def traceBeamsDevice(self, model: BeamModel, d_n_points: int, capacity: int, d_points32: int = 0, d_hits: int = 0, d_echo: int = 0,
+                         stream=None) -> int:
+        """ls_trace_scene_beams on device pointers (up to `capacity` 32-byte points, ls_hit records and echo words out, any may be 0;
+        the count in the device word d_n_points); the model's pattern is read during the call; enqueued on `stream` (a hipStream_t
+        as an int, None: the handle's), no wait.  -> 0, or -1 on an empty / uncommitted scene (nothing written)."""
+        rc = self.L.ls_trace_scene_beams(self.h, stream, C.byref(model), d_points32 or None, d_hits or None, d_echo or None, d_n_points or None,
+                                         capacity)
+        return -1 if rc == -1 else int(self._check(rc, "ls_trace_scene_beams"))
+
     # ---- test hooks
     def generateRaysAos(self, d_rays: int | None, d_hits: int | None):
         """LidarDevice::allRaysGPU's two buffers (Ray 32 B, Hit 24 B per ray) in device memory of the caller."""
@@ -800,3 +855,40 @@ def sweep_ray(d, pose12):
     if rc != 0:
         raise LidarShooterHipError(f"ls_debug_sweep_ray: status {rc}")
     return out
+
+
+def beam_pattern_rings(half_angle_az: float, half_angle_el: float, n_rings: int, per_ring: int):
+    """ls_beam_pattern_rings: the centre sample and n_rings concentric rings of per_ring samples -> float32 (1 + n_rings * per_ring,
+    3) records (a, b, k)"""
+    L = load()
+    S = 1 + int(n_rings) * int(per_ring)
+    out = np.zeros((max(S, 1), 3), np.float32)
+    rc = L.ls_beam_pattern_rings(float(half_angle_az), float(half_angle_el), int(n_rings), int(per_ring), _f32p(out) if S <= 64 else None)
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_beam_pattern_rings: status {rc}")
+    return out
+
+
+def beam_ray(sin_theta, cos_theta, cos_phi, sin_phi, abk):
+    """ls_debug_beam_ray: the sub-ray ls_trace_scene_beams casts for sample (a, b, k) of the ray with these factor-table entries, on
+    the host -> float32[8] (origin, tmin, direction, tmax)"""
+    L = load()
+    s, out = np.ascontiguousarray(abk, np.float32).reshape(3), np.zeros(8, np.float32)
+    rc = L.ls_debug_beam_ray(float(sin_theta), float(cos_theta), float(cos_phi), float(sin_phi), _f32p(s), _f32p(out))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_debug_beam_ray: status {rc}")
+    return out
+
+
+def beam_echoes(model: BeamModel, r, hit):
+    """ls_debug_beam_echoes: the returns of one beam from the reported ranges r[S] and the hit flags hit[S] of its sub-rays, on the
+    host -> uint32 (n, 2): the bits of r_e and the echo word, in ascending range"""
+    L = load()
+    rr, hh = np.ascontiguousarray(r, np.float32).reshape(-1), np.ascontiguousarray(hit, np.uint8).reshape(-1)
+    if rr.shape[0] != model.n_samples or hh.shape[0] != model.n_samples:
+        raise ValueError("r, hit: one entry per sample of the model")
+    out, n = np.zeros((3, 2), np.uint32), C.c_uint32(0)
+    rc = L.ls_debug_beam_echoes(C.byref(model), _f32p(rr), hh.ctypes.data, out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_debug_beam_echoes: status {rc}")
+    return out[:n.value].copy()

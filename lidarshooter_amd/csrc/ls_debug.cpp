@@ -6,6 +6,9 @@
 #include "ls_hit_attr.h"
 #include "ls_return_model.h"
 #include "ls_sweep.h"
+#include "ls_beam.h"
+
+#include <algorithm>
 
 using namespace lsi;
 
@@ -146,6 +149,47 @@ int ls_debug_sweep_ray(const float d[3], const float pose12[12], float ray8[8])
     if (!d || !pose12 || !ray8) return LS_ERR_INVALID_ARGUMENT;
     ls::sweep_ray(pose12, d[0], d[1], d[2], ray8);
     return LS_OK;
+}
+
+int ls_debug_beam_ray(float sin_theta, float cos_theta, float cos_phi, float sin_phi, const float abk[3], float ray8[8])
+{
+    if (!abk || !ray8) return LS_ERR_INVALID_ARGUMENT;
+    ls::beam_ray(sin_theta, cos_theta, cos_phi, sin_phi, abk[0], abk[1], ray8);
+    return LS_OK;
+}
+
+// what a group of k_beam_reduce's lanes does, position by position: the keys in ascending order, the ballot masks, beam_select
+int ls_debug_beam_echoes(const ls_beam_model *model, const float *r, const uint8_t *hit, uint32_t *out, uint32_t *n_out)
+{
+    if (!model || !r || !hit || !out || !n_out) return LS_ERR_INVALID_ARGUMENT;
+    const uint32_t S = model->n_samples;
+    if (S < 1u || S > ls::kBeamMaxSamples || !model->returns || (model->returns & ~(uint32_t)(LS_BEAM_FIRST | LS_BEAM_LAST | LS_BEAM_STRONGEST)) ||
+        model->min_count < 1u || model->min_count > S || !(model->echo_separation >= 0.0f))
+        return LS_ERR_INVALID_ARGUMENT;
+    unsigned long long key[ls::kBeamMaxSamples];
+    for (uint32_t s = 0; s < S; ++s) key[s] = hit[s] ? ls::beam_key(r[s], s) : ls::kBeamMiss;
+    std::sort(key, key + S);
+    unsigned long long starts = 0;
+    uint32_t n_hits = 0;
+    for (uint32_t j = 0; j < S; ++j) {
+        if (ls::beam_starts_echo(j ? key[j - 1] : 0ull, key[j], j, model->echo_separation)) starts |= 1ull << j;
+        if (key[j] != ls::kBeamMiss) ++n_hits;
+    }
+    const ls::BeamReturns ret = ls::beam_select(starts, n_hits, model->min_count, model->returns);
+    const uint32_t n = ret.n, w[3] = {ret.w0, ret.w1, ret.w2};
+    for (uint32_t i = 0; i < n; ++i) {
+        const unsigned long long sel = key[ls::beam_word_where(w[i])];
+        out[2 * i] = (uint32_t)(sel >> 8);
+        out[2 * i + 1] = ls::beam_word(w[i] & 7u, ls::beam_word_count(w[i]), ls::beam_key_sample(sel));
+    }
+    *n_out = n;
+    return LS_OK;
+}
+
+int ls_debug_beam_model_check(const ls_beam_model *model, uint32_t shard_rays, uint32_t capacity)
+{
+    int status = LS_OK;
+    return ls::beam_model_invalid(model, shard_rays, capacity, &status) ? status : LS_OK;
 }
 
 }  // extern "C"

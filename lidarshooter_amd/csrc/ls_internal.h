@@ -7,7 +7,8 @@
 //   ls_trace.cpp     traceScene: output buffers, frames in flight, the per-frame launch sequence, stage timings
 //   ls_rays.cpp      ls_trace_rays: the query set of per-geometry hierarchies (built lazily), batches of geometries per launch;
 //                    ls_hit_attributes: the per-geomID table of its gather kernel; ls_apply_return_model: the same table, its scratch;
-//                    ls_trace_scene_sweep: its scratch around the same walk (ls_sweep.hip, ls_sweep.h)
+//                    ls_trace_scene_sweep: its scratch around the same walk (ls_sweep.hip, ls_sweep.h);
+//                    ls_trace_scene_beams: likewise (ls_beam.hip, ls_beam.h)
 //   ls_host_pool.cpp worker threads for host-side copies, point expansion
 //   ls_debug.cpp     include/lidarshooter_hip_debug.h (tests and bench.py only)
 #pragma once
@@ -285,6 +286,12 @@ struct ls_tracer {
         // bytes each) and the hit count of every 256 of them (every call is ordered through the handle's stream: one at a time)
         lsi::DevBuf<uint8_t> sweep_rays, sweep_hits;
         lsi::DevBuf<uint32_t> sweep_counts;
+        // ls_trace_scene_beams: the shard's sub-ray records (32 bytes each, at ray * S + sample), the walk's dense hit records (16
+        // bytes each), the returns of every beam (3 x 16 bytes) and, in one array, the return count of every beam and of every 256
+        // of them (one call at a time, as the sweep)
+        lsi::DevBuf<uint8_t> beam_rays, beam_hits;
+        lsi::DevBuf<uint4> beam_blocks;
+        lsi::DevBuf<uint32_t> beam_counts;
         std::vector<RayQuerySlot> built;       // per layout entry
         std::vector<int> layout_ids;           // geometry ids of the layout the slots were made for ...
         std::vector<uint32_t> layout_firsts;   // ... and their first vertex, first triangle in it

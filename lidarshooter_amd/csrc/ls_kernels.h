@@ -307,6 +307,17 @@ size_t sweep_block_count(uint32_t nq);
 void launch_sweep_rays(hipStream_t s, const SensorTables &tb, const float *pose, void *rays, void *rays_out);
 void launch_sweep_pack(hipStream_t s, const SensorTables &tb, const void *dense, uint32_t *block_counts, const float *pose, bool deskew,
                        void *points32, void *hits, uint32_t *n_points);
+// ls_trace_scene_beams (ls_beam.hip): the S samples of every ray of the shard as 32-byte records at q * S + s (q the shard-local ray
+// index; what launch_trace_rays reads); then, over the walk's dense ls_hit records of those sub-rays, the echoes of every beam
+// (blocks: 3 x 16 bytes per beam, cnt: one word per beam) and their ordered pack: 32-byte points, ls_hit records with the global
+// ray index and the reported range, echo words (any may be nullptr), the count in *n_points.  block_counts: beam_block_count(rays
+// of the shard) words.  The pattern travels by value in the kernel arguments (ls_beam.h).
+struct BeamPattern;
+size_t beam_block_count(uint32_t nq);
+void launch_beam_rays(hipStream_t s, const SensorTables &tb, const BeamPattern &pat, uint32_t S, void *rays);
+void launch_beam_pack(hipStream_t s, const SensorTables &tb, const BeamPattern &pat, uint32_t S, float separation, uint32_t min_count,
+                      uint32_t returns, const void *dense, void *blocks, uint32_t *cnt, uint32_t *block_counts, void *points32, void *hits,
+                      uint32_t *echo, uint32_t *n_points, uint32_t capacity);
 void launch_rowcount(hipStream_t s, const uint32_t *gid, uint32_t nrays, uint32_t *row_counts, uint32_t *queue_heads = nullptr);   // queue_heads: zeroed for the next k_trace
 // Progress of a synchronous frame whose compact points go straight to pinned host memory (ls_trace_scene_begin /
 // ls_trace_scene_expand): the device publishes, with system-scope release, (1) the frame's hit count as the pack pass

@@ -7,6 +7,9 @@
 // an ordered compaction: ls_returns.hip; after them).
 // ls_trace_scene_sweep / ls_trace_scene_sweep_host: a frame whose sensor moves during the turn -- the shard's rays through per-column
 // poses, the closest-hit walk over them, an ordered pack (ls_sweep.hip; at the end); ls_sweep_poses_constant_twist: a pose table.
+// ls_trace_scene_beams / ls_trace_scene_beams_host: a frame of diverging beams -- S sub-rays per ray of the shard, the same walk over
+// them, the echoes of every beam and an ordered pack of the selected returns (ls_beam.hip; after the sweep);
+// ls_beam_pattern_rings: a sample pattern.
 //
 // The query set (ls_tracer::RayQuery) is a hierarchy set of its own -- one hierarchy per geometry, built by the kernels of
 // the instanced commit (hier_layout / hier_build, ls_commit.cpp) into buffers nothing in the frame path reads or writes,
@@ -19,6 +22,7 @@
 // poses builds nothing; new vertices refit that geometry (its sorted order is kept in the set's own keys), new indices rebuild it.
 #include "ls_internal.h"
 #include "ls_return_model.h"
+#include "ls_beam.h"
 
 #include <algorithm>
 #include <cmath>
@@ -226,6 +230,7 @@ void ray_query_release(ls_tracer *tr)
     release(q.records); release(q.nodes); release(q.wide_nodes); release(q.range_boxes); release(q.verts);
     release(q.keys_a); release(q.keys_b); release(q.vals_b); release(q.sort_temp); release(q.spill); release(q.io);
     release(q.sweep_rays); release(q.sweep_hits); release(q.sweep_counts);
+    release(q.beam_rays); release(q.beam_hits); release(q.beam_blocks); release(q.beam_counts);
     if (q.d_maxabs) (void)hipFree(q.d_maxabs);
     if (q.d_counters) (void)hipFree(q.d_counters);
     if (q.ev_ready) (void)hipEventDestroy(q.ev_ready);
@@ -615,6 +620,78 @@ int sweep_host_locked(ls_tracer *tr, const float *col_pose, uint32_t n_cols, uin
     return LS_OK;
 }
 
+// ---- ls_trace_scene_beams: diverging beams with multi-echo returns (ls_beam.hip around the ray queries' walk) --------------
+
+// what both entry points refuse before any device call: an open frame graph, a NULL count, the model, the capacity, the size
+int beams_check(ls_tracer *tr, const ls_beam_model *model, const void *n_points, uint32_t capacity)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (!n_points) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null count output");
+    int status = LS_OK;
+    if (const char *why = ls::beam_model_invalid(model, shard_rays(tr), capacity, &status)) return fail(tr, status, why);
+    return LS_OK;
+}
+
+uint32_t beam_returns(const ls_beam_model *model) { return (uint32_t)__builtin_popcount(model->returns); }
+
+// (beams_check passed) the return codes, stream order and hierarchies of sweep_locked
+int beams_locked(ls_tracer *tr, hipStream_t s, const ls_beam_model *model, void *d_points32, void *d_hits, uint32_t *d_echo, uint32_t *d_n_points,
+                 uint32_t capacity)
+{
+    ls_tracer::RayQuery &q = tr->rq;
+    q.last_built = 0;
+    if (!tr->committed || tr->n_tris == 0) return -1;   // as ls_trace_scene; nothing is written, the count included
+    const uint32_t nq = shard_rays(tr), S = model->n_samples, n = nq * S;   // n <= 2^27
+    ls::BeamPattern pat;   // the caller's pattern, read here and now: it travels in the kernel arguments
+    std::memset(static_cast<void *>(&pat), 0, sizeof(pat));
+    for (uint32_t k = 0; k < S; ++k) {
+        pat.a[k] = model->pattern[3 * k];
+        pat.b[k] = model->pattern[3 * k + 1];
+        pat.k[k] = model->pattern[3 * k + 2];
+    }
+    int rc;
+    if ((rc = query_enter(tr, s))) return rc;
+    if ((rc = ensure(tr, q.beam_rays, (size_t)n * 32))) return rc;
+    if ((rc = ensure(tr, q.beam_hits, (size_t)n * 16))) return rc;
+    if ((rc = ensure(tr, q.beam_blocks, 3 * (size_t)nq))) return rc;
+    if ((rc = ensure(tr, q.beam_counts, (size_t)nq + ls::beam_block_count(nq)))) return rc;
+    const ls::SensorTables tb = tables(tr);
+    ls::launch_beam_rays(s, tb, pat, S, q.beam_rays.p);
+    if ((rc = query_walk(tr, s, q.beam_rays.p, n, q.beam_hits.p, kClosest))) return rc;
+    ls::launch_beam_pack(s, tb, pat, S, model->echo_separation, model->min_count, model->returns, q.beam_hits.p, q.beam_blocks.p, q.beam_counts.p,
+                         q.beam_counts.p + nq, d_points32, d_hits, d_echo, d_n_points, capacity);
+    LS_HIP(hipGetLastError());
+    return query_leave(tr, s);
+}
+
+// the host-memory variant: the outputs staged in q.io, on the handle's stream; the count comes back first, then as many records
+int beams_host_locked(ls_tracer *tr, const ls_beam_model *model, void *points32, void *hits, uint32_t *echo, uint32_t *n_points)
+{
+    tr->rq.last_built = 0;
+    if (!tr->committed || tr->n_tris == 0) return -1;
+    ls_tracer::RayQuery &q = tr->rq;
+    hipStream_t s = tr->stream;
+    int rc;
+    if ((rc = flush_pipeline(tr))) return rc;
+    const size_t cap = (size_t)beam_returns(model) * shard_rays(tr);   // <= 3 * 2^27
+    const size_t point_bytes = points32 ? cap * 32 : 0, hit_bytes = hits ? cap * 16 : 0, echo_bytes = echo ? (cap * 4 + 15) & ~(size_t)15 : 0;
+    if ((rc = ensure(tr, q.io, point_bytes + hit_bytes + echo_bytes + 16))) return rc;
+    uint8_t *d_points = q.io.p, *d_hits = d_points + point_bytes, *d_echo = d_hits + hit_bytes, *d_n = d_echo + echo_bytes;
+    if ((rc = beams_locked(tr, s, model, points32 ? d_points : nullptr, hits ? d_hits : nullptr, echo ? reinterpret_cast<uint32_t *>(d_echo) : nullptr,
+                           reinterpret_cast<uint32_t *>(d_n), (uint32_t)cap)))
+        return rc;
+    uint32_t count = 0;
+    LS_HIP(hipMemcpyAsync(&count, d_n, 4, hipMemcpyDeviceToHost, s));
+    LS_HIP(hipStreamSynchronize(s));
+    if (count > cap) return fail(tr, LS_ERR_HIP, "ls_trace_scene_beams: more returns than the beams can give");
+    if (count && points32) LS_HIP(hipMemcpyAsync(points32, d_points, (size_t)count * 32, hipMemcpyDeviceToHost, s));
+    if (count && hits) LS_HIP(hipMemcpyAsync(hits, d_hits, (size_t)count * 16, hipMemcpyDeviceToHost, s));
+    if (count && echo) LS_HIP(hipMemcpyAsync(echo, d_echo, (size_t)count * 4, hipMemcpyDeviceToHost, s));
+    LS_HIP(hipStreamSynchronize(s));
+    *n_points = count;
+    return LS_OK;
+}
+
 }  // namespace
 
 void hit_attr_release(ls_tracer *tr)
@@ -724,6 +801,52 @@ int ls_trace_scene_sweep_host(ls_tracer *tr, const float *col_pose, uint32_t n_c
 {
     LS_ENTER(tr);
     return sweep_host_locked(tr, col_pose, n_cols, flags, points32, hits, n_points, capacity, rays_out);
+}
+
+// the refusals come before anything touches the device (the handle's included): LS_ENTER with beams_check in front of hipSetDevice
+#define LS_ENTER_BEAMS(tr, model, n_points, capacity, misaligned)                                                        \
+    if (!(tr)) return LS_ERR_INVALID_ARGUMENT;                                                                           \
+    std::lock_guard<std::mutex> lock_((tr)->mu);                                                                         \
+    if (const int refused_ = beams_check((tr), (model), (n_points), (capacity))) return refused_;                        \
+    if (misaligned)                                                                                                      \
+        return lsi::fail((tr), LS_ERR_INVALID_ARGUMENT,                                                                  \
+                         "points and hit records must be 16-byte aligned, the echo words and the count 4-byte aligned"); \
+    lsi::SinkScope sink_scope_(tr);                                                                                      \
+    if (hipSetDevice((tr)->device) != hipSuccess) return lsi::fail((tr), LS_ERR_HIP, "hipSetDevice failed")
+
+int ls_trace_scene_beams(ls_tracer *tr, void *hip_stream, const ls_beam_model *model, void *d_points32, void *d_hits, uint32_t *d_echo,
+                         uint32_t *d_n_points, uint32_t capacity)
+{
+    LS_ENTER_BEAMS(tr, model, d_n_points, capacity,
+                   ((uintptr_t)d_points32 & 15u) || ((uintptr_t)d_hits & 15u) || ((uintptr_t)d_echo & 3u) || ((uintptr_t)d_n_points & 3u));
+    return beams_locked(tr, hip_stream ? static_cast<hipStream_t>(hip_stream) : tr->stream, model, d_points32, d_hits, d_echo, d_n_points, capacity);
+}
+
+int ls_trace_scene_beams_host(ls_tracer *tr, const ls_beam_model *model, void *points32, void *hits, uint32_t *echo, uint32_t *n_points,
+                              uint32_t capacity)
+{
+    LS_ENTER_BEAMS(tr, model, n_points, capacity, false);   // (host memory: any alignment)
+    return beams_host_locked(tr, model, points32, hits, echo, n_points);
+}
+
+// host only: the centre sample, then ring after ring; double throughout, one rounding per entry (k from the rounded a and b)
+int ls_beam_pattern_rings(float half_angle_az, float half_angle_el, uint32_t n_rings, uint32_t per_ring, float *pattern)
+{
+    if (!pattern || !std::isfinite(half_angle_az) || !std::isfinite(half_angle_el)) return LS_ERR_INVALID_ARGUMENT;
+    if ((unsigned long long)n_rings * per_ring + 1ull > ls::kBeamMaxSamples) return LS_ERR_INVALID_ARGUMENT;
+    pattern[0] = 0.0f;
+    pattern[1] = 0.0f;
+    pattern[2] = 1.0f;
+    float *p = pattern + 3;
+    for (uint32_t j = 1; j <= n_rings; ++j)
+        for (uint32_t i = 0; i < per_ring; ++i, p += 3) {
+            const double rho = (double)j / (double)n_rings, phi = 2.0 * M_PI * ((double)i + 0.5 * (double)(j - 1)) / (double)per_ring;
+            p[0] = (float)((double)half_angle_az * rho * std::cos(phi));
+            p[1] = (float)((double)half_angle_el * rho * std::sin(phi));
+            const double a = p[0], b = p[1];
+            p[2] = (float)std::sqrt(1.0 + (a * a + b * b));
+        }
+    return LS_OK;
 }
 
 // host only: tau_h = t0 + h dt; R_h = Rodrigues' rotation by ang_vel * tau_h, o_h = lin_vel * tau_h; double throughout, one rounding
