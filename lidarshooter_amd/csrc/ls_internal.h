@@ -5,10 +5,10 @@
 //   ls_registry.cpp  ITracer's geometry bookkeeping: add / remove / update (EmbreeTracer.cpp:115-288), uploads
 //   ls_commit.cpp    commitScene: layout, group-culling data, BVH build / refit / instanced hierarchies
 //   ls_trace.cpp     traceScene: output buffers, frames in flight, the per-frame launch sequence, stage timings
-//   ls_rays.cpp      ls_trace_rays: the query set of per-geometry hierarchies (built lazily), batches of geometries per launch;
-//                    ls_hit_attributes: the per-geomID table of its gather kernel; ls_apply_return_model: the same table, its scratch;
-//                    ls_trace_scene_sweep: its scratch around the same walk (ls_sweep.hip, ls_sweep.h);
-//                    ls_trace_scene_beams: likewise (ls_beam.hip, ls_beam.h)
+//   ls_query.cpp     ls_trace_rays / ls_occluded_rays / ls_closest_points: the query set of per-geometry hierarchies (built lazily),
+//                    batches of geometries per launch; what every query entry point shares (stream hand-over, staging, read-back)
+//   ls_gather.cpp    ls_hit_attributes: the per-geomID table of its gather kernel; ls_apply_return_model: the same table, its scratch
+//   ls_scan.cpp      ls_trace_scene_sweep, ls_trace_scene_beams: their scratch around the queries' walk (ls_sweep.hip, ls_beam.hip)
 //   ls_host_pool.cpp worker threads for host-side copies, point expansion
 //   ls_debug.cpp     include/lidarshooter_hip_debug.h (tests and bench.py only)
 #pragma once
@@ -24,6 +24,7 @@
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -259,7 +260,7 @@ struct ls_tracer {
     uint32_t last_slot = 0xFFFFFFFFu;   // the frame issued last: its stream of the three-stream rotation (none: it ran on `stream`)
     hipStream_t last_stream = nullptr;
 
-    // ls_trace_rays (ls_rays.cpp): a hierarchy set of its own -- nothing here is read or written by the frame path, so that
+    // ls_trace_rays (ls_query.cpp): a hierarchy set of its own -- nothing here is read or written by the frame path, so that
     // frames issued after a query on other streams may overlap it
     struct RayQuerySlot {
         bool valid = false;
@@ -281,7 +282,7 @@ struct ls_tracer {
         uint32_t *d_maxabs = nullptr;          // kMaxGeoms words
         uint32_t *d_counters = nullptr;        // ray counter of each launch (kMaxGeoms / kGeomsPerLaunch words)
         lsi::DevBuf<uint32_t> spill;
-        lsi::DevBuf<uint8_t> io;               // ls_trace_rays_host: rays, then hit records
+        lsi::DevBuf<uint8_t> io;               // the host-memory variants' staging (IoPlan)
         // ls_trace_scene_sweep: the shard's ray records (32 bytes each, ascending ray index), the walk's dense hit records (16
         // bytes each) and the hit count of every 256 of them (every call is ordered through the handle's stream: one at a time)
         lsi::DevBuf<uint8_t> sweep_rays, sweep_hits;
@@ -299,7 +300,7 @@ struct ls_tracer {
         hipEvent_t ev_ready = nullptr, ev_done = nullptr;
         long last_built = 0;                   // LS_INFO_RAY_QUERY_BUILT
     } rq;
-    // ls_hit_attributes (ls_rays.cpp): the per-geomID table k_hit_attributes reads, refreshed by the call that finds it out of
+    // ls_hit_attributes (ls_gather.cpp): the per-geomID table k_hit_attributes reads, refreshed by the call that finds it out of
     // date (a pose, a vertex or index buffer, the registry or the sensor pose changed)
     struct HitAttr {
         lsi::DevBuf<ls::AttrGeom> table;       // device, indexed by geomID
@@ -436,15 +437,51 @@ int hier_layout(ls_tracer *tr, HierSet &hs, const std::vector<Geometry *> &order
 // four-wide twins now (the slot's wide_made says whether they were made)
 int hier_build(ls_tracer *tr, HierSet &hs, hipStream_t s, size_t i, const Geometry &ge, uint32_t vfirst, uint32_t tfirst, const float *A12,
                const float *R9, const float *T3, uint32_t leaf_size, bool refit, bool widen);
-// ls_rays.cpp
+// ls_query.cpp
 void ray_query_release(ls_tracer *tr);
+#pragma GCC visibility push(hidden)   // what ls_gather.cpp and ls_scan.cpp share with it: not exported
+constexpr uint32_t kMaxQueryRecords = 0xFFF00000u;   // rays, points or hit records in one call
+// the registry's geometry of layout entry i, provided it still is what the last commit laid out (every query's check)
+int committed_geometry(ls_tracer *tr, size_t i, Geometry **out);
+// the last test of every query's check: -1 without a committed, non-empty scene, as ls_trace_scene (nothing is written)
+inline int uncommitted(const ls_tracer *tr) { return !tr->committed || tr->n_tris == 0 ? -1 : LS_OK; }
+hipStream_t stream_of(const ls_tracer *tr, void *hip_stream);   // the caller's stream, or the handle's for NULL
+inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+template <typename... P>
+inline bool misaligned16(const P *...p) { return (misaligned(p, 16) || ...); }
+// a query's place among what the handle issues (query_enter: the call's one flush_pipeline) and its walk over the hierarchies
+struct RayQueryKind;
+const RayQueryKind &closest_hits();   // ls_trace_rays' kind: the walk of the frames in ls_scan.cpp
+int query_enter(ls_tracer *tr, hipStream_t s);
+int query_walk(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out, const RayQueryKind &kind);
+int query_leave(ls_tracer *tr, hipStream_t s);
+// the host-memory variants stage in RayQuery::io: add() every piece (each starts 16-byte aligned), ensure total(), then form pointers
+struct IoPlan {
+    size_t bytes = 0;
+    size_t add(size_t n) { const size_t at = bytes; bytes += (n + 15) & ~(size_t)15; return at; }
+    size_t total() const { return bytes; }
+};
+// one output of a counted read-back: `bytes` of every record the device counted; rows != 0: rows x bytes at this pitch, whatever the count
+struct Fetch {
+    void *dst;   // (NULL: not wanted)
+    const uint8_t *src;
+    size_t bytes, rows = 0, pitch = 0;
+};
+// on the handle's stream: the count word comes back first (above limit: LS_ERR_HIP with this message), then the outputs; returns
+// when they are filled and *n_out is the count
+int fetch_counted(ls_tracer *tr, const void *d_count, size_t limit, const char *overflow, std::initializer_list<Fetch> outs, uint32_t *n_out);
+#pragma GCC visibility pop
+// ls_gather.cpp
 void hit_attr_release(ls_tracer *tr);
 
 }  // namespace lsi
 
-// every entry point that takes a handle: argument check, the handle's mutex, its device
-#define LS_ENTER(tr)                                   \
-    if (!(tr)) return LS_ERR_INVALID_ARGUMENT;         \
-    std::lock_guard<std::mutex> lock_((tr)->mu);       \
-    lsi::SinkScope sink_scope_(tr);                    \
+// every entry point that takes a handle: argument check, the handle's mutex, what it refuses before anything touches the device
+// (an expression evaluated under the mutex: a status to return, or 0), its device
+#define LS_ENTER_CHECKED(tr, refusal)                   \
+    if (!(tr)) return LS_ERR_INVALID_ARGUMENT;          \
+    std::lock_guard<std::mutex> lock_((tr)->mu);        \
+    if (const int refused_ = (refusal)) return refused_; \
+    lsi::SinkScope sink_scope_(tr);                     \
     if (hipSetDevice((tr)->device) != hipSuccess) return lsi::fail((tr), LS_ERR_HIP, "hipSetDevice failed")
+#define LS_ENTER(tr) LS_ENTER_CHECKED(tr, LS_OK)

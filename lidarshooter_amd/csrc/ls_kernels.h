@@ -238,7 +238,7 @@ void launch_trace_instanced(hipStream_t s, uint32_t grid_blocks, const SensorTab
 void launch_widen(hipStream_t s, const FatNode *nodes, uint32_t n_leaves, WideNode *wide);
 
 // ls_trace_rays (ls_rays.hip): closest hits of caller-supplied rays (32-byte records: origin, tmin, direction, tmax, in the
-// sensor frame) over the query set's hierarchies, one per geometry in mesh space (ls_rays.cpp).  A geometry whose mesh ->
+// sensor frame) over the query set's hierarchies, one per geometry in mesh space (ls_query.cpp).  A geometry whose mesh ->
 // sensor map has no usable inverse has its hierarchy over its SENSOR-frame vertices instead: xform 0, minv = identity, o = 0.
 struct RayGeom {
     uint32_t node_first, rec_first;   // this geometry's nodes / records inside the query set's arrays
@@ -267,7 +267,7 @@ void launch_occluded_rays(hipStream_t s, uint32_t grid_blocks, const void *rays,
 // ls_closest_points (ls_points.hip): the nearest surface point to each of n caller points (16-byte records: x, y, z in the
 // sensor frame, radius) over the same hierarchies, described by the same RayBatch; out = n 32-byte records (qx, qy, qz, dist |
 // geom, prim, index, 0).  PointMargins is what makes a box's distance a lower bound of the exact test's float32 d2
-// (ls_rays.cpp: point_margins), per geometry of the batch.
+// (ls_query.cpp: point_margins), per geometry of the batch.
 struct PointMargins {
     uint32_t last;                    // 1: the last launch of a query (the running d2 kept in a record's last word is cleared)
     float e0[kGeomsPerLaunch];        // every box is widened by e0 + e1 * |p|inf (the hierarchy's own units) ...

@@ -7,7 +7,7 @@
 //   * per four-wide node the squared distance of the query point to each child box, in the hierarchy's own space (mesh space:
 //     p_m = minv * p + o), every box widened by E, and scaled into the sensor frame by s2 <= sigma_min^2 of mesh -> sensor;
 //   * a child is dropped only when that lower bound is STRICTLY greater than the current bound min(best d2, radius^2): the
-//     margins E and s2 (PointMargins, ls_rays.cpp: point_margins) make it a lower bound of the float32 d2 the exact test
+//     margins E and s2 (PointMargins, ls_query.cpp: point_margins) make it a lower bound of the float32 d2 the exact test
 //     gives for every triangle below the box, so the result is the brute force's bit for bit, ties included;
 //   * the four children are sorted nearest first; the nearest is walked on, the others are pushed farthest first.  The stack
 //     holds references only (a bound next to each would double the 32 KiB of LDS that sets the occupancy): a node popped
