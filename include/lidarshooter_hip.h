@@ -729,8 +729,8 @@ typedef struct ls_beam_model {
  * for it.  Frames of ls_trace_scene* are unaffected.  The call uses scratch of its own on the handle, grown on demand and released
  * with the query state: the shard's rays x S x (32 bytes of ray record + 16 of dense hit record), 48 + 4 bytes per ray for its
  * returns, one word per 256 rays; calls on one handle use it one after the other.
- * Not offered: per-sample weights (every sub-hit counts once); beams under the per-column poses of ls_trace_scene_sweep; a call of
- * the ITracer adapter.  ls_apply_return_model refuses these records (ls_hit_attributes calls them invalid): their t is the
+ * Per-sample weights and beams under the per-column poses of ls_trace_scene_sweep: ls_trace_scene_beams_sweep below (here every
+ * sub-hit counts once and the sensor is at rest).  Not offered: a call of the ITracer adapter.  ls_apply_return_model refuses these records (ls_hit_attributes calls them invalid): their t is the
  * reported range r_e, not the distance along the sub-ray that the exact test needs. */
 int ls_trace_scene_beams(ls_tracer *tr, void *hip_stream, const ls_beam_model *model,
                          void *d_points32, void *d_hits, uint32_t *d_echo, uint32_t *d_n_points, uint32_t capacity);
@@ -745,6 +745,59 @@ int ls_trace_scene_beams_host(ls_tracer *tr, const ls_beam_model *model,
  * b^2)), evaluated in double from the ROUNDED a and b, then rounded once.  pattern: S records of 3 floats.
  * LS_ERR_INVALID_ARGUMENT for a NULL pointer, more than 64 samples or non-finite angles. */
 int ls_beam_pattern_rings(float half_angle_az, float half_angle_el, uint32_t n_rings, uint32_t per_ring, float *pattern);
+
+/* ---- beam frames of a moving sensor, with a weight per sample: ls_trace_scene_beams and ls_trace_scene_sweep in one call.  A
+ * spinning LiDAR on a moving carrier both diverges and skews, and the power across its footprint is no top hat but roughly a
+ * Gaussian: the sub-rays of every beam go through their column's pose, and an echo is as strong as the weights of its members.
+ *   model:   exactly as in ls_trace_scene_beams: the same validation, the same limits (S <= 64, the shard's rays x S <= 2^27), the
+ *            same capacity rule.
+ *   weights: HOST memory: NULL -- every sample weighs 1 -- or n_samples integers, each in 1..65535 (else
+ *            LS_ERR_INVALID_ARGUMENT).  Like the pattern they are read and validated during the call and travel in the kernel
+ *            arguments (128 bytes on top of the pattern's 768): nothing of the caller's outlives the call.  Integers on purpose: the
+ *            strength W_e of an echo, the sum of its members' weights, is exact and independent of any order, and at most 64 x 65535
+ *            < 2^24, so exact as a float.
+ *   echoes:  formed as in ls_trace_scene_beams: the keys, the (r, s) order, the separation rule.  An echo is detectable when n_e
+ *            >= min_count AND W_e >= min_weight (min_weight 0: no strength threshold).  Among the detectable echoes FIRST is the
+ *            nearest, LAST the farthest, STRONGEST the one with the largest W_e (the nearer of equals); coinciding selections are
+ *            one record, the records in ascending range, as there.
+ *   d_col_pose, n_cols: NULL with n_cols 0: the sensor is at rest.  Otherwise the table of ls_trace_scene_sweep: n_cols must equal
+ *            LS_INFO_AZIMUTH_COUNT, 12 floats per GLOBAL column, device memory, 4-byte aligned, never read on the host.
+ *   sub-rays: sample s of ray (v, h) is ls_trace_scene_beams' sub-ray d_s (a component -0 made +0) carried through the pose of
+ *            column h by ls_trace_scene_sweep's sequence: origin o_h, direction d'_s,i = (R[i][0] d_s,x + R[i][1] d_s,y) + R[i][2]
+ *            d_s,z, tmin 0, tmax 1e16 -- two existing sequences composed, no new arithmetic (ls_debug_beam_sweep_ray in
+ *            lidarshooter_hip_debug.h runs them on the host).  An identity record gives ls_trace_scene_beams' sub-ray bit for bit,
+ *            a centre-only pattern ls_trace_scene_sweep's ray; a column whose record holds a non-finite value yields misses for
+ *            all its sub-rays, hence no returns.  At rest the sub-rays are ls_trace_scene_beams'.
+ *   flags:   0 or LS_SWEEP_DESKEW (other bits: LS_ERR_INVALID_ARGUMENT).  By default xyz = r_e * d per axis with the nominal d
+ *            and no sum: ls_trace_scene_beams' points, the sensor's report in the frame of its own instant.  With LS_SWEEP_DESKEW
+ *            xyz = o_h + r_e * d' per axis, d' = R_h d (ls_trace_scene_sweep's deskewed point for the nominal direction and the
+ *            reported range).  At rest the flag changes nothing.
+ *   intensity: (64.0f * (float)W_e) / (float)W_total, W_total the sum of all S weights; with NULL weights (64 n_e) / S, the bits of
+ *            ls_trace_scene_beams.  The echo word keeps its layout (n_e in bits 8-14); W_e is not reported apart from the intensity.
+ *   d_hits, d_echo, d_n_points, capacity, the order of the records, NULL outputs: as in ls_trace_scene_beams.
+ * With NULL weights, min_weight 0 and no table (or an identity table) the call returns ls_trace_scene_beams' bytes.  Return codes,
+ * alignment checks, stream order, the frame graph rule, the shard handling and LS_INFO_RAY_QUERY_BUILT are those of
+ * ls_trace_scene_beams and ls_trace_scene_sweep; the checks run in the order: frame graph, NULL count, model, weights, pose table
+ * and flags, alignment, then the commit (-1 with no commit or an empty scene writes nothing, the count included).  The call uses
+ * the scratch of ls_trace_scene_beams on the handle and 12 more bytes per ray; calls on one handle use it one after the other.
+ * Not offered: these echoes through ls_apply_return_model (their t is still the reported range); a rays_out; a call of the ITracer
+ * adapter; geometries that move during the turn. */
+int ls_trace_scene_beams_sweep(ls_tracer *tr, void *hip_stream, const ls_beam_model *model,
+                               const uint32_t *weights, uint32_t min_weight,
+                               const float *d_col_pose, uint32_t n_cols, uint32_t flags,
+                               void *d_points32, void *d_hits, uint32_t *d_echo, uint32_t *d_n_points, uint32_t capacity);
+/* The same with host memory (pageable) in and out, on the handle's stream: the table is copied to the device; returns when the
+ * outputs are filled (*n_points records of each). */
+int ls_trace_scene_beams_sweep_host(ls_tracer *tr, const ls_beam_model *model,
+                                    const uint32_t *weights, uint32_t min_weight,
+                                    const float *col_pose, uint32_t n_cols, uint32_t flags,
+                                    void *points32, void *hits, uint32_t *echo, uint32_t *n_points, uint32_t capacity);
+
+/* Gaussian weights for a pattern (host only, no handle, no device): w_s = max(1, round(65535 exp(-((a_s / sigma_az)^2 + (b_s /
+ * sigma_el)^2) / 2))), evaluated in double and rounded once: the centre sample gets 65535.  weights: n_samples words.
+ * LS_ERR_INVALID_ARGUMENT for NULL pointers, n_samples outside 1..64, non-finite pattern entries, sigmas that are non-finite or
+ * <= 0. */
+int ls_beam_weights_gaussian(const float *pattern, uint32_t n_samples, float sigma_az, float sigma_el, uint32_t *weights);
 
 #ifdef __cplusplus
 }

@@ -87,6 +87,19 @@ int ls_debug_beam_echoes(const ls_beam_model *model, const float *r, const uint8
  * otherwise valid arguments (no device, no handle): LS_OK, LS_ERR_INVALID_ARGUMENT or LS_ERR_OUT_OF_RANGE */
 int ls_debug_beam_model_check(const ls_beam_model *model, uint32_t shard_rays, uint32_t capacity);
 
+/* the sub-ray ls_trace_scene_beams_sweep casts for sample abk of the ray with these factor-table entries under one column's pose
+ * record, on the host (no device, no handle): ls_debug_beam_ray's sequence, then ls_debug_sweep_ray's on its direction -- what
+ * k_beam_sweep_rays runs -> origin o, tmin 0, d'_s = R d_s, tmax 1e16 */
+int ls_debug_beam_sweep_ray(float sin_theta, float cos_theta, float cos_phi, float sin_phi, const float abk[3], const float pose12[12], float ray8[8]);
+/* ls_debug_beam_echoes with a weight per sample (NULL: 1 each; n_samples integers in 1..65535 otherwise) and the strength threshold
+ * min_weight: the keys, the echo starts, the strengths and the selection k_beam_reduce_weighted runs (csrc/ls_beam.h) -> *n_out
+ * returns, 0..3, in ascending range, three words each in out: the bits of r_e, the echo word and the strength W_e.
+ * LS_ERR_INVALID_ARGUMENT as ls_debug_beam_echoes, and for a weight outside 1..65535. */
+int ls_debug_beam_echoes_weighted(const ls_beam_model *model, const uint32_t *weights, uint32_t min_weight, const float *r, const uint8_t *hit, uint32_t *out /* up to 3 x {r bits, echo word, W_e} */, uint32_t *n_out);
+/* the status ls_trace_scene_beams_sweep would return for this model and these weights (NULL: 1 each) on a handle whose shard has
+ * shard_rays rays, with this capacity and otherwise valid arguments (no device, no handle) */
+int ls_debug_beam_sweep_check(const ls_beam_model *model, const uint32_t *weights, uint32_t shard_rays, uint32_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,12 +56,14 @@ SYMBOLS = (
     "ls_apply_return_model", "ls_apply_return_model_host",
     "ls_trace_scene_sweep", "ls_trace_scene_sweep_host", "ls_sweep_poses_constant_twist",
     "ls_trace_scene_beams", "ls_trace_scene_beams_host", "ls_beam_pattern_rings",
+    "ls_trace_scene_beams_sweep", "ls_trace_scene_beams_sweep_host", "ls_beam_weights_gaussian",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
 DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_scene_size", "ls_debug_download_scene",
                  "ls_debug_download_bvh", "ls_debug_sort_pairs", "ls_debug_expand_hits", "ls_debug_closest_on_triangle",
                  "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model", "ls_debug_sweep_ray",
-                 "ls_debug_beam_ray", "ls_debug_beam_echoes", "ls_debug_beam_model_check")
+                 "ls_debug_beam_ray", "ls_debug_beam_echoes", "ls_debug_beam_model_check",
+                 "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check")
 
 
 class SensorDesc(C.Structure):
@@ -251,6 +253,12 @@ def load() -> C.CDLL:
     L.ls_debug_beam_ray.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, f32p, f32p]
     L.ls_debug_beam_echoes.argtypes = [C.POINTER(BeamModel), f32p, vp, u32p, u32p]
     L.ls_debug_beam_model_check.argtypes = [C.POINTER(BeamModel), u32, u32]
+    L.ls_trace_scene_beams_sweep.argtypes = [vp, vp, C.POINTER(BeamModel), u32p, u32, vp, u32, u32, vp, vp, vp, vp, u32]
+    L.ls_trace_scene_beams_sweep_host.argtypes = [vp, C.POINTER(BeamModel), u32p, u32, vp, u32, u32, vp, vp, vp, u32p, u32]
+    L.ls_beam_weights_gaussian.argtypes = [f32p, u32, C.c_float, C.c_float, u32p]
+    L.ls_debug_beam_sweep_ray.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, f32p, f32p, f32p]
+    L.ls_debug_beam_echoes_weighted.argtypes = [C.POINTER(BeamModel), u32p, u32, f32p, vp, u32p, u32p]
+    L.ls_debug_beam_sweep_check.argtypes = [C.POINTER(BeamModel), u32p, u32, u32]
     L.ls_geometry_type.argtypes = [vp, C.c_char_p]
     L.ls_debug_dense_hits.argtypes = [vp, f32p, u32p]
     L.ls_debug_trace_bruteforce.argtypes = [vp, f32p, u32p]
@@ -265,6 +273,10 @@ def load() -> C.CDLL:
 
 def _f32p(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _u32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
 
 
 IDENTITY_AFFINE = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32)
@@ -738,6 +750,46 @@ class Tracer:
                                          capacity)
         return -1 if rc == -1 else int(self._check(rc, "ls_trace_scene_beams"))
 
+    def traceBeamsSweep(self, model: BeamModel, weights=None, min_weight: int = 0, col_pose=None, flags: int = 0, points: bool = True,
+                        hits: bool = True, echo: bool = True):
+        """A frame of weighted beams from a moving sensor (ls_trace_scene_beams_sweep_host): traceBeamsHost with `weights` -- None
+        (1 each) or model.n_samples integers in 1..65535 --, the strength threshold `min_weight` and `col_pose` -- None (the sensor at
+        rest) or float32 (H, 12) as for traceSweep; flags: 0 or LS_SWEEP_DESKEW.  -> (rc, k, points uint8[k, 32] or None, hits
+        HIT_DTYPE[k] or None, echo words uint32[k] or None); rc = -1 (no commit, empty scene): no record."""
+        w = None if weights is None else np.ascontiguousarray(weights, np.uint32).reshape(-1)
+        if w is not None and w.shape[0] != model.n_samples:
+            raise ValueError("weights: one per sample of the model")
+        pose = None if col_pose is None else np.ascontiguousarray(col_pose, np.float32)
+        if pose is not None and (pose.ndim != 2 or pose.shape[1] != 12):
+            raise ValueError("col_pose: float32 (H, 12)")
+        cap = model.n_returns * self.getTotalRays()
+        pts = np.zeros((cap, 32), np.uint8) if points else None
+        out = np.zeros(cap, HIT_DTYPE) if hits else None
+        ew = np.zeros(cap, np.uint32) if echo else None
+        k = C.c_uint32(0)
+        rc = self.L.ls_trace_scene_beams_sweep_host(self.h, C.byref(model), None if w is None else _u32p(w), int(min_weight),
+                                                    pose.ctypes.data if pose is not None and pose.size else None, 0 if pose is None else pose.shape[0],
+                                                    flags, pts.ctypes.data if points else None, out.ctypes.data if hits else None,
+                                                    ew.ctypes.data if echo else None, C.byref(k), cap)
+        if rc == -1:
+            return -1, 0, (pts[:0] if points else None), (out[:0] if hits else None), (ew[:0] if echo else None)
+        self._check(rc, "ls_trace_scene_beams_sweep_host")
+        n = int(k.value)
+        return int(rc), n, (pts[:n].copy() if points else None), (out[:n].copy() if hits else None), (ew[:n].copy() if echo else None)
+
+    def traceBeamsSweepDevice(self, model: BeamModel, d_n_points: int, capacity: int, d_points32: int = 0, d_hits: int = 0, d_echo: int = 0,
+                              weights=None, min_weight: int = 0, d_col_pose: int = 0, n_cols: int = 0, flags: int = 0, stream=None) -> int:
+        """ls_trace_scene_beams_sweep on device pointers: traceBeamsDevice with `weights` (host memory: None, or model.n_samples
+        integers in 1..65535, read during the call), `min_weight`, the pose table d_col_pose (0 with n_cols 0: the sensor at rest;
+        else n_cols 48-byte records) and flags (0 or LS_SWEEP_DESKEW); enqueued on `stream`, no wait.  -> 0, or -1 on an empty /
+        uncommitted scene (nothing written)."""
+        w = None if weights is None else np.ascontiguousarray(weights, np.uint32).reshape(-1)
+        if w is not None and w.shape[0] != model.n_samples:
+            raise ValueError("weights: one per sample of the model")
+        rc = self.L.ls_trace_scene_beams_sweep(self.h, stream, C.byref(model), None if w is None else _u32p(w), int(min_weight), d_col_pose or None,
+                                               n_cols, flags, d_points32 or None, d_hits or None, d_echo or None, d_n_points or None, capacity)
+        return -1 if rc == -1 else int(self._check(rc, "ls_trace_scene_beams_sweep"))
+
     # ---- test hooks
     def generateRaysAos(self, d_rays: int | None, d_hits: int | None):
         """LidarDevice::allRaysGPU's two buffers (Ray 32 B, Hit 24 B per ray) in device memory of the caller."""
@@ -891,4 +943,43 @@ def beam_echoes(model: BeamModel, r, hit):
     rc = L.ls_debug_beam_echoes(C.byref(model), _f32p(rr), hh.ctypes.data, out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n))
     if rc != 0:
         raise LidarShooterHipError(f"ls_debug_beam_echoes: status {rc}")
+    return out[:n.value].copy()
+
+
+def beam_weights_gaussian(pattern, sigma_az: float, sigma_el: float):
+    """ls_beam_weights_gaussian: a weight per sample of a pattern, 65535 at the centre of a Gaussian with these standard deviations
+    (the units of the pattern's a and b) -> uint32 (S,), each in 1..65535"""
+    L = load()
+    pat = np.ascontiguousarray(pattern, np.float32).reshape(-1, 3)
+    out = np.zeros(max(pat.shape[0], 1), np.uint32)
+    rc = L.ls_beam_weights_gaussian(_f32p(pat), pat.shape[0], float(sigma_az), float(sigma_el), _u32p(out) if pat.shape[0] <= 64 else None)
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_beam_weights_gaussian: status {rc}")
+    return out[:pat.shape[0]]
+
+
+def beam_sweep_ray(sin_theta, cos_theta, cos_phi, sin_phi, abk, pose12):
+    """ls_debug_beam_sweep_ray: the sub-ray ls_trace_scene_beams_sweep casts for sample (a, b, k) of the ray with these factor-table
+    entries under one pose record, on the host -> float32[8] (origin, tmin, direction, tmax)"""
+    L = load()
+    s, p, out = np.ascontiguousarray(abk, np.float32).reshape(3), np.ascontiguousarray(pose12, np.float32).reshape(12), np.zeros(8, np.float32)
+    rc = L.ls_debug_beam_sweep_ray(float(sin_theta), float(cos_theta), float(cos_phi), float(sin_phi), _f32p(s), _f32p(p), _f32p(out))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_debug_beam_sweep_ray: status {rc}")
+    return out
+
+
+def beam_echoes_weighted(model: BeamModel, weights, min_weight, r, hit):
+    """ls_debug_beam_echoes_weighted: beam_echoes with a weight per sample (None: 1 each) and the strength threshold -> uint32 (n, 3):
+    the bits of r_e, the echo word and the strength W_e, in ascending range"""
+    L = load()
+    rr, hh = np.ascontiguousarray(r, np.float32).reshape(-1), np.ascontiguousarray(hit, np.uint8).reshape(-1)
+    w = None if weights is None else np.ascontiguousarray(weights, np.uint32).reshape(-1)
+    if rr.shape[0] != model.n_samples or hh.shape[0] != model.n_samples or (w is not None and w.shape[0] != model.n_samples):
+        raise ValueError("r, hit, weights: one entry per sample of the model")
+    out, n = np.zeros((3, 3), np.uint32), C.c_uint32(0)
+    rc = L.ls_debug_beam_echoes_weighted(C.byref(model), None if w is None else _u32p(w), int(min_weight), _f32p(rr), hh.ctypes.data, _u32p(out),
+                                         C.byref(n))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_debug_beam_echoes_weighted: status {rc}")
     return out[:n.value].copy()

@@ -128,6 +128,79 @@ LS_BEAM_HD BeamReturns beam_select(unsigned long long starts, uint32_t n_hits, u
 // the intensity of an echo of n members out of S samples: the frame's constant when every sample is in it
 LS_BEAM_HD float beam_intensity(uint32_t n, uint32_t S) { return (64.0f * (float)n) / (float)S; }
 
+// ---- ls_trace_scene_beams_sweep: weighted echoes.  Sample s weighs w_s, an integer in 1..65535; the strength of
+// an echo is W_e, the sum of its members' weights -- exact, independent of the order, at most 64 * 65535 < 2^24 and so exact as a
+// float.  An echo is detectable with n_e >= min_count members AND W_e >= min_weight; STRONGEST is the largest W_e, the nearer of
+// equals.  k_beam_reduce_weighted gives every position of the ascending order a lane and ls_debug_beam_echoes_weighted a loop
+// turn; both run the per-position functions below and then beam_select_weighted.
+
+// the weights as the kernels take them: by value, 128 bytes of kernel arguments; every entry beyond the samples is 0
+struct BeamWeights {
+    uint16_t w[kBeamMaxSamples];
+};
+
+// the end (one past the last position) of the echo that starts at position `at`: the next start, or n_hits
+LS_BEAM_HD uint32_t beam_echo_end(unsigned long long starts, uint32_t n_hits, uint32_t at)
+{
+    const unsigned long long later = starts & ~((2ull << at) - 1ull);   // (at = 63: 2 << 63 is 0, no later position)
+    return later ? beam_ctz64(later) : n_hits;
+}
+
+LS_BEAM_HD bool beam_detectable(uint32_t n, uint32_t W, uint32_t min_count, uint32_t min_weight) { return n >= min_count && W >= min_weight; }
+
+// what the maximum is taken over: the larger W_e wins, among equals the lower position; 0 stands for no echo (W_e >= 1)
+LS_BEAM_HD uint32_t beam_strength(uint32_t W, uint32_t at) { return (W << 6) | (63u - at); }
+LS_BEAM_HD uint32_t beam_strength_where(uint32_t strength) { return 63u - (strength & 63u); }
+
+// beam_select with the detectable echoes and the strongest of them found by the caller.  starts, n_hits: as for beam_select;
+// detectable: the start positions of the detectable echoes; best_at: the start of the strongest one (read only when there is a
+// detectable echo).  The words carry the member count, as beam_select's do; the caller looks W_e up at the word's position.
+LS_BEAM_HD BeamReturns beam_select_weighted(unsigned long long starts, uint32_t n_hits, unsigned long long detectable, uint32_t best_at,
+                                            uint32_t returns)
+{
+    BeamReturns out = {0u, 0u, 0u, 0u};
+    if (!detectable) return out;
+    const uint32_t first_at = beam_ctz64(detectable), last_at = 63u - (uint32_t)__builtin_clzll(detectable);
+    const uint32_t first_n = beam_echo_end(starts, n_hits, first_at) - first_at, last_n = beam_echo_end(starts, n_hits, last_at) - last_at,
+                   best_n = beam_echo_end(starts, n_hits, best_at) - best_at;
+    uint32_t wf = (returns & LS_BEAM_FIRST) ? beam_word(LS_BEAM_FIRST, first_n, first_at) : 0u;
+    uint32_t ws = (returns & LS_BEAM_STRONGEST) ? beam_word(LS_BEAM_STRONGEST, best_n, best_at) : 0u;
+    uint32_t wl = (returns & LS_BEAM_LAST) ? beam_word(LS_BEAM_LAST, last_n, last_at) : 0u;
+    // first_at <= best_at <= last_at: the three are in ascending range; equal positions become one record (as in beam_select)
+    if (wf && ws && first_at == best_at) { wf |= LS_BEAM_STRONGEST; ws = 0u; }
+    if (wl && ws && best_at == last_at) { ws |= LS_BEAM_LAST; wl = 0u; }
+    if (wl && wf && first_at == last_at) { wf |= LS_BEAM_LAST; wl = 0u; }
+    out.n = (wf ? 1u : 0u) + (ws ? 1u : 0u) + (wl ? 1u : 0u);
+    out.w0 = wf ? wf : ws ? ws : wl;
+    out.w1 = wf ? (ws ? ws : wl) : (ws ? wl : 0u);
+    out.w2 = wf && ws ? wl : 0u;
+    return out;
+}
+
+// the intensity of an echo of strength W out of W_total, the sum of all S weights: (64 n) / S with unit weights, beam_intensity's bits
+LS_BEAM_HD float beam_intensity_weighted(uint32_t W, uint32_t W_total) { return (64.0f * (float)W) / (float)W_total; }
+
+// nullptr when the weights (nullptr: every sample weighs 1) of S samples can be used, else what is wrong with them
+inline const char *beam_weights_invalid(const uint32_t *weights, uint32_t S)
+{
+    if (!weights) return nullptr;
+    for (uint32_t s = 0; s < S; ++s)
+        if (weights[s] < 1u || weights[s] > 65535u) return "beam weights: a weight outside 1..65535";
+    return nullptr;
+}
+
+// the weights by value (nullptr: 1 each) and their sum W_total
+inline BeamWeights beam_weights_by_value(const uint32_t *weights, uint32_t S, uint32_t *total)
+{
+    BeamWeights out = {};
+    *total = 0u;
+    for (uint32_t s = 0; s < S; ++s) {
+        out.w[s] = (uint16_t)(weights ? weights[s] : 1u);
+        *total += out.w[s];
+    }
+    return out;
+}
+
 // nullptr when the model can be traced over shard_rays rays into `capacity` records, else what is wrong with it; *status:
 // LS_ERR_INVALID_ARGUMENT, or LS_ERR_OUT_OF_RANGE for more than 2^27 sub-rays (an otherwise valid call)
 inline const char *beam_model_invalid(const ls_beam_model *m, uint32_t shard_rays, uint32_t capacity, int *status)

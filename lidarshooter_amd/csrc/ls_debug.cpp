@@ -192,6 +192,66 @@ int ls_debug_beam_model_check(const ls_beam_model *model, uint32_t shard_rays, u
     return ls::beam_model_invalid(model, shard_rays, capacity, &status) ? status : LS_OK;
 }
 
+// beam_ray, then sweep_ray on its direction: what a lane of k_beam_sweep_rays does
+int ls_debug_beam_sweep_ray(float sin_theta, float cos_theta, float cos_phi, float sin_phi, const float abk[3], const float pose12[12], float ray8[8])
+{
+    if (!abk || !pose12 || !ray8) return LS_ERR_INVALID_ARGUMENT;
+    float b[8];
+    ls::beam_ray(sin_theta, cos_theta, cos_phi, sin_phi, abk[0], abk[1], b);
+    ls::sweep_ray(pose12, b[4], b[5], b[6], ray8);
+    return LS_OK;
+}
+
+// what a group of k_beam_reduce_weighted's lanes does, position by position: the keys in ascending order, the start mask, the prefix
+// sums of the weights, the strength of every echo, the detectable ones and the strongest, beam_select_weighted
+int ls_debug_beam_echoes_weighted(const ls_beam_model *model, const uint32_t *weights, uint32_t min_weight, const float *r, const uint8_t *hit,
+                                  uint32_t *out, uint32_t *n_out)
+{
+    if (!model || !r || !hit || !out || !n_out) return LS_ERR_INVALID_ARGUMENT;
+    const uint32_t S = model->n_samples;
+    if (S < 1u || S > ls::kBeamMaxSamples || !model->returns || (model->returns & ~(uint32_t)(LS_BEAM_FIRST | LS_BEAM_LAST | LS_BEAM_STRONGEST)) ||
+        model->min_count < 1u || model->min_count > S || !(model->echo_separation >= 0.0f) || ls::beam_weights_invalid(weights, S))
+        return LS_ERR_INVALID_ARGUMENT;
+    uint32_t w_total = 0;
+    const ls::BeamWeights wts = ls::beam_weights_by_value(weights, S, &w_total);
+    unsigned long long key[ls::kBeamMaxSamples];
+    for (uint32_t s = 0; s < S; ++s) key[s] = hit[s] ? ls::beam_key(r[s], s) : ls::kBeamMiss;
+    std::sort(key, key + S);
+    unsigned long long starts = 0, detectable = 0;
+    uint32_t n_hits = 0, upto[ls::kBeamMaxSamples], W[ls::kBeamMaxSamples], best = 0;
+    for (uint32_t j = 0; j < S; ++j) {
+        if (ls::beam_starts_echo(j ? key[j - 1] : 0ull, key[j], j, model->echo_separation)) starts |= 1ull << j;
+        if (key[j] != ls::kBeamMiss) ++n_hits;
+        upto[j] = (j ? upto[j - 1] : 0u) + (key[j] != ls::kBeamMiss ? (uint32_t)wts.w[ls::beam_key_sample(key[j])] : 0u);
+    }
+    for (uint32_t j = 0; j < S; ++j) {
+        W[j] = 0;
+        if (!((starts >> j) & 1ull)) continue;
+        const uint32_t end = ls::beam_echo_end(starts, n_hits, j);
+        W[j] = upto[end - 1] - (j ? upto[j - 1] : 0u);
+        if (!ls::beam_detectable(end - j, W[j], model->min_count, min_weight)) continue;
+        detectable |= 1ull << j;
+        best = std::max(best, ls::beam_strength(W[j], j));
+    }
+    const ls::BeamReturns ret = ls::beam_select_weighted(starts, n_hits, detectable, ls::beam_strength_where(best), model->returns);
+    const uint32_t n = ret.n, w[3] = {ret.w0, ret.w1, ret.w2};
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t at = ls::beam_word_where(w[i]);
+        out[3 * i] = (uint32_t)(key[at] >> 8);
+        out[3 * i + 1] = ls::beam_word(w[i] & 7u, ls::beam_word_count(w[i]), ls::beam_key_sample(key[at]));
+        out[3 * i + 2] = W[at];
+    }
+    *n_out = n;
+    return LS_OK;
+}
+
+int ls_debug_beam_sweep_check(const ls_beam_model *model, const uint32_t *weights, uint32_t shard_rays, uint32_t capacity)
+{
+    int status = LS_OK;
+    if (ls::beam_model_invalid(model, shard_rays, capacity, &status)) return status;
+    return ls::beam_weights_invalid(weights, model->n_samples) ? LS_ERR_INVALID_ARGUMENT : LS_OK;
+}
+
 }  // extern "C"
 
 int ls_debug_expand_hits(void *dst_points32, const void *hits8, uint32_t n, const float *sin_theta, const float *cos_theta,

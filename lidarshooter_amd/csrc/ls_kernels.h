@@ -318,6 +318,15 @@ void launch_beam_rays(hipStream_t s, const SensorTables &tb, const BeamPattern &
 void launch_beam_pack(hipStream_t s, const SensorTables &tb, const BeamPattern &pat, uint32_t S, float separation, uint32_t min_count,
                       uint32_t returns, const void *dense, void *blocks, uint32_t *cnt, uint32_t *block_counts, void *points32, void *hits,
                       uint32_t *echo, uint32_t *n_points, uint32_t capacity);
+// ls_trace_scene_beams_sweep (ls_beam.hip): the same two steps with the pose table of ls_trace_scene_sweep (nullptr: the sensor at
+// rest -- launch_beam_rays' records) and a weight per sample (by value as well; w_total: their sum).  wsum: 3 words per beam, the
+// strength W_e of every record of `blocks`.  deskew: the points through their column's pose (nothing changes without a table).
+struct BeamWeights;
+void launch_beam_sweep_rays(hipStream_t s, const SensorTables &tb, const BeamPattern &pat, uint32_t S, const float *pose, void *rays);
+void launch_beam_sweep_pack(hipStream_t s, const SensorTables &tb, const BeamPattern &pat, const BeamWeights &wts, uint32_t w_total, uint32_t S,
+                            float separation, uint32_t min_count, uint32_t min_weight, uint32_t returns, const float *pose, bool deskew,
+                            const void *dense, void *blocks, uint32_t *wsum, uint32_t *cnt, uint32_t *block_counts, void *points32, void *hits,
+                            uint32_t *echo, uint32_t *n_points, uint32_t capacity);
 void launch_rowcount(hipStream_t s, const uint32_t *gid, uint32_t nrays, uint32_t *row_counts, uint32_t *queue_heads = nullptr);   // queue_heads: zeroed for the next k_trace
 // Progress of a synchronous frame whose compact points go straight to pinned host memory (ls_trace_scene_begin /
 // ls_trace_scene_expand): the device publishes, with system-scope release, (1) the frame's hit count as the pack pass

@@ -3,7 +3,9 @@
 //   ls_trace_scene_sweep  a frame whose sensor moves during the turn -- the shard's rays through per-column poses, the closest-hit
 //                         walk over them, an ordered pack (ls_sweep.hip); ls_sweep_poses_constant_twist: a pose table;
 //   ls_trace_scene_beams  a frame of diverging beams -- S sub-rays per ray of the shard, the same walk over them, the echoes of every
-//                         beam and an ordered pack of the selected returns (ls_beam.hip); ls_beam_pattern_rings: a sample pattern.
+//                         beam and an ordered pack of the selected returns (ls_beam.hip); ls_beam_pattern_rings: a sample pattern;
+//   ls_trace_scene_beams_sweep  the two together, with a weight per sample: the sub-rays through per-column poses, the same walk,
+//                         the weighted echoes and their pack (ls_beam.hip); ls_beam_weights_gaussian: a weight per sample.
 #include "ls_internal.h"
 #include "ls_beam.h"
 
@@ -86,6 +88,56 @@ int beams_issue(ls_tracer *tr, hipStream_t s, const ls_beam_model *model, void *
     return LS_OK;
 }
 
+// what both entry points of the beams under a sweep refuse, in this order, before anything touches the device; host memory may have
+// any alignment
+int beams_sweep_check(ls_tracer *tr, const ls_beam_model *model, const uint32_t *weights, const float *col_pose, uint32_t n_cols, uint32_t flags,
+                      const void *points32, const void *hits, const uint32_t *echo, const uint32_t *n_points, uint32_t capacity, bool host)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (!n_points) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null count output");
+    int status = LS_OK;
+    if (const char *why = ls::beam_model_invalid(model, shard_rays(tr), capacity, &status)) return fail(tr, status, why);
+    if (const char *why = ls::beam_weights_invalid(weights, model->n_samples)) return fail(tr, LS_ERR_INVALID_ARGUMENT, why);
+    if (col_pose ? n_cols != tr->H : n_cols != 0u)
+        return fail(tr, LS_ERR_INVALID_ARGUMENT, "one pose per azimuth column of the full raster (LS_INFO_AZIMUTH_COUNT), or no table and n_cols 0");
+    if (flags & ~(uint32_t)LS_SWEEP_DESKEW) return fail(tr, LS_ERR_INVALID_ARGUMENT, "unknown sweep flags");
+    if (!host && (misaligned16(points32, hits) || misaligned(echo, 4) || misaligned(n_points, 4) || misaligned(col_pose, 4)))
+        return fail(tr, LS_ERR_INVALID_ARGUMENT,
+                    "points and hit records must be 16-byte aligned, the echo words, the count and the poses 4-byte aligned");
+    tr->rq.last_built = 0;
+    return uncommitted(tr);   // (nothing is written, the count included)
+}
+
+int beams_sweep_issue(ls_tracer *tr, hipStream_t s, const ls_beam_model *model, const uint32_t *weights, uint32_t min_weight, const float *d_col_pose,
+                      uint32_t flags, void *d_points32, void *d_hits, uint32_t *d_echo, uint32_t *d_n_points, uint32_t capacity)
+{
+    ls_tracer::RayQuery &q = tr->rq;
+    const uint32_t nq = shard_rays(tr), S = model->n_samples, n = nq * S;   // n <= 2^27
+    ls::BeamPattern pat;   // the caller's pattern and weights, read here and now: they travel in the kernel arguments
+    std::memset(static_cast<void *>(&pat), 0, sizeof(pat));
+    for (uint32_t k = 0; k < S; ++k) {
+        pat.a[k] = model->pattern[3 * k];
+        pat.b[k] = model->pattern[3 * k + 1];
+        pat.k[k] = model->pattern[3 * k + 2];
+    }
+    uint32_t w_total = 0;
+    const ls::BeamWeights wts = ls::beam_weights_by_value(weights, S, &w_total);
+    const size_t n_blocks = ls::beam_block_count(nq);
+    int rc;
+    if ((rc = ensure(tr, q.beam_rays, (size_t)n * 32))) return rc;
+    if ((rc = ensure(tr, q.beam_hits, (size_t)n * 16))) return rc;
+    if ((rc = ensure(tr, q.beam_blocks, 3 * (size_t)nq))) return rc;
+    if ((rc = ensure(tr, q.beam_counts, (size_t)nq + n_blocks + 3 * (size_t)nq))) return rc;   // counts, block counts, a strength per record
+    const ls::SensorTables tb = tables(tr);
+    ls::launch_beam_sweep_rays(s, tb, pat, S, d_col_pose, q.beam_rays.p);
+    if ((rc = query_walk(tr, s, q.beam_rays.p, n, q.beam_hits.p, closest_hits()))) return rc;
+    ls::launch_beam_sweep_pack(s, tb, pat, wts, w_total, S, model->echo_separation, model->min_count, min_weight, model->returns, d_col_pose,
+                               (flags & LS_SWEEP_DESKEW) != 0, q.beam_hits.p, q.beam_blocks.p, q.beam_counts.p + nq + n_blocks, q.beam_counts.p,
+                               q.beam_counts.p + nq, d_points32, d_hits, d_echo, d_n_points, capacity);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
 }  // namespace
 
 }  // namespace lsi
@@ -160,6 +212,57 @@ int ls_trace_scene_beams_host(ls_tracer *tr, const ls_beam_model *model, void *p
         return rc;
     return fetch_counted(tr, buf.p + at_n, cap, "ls_trace_scene_beams: more returns than the beams can give",
                          {{points32, buf.p + at_points, 32}, {hits, buf.p + at_hits, 16}, {echo, buf.p + at_echo, 4}}, n_points);
+}
+
+int ls_trace_scene_beams_sweep(ls_tracer *tr, void *hip_stream, const ls_beam_model *model, const uint32_t *weights, uint32_t min_weight,
+                               const float *d_col_pose, uint32_t n_cols, uint32_t flags, void *d_points32, void *d_hits, uint32_t *d_echo,
+                               uint32_t *d_n_points, uint32_t capacity)
+{
+    LS_ENTER_CHECKED(tr, beams_sweep_check(tr, model, weights, d_col_pose, n_cols, flags, d_points32, d_hits, d_echo, d_n_points, capacity, false));
+    const hipStream_t s = stream_of(tr, hip_stream);
+    int rc;
+    if ((rc = query_enter(tr, s)) ||
+        (rc = beams_sweep_issue(tr, s, model, weights, min_weight, d_col_pose, flags, d_points32, d_hits, d_echo, d_n_points, capacity)))
+        return rc;
+    return query_leave(tr, s);
+}
+
+// the poses and the outputs staged in q.io, on the handle's stream; the count comes back first, then as many records
+int ls_trace_scene_beams_sweep_host(ls_tracer *tr, const ls_beam_model *model, const uint32_t *weights, uint32_t min_weight, const float *col_pose,
+                                    uint32_t n_cols, uint32_t flags, void *points32, void *hits, uint32_t *echo, uint32_t *n_points, uint32_t capacity)
+{
+    LS_ENTER_CHECKED(tr, beams_sweep_check(tr, model, weights, col_pose, n_cols, flags, points32, hits, echo, n_points, capacity, true));
+    DevBuf<uint8_t> &buf = tr->rq.io;
+    const hipStream_t s = tr->stream;
+    int rc;
+    if ((rc = query_enter(tr, s))) return rc;
+    const size_t cap = (size_t)__builtin_popcount(model->returns) * shard_rays(tr);   // what the beams can give: <= 3 * 2^27
+    IoPlan io;
+    const size_t at_points = io.add(points32 ? cap * 32 : 0), at_hits = io.add(hits ? cap * 16 : 0), at_pose = io.add((size_t)n_cols * 48),
+                 at_echo = io.add(echo ? cap * 4 : 0), at_n = io.add(4);
+    if ((rc = ensure(tr, buf, io.total()))) return rc;
+    if (col_pose) LS_HIP(hipMemcpyAsync(buf.p + at_pose, col_pose, (size_t)n_cols * 48, hipMemcpyHostToDevice, s));
+    if ((rc = beams_sweep_issue(tr, s, model, weights, min_weight, col_pose ? reinterpret_cast<const float *>(buf.p + at_pose) : nullptr, flags,
+                                points32 ? buf.p + at_points : nullptr, hits ? buf.p + at_hits : nullptr,
+                                echo ? reinterpret_cast<uint32_t *>(buf.p + at_echo) : nullptr, reinterpret_cast<uint32_t *>(buf.p + at_n), (uint32_t)cap)))
+        return rc;
+    return fetch_counted(tr, buf.p + at_n, cap, "ls_trace_scene_beams_sweep: more returns than the beams can give",
+                         {{points32, buf.p + at_points, 32}, {hits, buf.p + at_hits, 16}, {echo, buf.p + at_echo, 4}}, n_points);
+}
+
+// host only: w_s = max(1, round(65535 exp(-((a / sigma_az)^2 + (b / sigma_el)^2) / 2))); double throughout, one rounding
+int ls_beam_weights_gaussian(const float *pattern, uint32_t n_samples, float sigma_az, float sigma_el, uint32_t *weights)
+{
+    if (!pattern || !weights || n_samples < 1u || n_samples > ls::kBeamMaxSamples) return LS_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(sigma_az) || !std::isfinite(sigma_el) || !(sigma_az > 0.0f) || !(sigma_el > 0.0f)) return LS_ERR_INVALID_ARGUMENT;
+    for (uint32_t k = 0; k < 3u * n_samples; ++k)
+        if (!std::isfinite(pattern[k])) return LS_ERR_INVALID_ARGUMENT;
+    for (uint32_t s = 0; s < n_samples; ++s) {
+        const double a = (double)pattern[3 * s] / (double)sigma_az, b = (double)pattern[3 * s + 1] / (double)sigma_el;
+        const double w = std::round(65535.0 * std::exp(-0.5 * (a * a + b * b)));
+        weights[s] = w < 1.0 ? 1u : (uint32_t)w;
+    }
+    return LS_OK;
 }
 
 // host only: the centre sample, then ring after ring; double throughout, one rounding per entry (k from the rounded a and b)

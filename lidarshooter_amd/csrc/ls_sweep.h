@@ -9,6 +9,9 @@
 // leaves a non-finite origin or direction -- k_trace_rays calls such a ray a miss.
 #pragma once
 
+#include <stddef.h>
+#include <stdint.h>
+
 #if defined(__HIPCC__)
 #define LS_SWEEP_HD __host__ __device__ __forceinline__
 #else
@@ -48,5 +51,24 @@ LS_SWEEP_HD void sweep_point(const float *p, float dx, float dy, float dz, float
     out3[1] = p[7] + t * d[1];
     out3[2] = p[11] + t * d[2];
 }
+
+#if defined(__HIPCC__)
+// the 12 floats of column h's record (k_sweep_rays, k_sweep_pack; k_beam_sweep_rays, k_beam_sweep_pack); aligned16: the table's
+// address allows three 16-byte loads per record
+__device__ __forceinline__ void load_pose(const float *__restrict__ pose, uint32_t h, bool aligned16, float *p)
+{
+    const float *src = pose + 12 * (size_t)h;
+    if (aligned16) {
+        const float4 a = reinterpret_cast<const float4 *>(src)[0], b = reinterpret_cast<const float4 *>(src)[1],
+                     c = reinterpret_cast<const float4 *>(src)[2];
+        p[0] = a.x; p[1] = a.y; p[2] = a.z; p[3] = a.w;
+        p[4] = b.x; p[5] = b.y; p[6] = b.z; p[7] = b.w;
+        p[8] = c.x; p[9] = c.y; p[10] = c.z; p[11] = c.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) p[k] = src[k];
+    }
+}
+#endif
 
 }  // namespace ls

@@ -24,22 +24,6 @@ namespace {
 
 constexpr uint32_t kSweepRows = kBlock / 64;   // rings per workgroup of k_sweep_rays: one per wave
 
-// the 12 floats of column h's record; aligned16: the table's address allows three 16-byte loads per record
-__device__ __forceinline__ void load_pose(const float *__restrict__ pose, uint32_t h, bool aligned16, float *p)
-{
-    const float *src = pose + 12 * (size_t)h;
-    if (aligned16) {
-        const float4 a = reinterpret_cast<const float4 *>(src)[0], b = reinterpret_cast<const float4 *>(src)[1],
-                     c = reinterpret_cast<const float4 *>(src)[2];
-        p[0] = a.x; p[1] = a.y; p[2] = a.z; p[3] = a.w;
-        p[4] = b.x; p[5] = b.y; p[6] = b.z; p[7] = b.w;
-        p[8] = c.x; p[9] = c.y; p[10] = c.z; p[11] = c.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) p[k] = src[k];
-    }
-}
-
 __global__ __launch_bounds__(kBlock) void k_sweep_rays(SensorTables tb, const float *__restrict__ pose, uint32_t aligned16,
                                                        float4 *__restrict__ rays, float4 *__restrict__ rays_out)
 {

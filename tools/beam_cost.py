@@ -3,7 +3,10 @@ the SYN-128 x 4096 raster with S = 8 samples per beam, against ls_trace_rays alo
 (restated on the host from the factor tables, the arithmetic of csrc/ls_beam.h in numpy float32) -- what the ray generation, the
 echo reduction and the ordered pack add to the walk.  Both are timed with device events on a stream of their own, in alternating
 rounds of the same length in one run, after a warm-up that also builds the query hierarchy.  Prints both times per call and
-their ratio.  For kernel times run it under the profiler in a run of its own:
+their ratio.  ls_trace_scene_beams_sweep (k_beam_sweep_rays, the walk, k_beam_reduce_weighted, k_beam_count + k_beam_sweep_pack)
+runs in the same rounds, on the same model, in three legs: at rest with unit weights (what the weighted reduce and pack cost against
+ls_trace_scene_beams), with a constant-twist pose table (unit weights), and with Gaussian weights (at rest).  For kernel times run
+it under the profiler in a run of its own:
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/beam_cost.py
 usage: python tools/beam_cost.py [--rounds N] [--calls M] [--samples S]
 """
@@ -74,20 +77,34 @@ def main():
     def rays_alone():
         assert tr.traceRaysDevice(d_rays.data_ptr(), n * S, d_dense.data_ptr(), s.cuda_stream) == 0
 
+    # the legs of ls_trace_scene_beams_sweep: a carrier at about 10 m/s turning at about 1 rad/s, one turn in 0.1 s; sigma = the half-angle
+    d_pose = torch.from_numpy(capi.sweep_poses_constant_twist((8.0, -5.0, 0.5), (0.1, -0.15, 1.0), 0.0, 0.1 / H, H)).to("cuda:0")
+    gauss = capi.beam_weights_gaussian(pat, 0.0015, 0.0015)
+
+    def sweep_leg(weights=None, pose=0):
+        def run():
+            assert tr.traceBeamsSweepDevice(model, d_n.data_ptr(), cap, d_points.data_ptr(), d_hits.data_ptr(), d_echo.data_ptr(), weights=weights,
+                                            d_col_pose=pose, n_cols=H if pose else 0, stream=s.cuda_stream) == 0
+        return run
+
+    legs = [("ls_trace_scene_beams", beams), ("ls_trace_rays alone", rays_alone), ("beams_sweep at rest, unit weights", sweep_leg()),
+            ("beams_sweep under a twist table", sweep_leg(pose=d_pose.data_ptr())), ("beams_sweep with Gaussian weights", sweep_leg(weights=gauss))]
+
     torch.cuda.synchronize()   # (the buffers' fills run on torch's stream: done before the handle's work starts)
-    for _ in range(6):         # the first call builds the hierarchy
-        beams()
-        rays_alone()
+    for _ in range(6):         # the first call builds the hierarchy; every leg is warmed up
+        for _, fn in legs[2:] + legs[:2]:
+            fn()
     torch.cuda.synchronize()
-    k = int(d_n[0].item())
+    k = int(d_n[0].item())   # (of the last warm-up call: ls_trace_scene_beams)
     dense = d_dense.cpu().numpy().view(np.uint32).reshape(n, S, 4)
     sub_hits = int(np.count_nonzero(dense[:, :, 1] != 0xFFFFFFFF))
     # the same sub-rays: every FIRST record is the nearest detectable echo of a beam with at least two sub-hits
     firsts = int(np.count_nonzero(d_echo.cpu().numpy().view(np.uint32)[:k] & 1))
     assert 0 < firsts <= int(np.count_nonzero((dense[:, :, 1] != 0xFFFFFFFF).sum(1) >= 2)), (firsts, k)
-    t_beams, t_rays = [], []
+    times = [[] for _ in legs]
+    t_beams, t_rays = times[0], times[1]
     for _ in range(a.rounds):
-        for fn, acc in ((beams, t_beams), (rays_alone, t_rays)):
+        for (_, fn), acc in zip(legs, times):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(s)
             for _ in range(a.calls):
@@ -100,9 +117,14 @@ def main():
     print(f"ls_trace_scene_beams: median {be:.1f} us per call (rounds {min(t_beams):.1f} .. {max(t_beams):.1f})")
     print(f"ls_trace_rays alone:  median {ra:.1f} us per call (rounds {min(t_rays):.1f} .. {max(t_rays):.1f})")
     print(f"ratio {be / ra:.3f}: ray generation + reduction + count + pack add {be - ra:.1f} us to the walk")
+    sweep = {}
+    for (name, _), acc, key in zip(legs[2:], times[2:], ("sweep_rest", "sweep_twist", "sweep_gauss")):
+        med = float(np.median(acc))
+        print(f"{name}: median {med:.1f} us per call (rounds {min(acc):.1f} .. {max(acc):.1f}), {med / be:.3f} x ls_trace_scene_beams")
+        sweep[key + "_us"], sweep[key + "_rounds_us"] = round(med, 2), [round(x, 2) for x in acc]
     print(json.dumps({"tool": "beam_cost", "beams": n, "samples": S, "sub_hits": sub_hits, "returns": k, "beams_us": round(be, 2),
                       "trace_rays_us": round(ra, 2), "ratio": round(be / ra, 4), "beams_rounds_us": [round(x, 2) for x in t_beams],
-                      "rays_rounds_us": [round(x, 2) for x in t_rays]}))
+                      "rays_rounds_us": [round(x, 2) for x in t_rays], **sweep}))
     tr.close()
 
 
