@@ -781,7 +781,7 @@ int ls_beam_pattern_rings(float half_angle_az, float half_angle_el, uint32_t n_r
  * and flags, alignment, then the commit (-1 with no commit or an empty scene writes nothing, the count included).  The call uses
  * the scratch of ls_trace_scene_beams on the handle and 12 more bytes per ray; calls on one handle use it one after the other.
  * Not offered: these echoes through ls_apply_return_model (their t is still the reported range); a rays_out; a call of the ITracer
- * adapter; geometries that move during the turn. */
+ * adapter; geometries that move during the turn (without beams: ls_trace_scene_sweep_moving below). */
 int ls_trace_scene_beams_sweep(ls_tracer *tr, void *hip_stream, const ls_beam_model *model,
                                const uint32_t *weights, uint32_t min_weight,
                                const float *d_col_pose, uint32_t n_cols, uint32_t flags,
@@ -798,6 +798,64 @@ int ls_trace_scene_beams_sweep_host(ls_tracer *tr, const ls_beam_model *model,
  * LS_ERR_INVALID_ARGUMENT for NULL pointers, n_samples outside 1..64, non-finite pattern entries, sigmas that are non-finite or
  * <= 0. */
 int ls_beam_weights_gaussian(const float *pattern, uint32_t n_samples, float sigma_az, float sigma_el, uint32_t *weights);
+
+/* ---- sweep frames with GEOMETRIES that move during the turn.  A car that crosses the field of view during the 0.1 s turn is
+ * sheared, stretched or compressed in the real cloud, for a sensor at rest as for a moving one; ls_trace_scene_sweep freezes every
+ * geometry at its committed pose.  Here a geometry may have a rigid displacement of its own per azimuth column.  Nothing is
+ * re-posed and no hierarchy is touched: a moved geometry is a moved ray -- the walk carries the ray through the inverse of the
+ * geometry's displacement and tests it against the geometry where it was committed. */
+typedef struct ls_geometry_motion {
+    uint32_t geom;             /* geomID (ls_add_geometry / ls_geometry_id) */
+    uint32_t reserved;         /* must be 0 */
+    const float *col_motion;   /* H records of 12 floats, row-major [Q | c]; DEVICE memory for the device call, host memory for _host */
+} ls_geometry_motion;
+
+/*   d_col_pose, n_cols: the sensor's pose table of ls_trace_scene_sweep, or NULL with n_cols 0: the sensor is at rest (the nominal
+ *            rays from the origin; LS_SWEEP_DESKEW then changes nothing).
+ *   motions: HOST memory, n_motions entries, read during the call; geometries not named are at rest.  Each names a geometry of the
+ *            committed scene once and gives its table: LS_INFO_AZIMUTH_COUNT records whatever the shard, 4-byte aligned, in device
+ *            memory, never read on the host.  Record h is the rigid displacement of the geometry at the moment the GLOBAL azimuth
+ *            column h fires, relative to where it was committed, expressed in the handle's sensor frame as the scene was committed
+ *            (the frame the sensor poses use): x_h = Q_h x_0 + c_h, Q[i][j] at 4 i + j, c[i] at 4 i + 3.  Q is taken to be a
+ *            rotation: its transpose serves as its inverse, and nothing checks that.  A caller whose motion is in the world frame
+ *            creates the handle with Rinv = I, t = 0, as for caller rays.
+ *   rays:    with (o, d) the ray ls_trace_scene_sweep casts for (v, h), geometry g sees e_i = o_i - c_i, o_g,i = (Q[0][i] e_0 +
+ *            Q[1][i] e_1) + Q[2][i] e_2, d_g,i = (Q[0][i] d_0 + Q[1][i] d_1) + Q[2][i] d_2, tmin 0, tmax 1e16, in float32 with no
+ *            fused multiply-add: ONE operation sequence (csrc/ls_motion.h; ls_debug_motion_ray in lidarshooter_hip_debug.h runs it
+ *            on the host).  An identity record gives the ray back.  A record with a non-finite entry, or one that yields a zero
+ *            d_g, makes THAT geometry invisible to THAT column; every other geometry is still tested.
+ *   hits:    for every ray, every geometry g of the committed scene contributes what ls_trace_rays would return for the record
+ *            (o_g, 0, d_g, 1e16) -- (o, 0, d, 1e16) for a geometry at rest -- against a scene that holds g alone at its committed
+ *            pose; the answer is the contribution with the smallest t, the lowest (geomID, primID) among equals.  t is along the
+ *            direction as given, as everywhere else.
+ *   outputs: those of ls_trace_scene_sweep -- d_points32, d_hits, d_n_points, capacity, the order of the records, NULL outputs --:
+ *            by default xyz = t * d with the nominal d and no sum, what the sensor reports; with LS_SWEEP_DESKEW xyz = o_h + t *
+ *            d'_h per axis: where the surface was, in the frame-start sensor frame, at the instant it was hit.
+ * With n_motions 0 the call returns ls_trace_scene_sweep's bytes, with identity tables for every geometry too; with no motions and
+ * no pose table ls_trace_scene's points, records and count.  LS_ERR_INVALID_ARGUMENT before any device call, in this order: a frame
+ * graph is open; a NULL count; a pose table whose n_cols is not H, or n_cols != 0 without one; unknown flag bits; motions NULL with
+ * n_motions > 0; a NULL table; a non-zero reserved; n_motions above ls_geometry_count() or the same geom twice; misaligned pointers;
+ * a capacity below the shard's ls_total_rays().  Then the commit state (-1 with no commit or an empty scene writes nothing, the
+ * count included), then LS_ERR_UNKNOWN_GEOMETRY for a geom that is not in the committed scene.  Stream order, the shard handling,
+ * LS_INFO_RAY_QUERY_BUILT and the query hierarchies are those of ls_trace_scene_sweep, whose scratch the call uses: a commit after
+ * which only poses changed still builds nothing.
+ * Not offered: a d_rays_out; these records through ls_hit_attributes / ls_apply_return_model (their exact test would need the
+ * geometry's own ray); beams; deforming meshes; a call of the ITracer adapter. */
+int ls_trace_scene_sweep_moving(ls_tracer *tr, void *hip_stream, const float *d_col_pose, uint32_t n_cols,
+                                const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags,
+                                void *d_points32, void *d_hits, uint32_t *d_n_points, uint32_t capacity);
+/* The same with host memory (pageable) in and out, on the handle's stream: the pose table and the motion tables are copied to the
+ * device; returns when the outputs are filled (*n_points records of each). */
+int ls_trace_scene_sweep_moving_host(ls_tracer *tr, const float *col_pose, uint32_t n_cols,
+                                     const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags,
+                                     void *points32, void *hits, uint32_t *n_points, uint32_t capacity);
+
+/* Motion table of a body at a constant twist (host only, no handle, no device): tau_h = t0 + h * dt; Q_h = Rodrigues' formula for
+ * the rotation ang_vel * tau_h, c_h = pivot - Q_h pivot + lin_vel * tau_h -- a body turning about `pivot` while it drives on;
+ * evaluated in double, rounded once to float32.  With pivot = 0 the bytes of ls_sweep_poses_constant_twist.  col_motion: n_cols
+ * records of 12 floats.  LS_ERR_INVALID_ARGUMENT for NULL pointers or non-finite inputs. */
+int ls_motion_constant_twist(const float lin_vel[3], const float ang_vel[3], const float pivot[3], double t0, double dt,
+                             uint32_t n_cols, float *col_motion);
 
 #ifdef __cplusplus
 }

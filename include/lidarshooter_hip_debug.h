@@ -100,6 +100,12 @@ int ls_debug_beam_echoes_weighted(const ls_beam_model *model, const uint32_t *we
  * shard_rays rays, with this capacity and otherwise valid arguments (no device, no handle) */
 int ls_debug_beam_sweep_check(const ls_beam_model *model, const uint32_t *weights, uint32_t shard_rays, uint32_t capacity);
 
+
+/* the ray a moving geometry sees (ls_trace_scene_sweep_moving): the 32-byte ray record ray8_in through the inverse of one motion
+ * record (12 floats, [Q | c] row-major), on the host (no device, no handle): the float32 operation sequence k_trace_rays_moving
+ * runs (csrc/ls_motion.h) -> origin Q^T (o - c), tmin 0, direction Q^T d, tmax 1e16 */
+int ls_debug_motion_ray(const float ray8_in[8], const float motion12[12], float ray8_out[8]);
+
 #ifdef __cplusplus
 }
 #endif

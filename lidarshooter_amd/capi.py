@@ -57,13 +57,14 @@ SYMBOLS = (
     "ls_trace_scene_sweep", "ls_trace_scene_sweep_host", "ls_sweep_poses_constant_twist",
     "ls_trace_scene_beams", "ls_trace_scene_beams_host", "ls_beam_pattern_rings",
     "ls_trace_scene_beams_sweep", "ls_trace_scene_beams_sweep_host", "ls_beam_weights_gaussian",
+    "ls_trace_scene_sweep_moving", "ls_trace_scene_sweep_moving_host", "ls_motion_constant_twist",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
 DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_scene_size", "ls_debug_download_scene",
                  "ls_debug_download_bvh", "ls_debug_sort_pairs", "ls_debug_expand_hits", "ls_debug_closest_on_triangle",
                  "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model", "ls_debug_sweep_ray",
                  "ls_debug_beam_ray", "ls_debug_beam_echoes", "ls_debug_beam_model_check",
-                 "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check")
+                 "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check", "ls_debug_motion_ray")
 
 
 class SensorDesc(C.Structure):
@@ -101,6 +102,12 @@ class BeamModel(C.Structure):
     @property
     def n_returns(self) -> int:
         return bin(self.returns & 7).count("1")
+
+
+class GeometryMotion(C.Structure):
+    """ls_geometry_motion: the geomID of a geometry that moves during the turn and its table of H records [Q | c] (an address:
+    device memory for the device call, host memory for the host variant)"""
+    _fields_ = [("geom", C.c_uint32), ("reserved", C.c_uint32), ("col_motion", C.c_void_p)]
 
 
 class ReturnModel(C.Structure):
@@ -259,6 +266,10 @@ def load() -> C.CDLL:
     L.ls_debug_beam_sweep_ray.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, f32p, f32p, f32p]
     L.ls_debug_beam_echoes_weighted.argtypes = [C.POINTER(BeamModel), u32p, u32, f32p, vp, u32p, u32p]
     L.ls_debug_beam_sweep_check.argtypes = [C.POINTER(BeamModel), u32p, u32, u32]
+    L.ls_trace_scene_sweep_moving.argtypes = [vp, vp, vp, u32, C.POINTER(GeometryMotion), u32, u32, vp, vp, vp, u32]
+    L.ls_trace_scene_sweep_moving_host.argtypes = [vp, vp, u32, C.POINTER(GeometryMotion), u32, u32, vp, vp, u32p, u32]
+    L.ls_motion_constant_twist.argtypes = [f32p, f32p, f32p, C.c_double, C.c_double, u32, f32p]
+    L.ls_debug_motion_ray.argtypes = [f32p, f32p, f32p]
     L.ls_geometry_type.argtypes = [vp, C.c_char_p]
     L.ls_debug_dense_hits.argtypes = [vp, f32p, u32p]
     L.ls_debug_trace_bruteforce.argtypes = [vp, f32p, u32p]
@@ -723,6 +734,46 @@ class Tracer:
                                          capacity, d_rays_out or None)
         return -1 if rc == -1 else int(self._check(rc, "ls_trace_scene_sweep"))
 
+    def traceSweepMoving(self, col_pose, motions, flags: int = 0, points: bool = True, hits: bool = True):
+        """A sweep frame whose geometries move during the turn (ls_trace_scene_sweep_moving_host): `col_pose` as in traceSweep, or
+        None: the sensor at rest; `motions` a dict geomID -> float32 (H, 12) table [Q | c] row-major, the rigid displacement of that
+        geometry when azimuth column h fires, relative to where it was committed, in the frame-start sensor frame (geometries not
+        named are at rest).  -> (rc, k, points uint8[k, 32] or None, hits HIT_DTYPE[k] or None); rc = -1: no record."""
+        pose = None if col_pose is None else np.ascontiguousarray(col_pose, np.float32)
+        if pose is not None and (pose.ndim != 2 or pose.shape[1] != 12):
+            raise ValueError("col_pose: float32 (H, 12)")
+        tabs = {int(g): np.ascontiguousarray(t, np.float32) for g, t in dict(motions).items()}
+        H = self.info(LS_INFO_AZIMUTH_COUNT)
+        if any(t.shape != (H, 12) for t in tabs.values()):
+            raise ValueError("motions: float32 (H, 12) per geometry")
+        arr = (GeometryMotion * max(1, len(tabs)))()
+        for m, (g, t) in zip(arr, tabs.items()):
+            m.geom, m.reserved, m.col_motion = g, 0, t.ctypes.data
+        n = self.getTotalRays()
+        pts = np.zeros((n, 32), np.uint8) if points else None
+        out = np.zeros(n, HIT_DTYPE) if hits else None
+        k = C.c_uint32(0)
+        rc = self.L.ls_trace_scene_sweep_moving_host(self.h, None if pose is None else pose.ctypes.data, 0 if pose is None else pose.shape[0],
+                                                     arr if tabs else None, len(tabs), flags, pts.ctypes.data if points else None,
+                                                     out.ctypes.data if hits else None, C.byref(k), n)
+        if rc == -1:
+            return -1, 0, (pts[:0] if points else None), (out[:0] if hits else None)
+        self._check(rc, "ls_trace_scene_sweep_moving_host")
+        return int(rc), int(k.value), (pts[:k.value].copy() if points else None), (out[:k.value].copy() if hits else None)
+
+    def traceSweepMovingDevice(self, d_col_pose: int, n_cols: int, motions, d_n_points: int, capacity: int, d_points32: int = 0,
+                               d_hits: int = 0, flags: int = 0, stream=None) -> int:
+        """ls_trace_scene_sweep_moving on device pointers: traceSweepDevice (d_col_pose 0 with n_cols 0: the sensor at rest) with
+        `motions`, a dict geomID -> device address of that geometry's H 48-byte records; enqueued on `stream` (a hipStream_t as an
+        int, None: the handle's), no wait.  -> 0, or -1 on an empty / uncommitted scene (nothing written)."""
+        items = list(dict(motions).items())
+        arr = (GeometryMotion * max(1, len(items)))()
+        for m, (g, addr) in zip(arr, items):
+            m.geom, m.reserved, m.col_motion = int(g), 0, int(addr)
+        rc = self.L.ls_trace_scene_sweep_moving(self.h, stream, d_col_pose or None, n_cols, arr if items else None, len(items), flags,
+                                                d_points32 or None, d_hits or None, d_n_points or None, capacity)
+        return -1 if rc == -1 else int(self._check(rc, "ls_trace_scene_sweep_moving"))
+
     def traceBeamsHost(self, model: BeamModel, points: bool = True, hits: bool = True, echo: bool = True):
         """A frame of diverging beams with multi-echo returns (ls_trace_scene_beams_host): model.n_samples sub-rays per ray of the
         shard, the returns of every beam in ascending ray index and range.  An output asked for with False comes back None.
@@ -906,6 +957,30 @@ def sweep_ray(d, pose12):
     rc = L.ls_debug_sweep_ray(_f32p(dd), _f32p(p), _f32p(out))
     if rc != 0:
         raise LidarShooterHipError(f"ls_debug_sweep_ray: status {rc}")
+    return out
+
+
+def motion_constant_twist(lin_vel, ang_vel, pivot, t0: float, dt: float, n_cols: int):
+    """ls_motion_constant_twist: the motion table of a body that turns about `pivot` while it drives on -> float32 (n_cols, 12),
+    [Q | c] row-major, tau_h = t0 + h dt"""
+    L = load()
+    lin, ang, piv = (np.ascontiguousarray(x, np.float32).reshape(3) for x in (lin_vel, ang_vel, pivot))
+    out = np.zeros((int(n_cols), 12), np.float32)
+    rc = L.ls_motion_constant_twist(_f32p(lin), _f32p(ang), _f32p(piv), float(t0), float(dt), int(n_cols), _f32p(out))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_motion_constant_twist: status {rc}")
+    return out
+
+
+def motion_ray(ray8, motion12):
+    """ls_debug_motion_ray: the ray a geometry under one motion record sees of the ray record ray8, on the host -> float32[8]
+    (origin Q^T (o - c), tmin 0, direction Q^T d, tmax 1e16)"""
+    L = load()
+    r, p = np.ascontiguousarray(ray8, np.float32).reshape(8), np.ascontiguousarray(motion12, np.float32).reshape(12)
+    out = np.zeros(8, np.float32)
+    rc = L.ls_debug_motion_ray(_f32p(r), _f32p(p), _f32p(out))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_debug_motion_ray: status {rc}")
     return out
 
 

@@ -6,6 +6,7 @@
 #include "ls_hit_attr.h"
 #include "ls_return_model.h"
 #include "ls_sweep.h"
+#include "ls_motion.h"
 #include "ls_beam.h"
 
 #include <algorithm>
@@ -148,6 +149,13 @@ int ls_debug_sweep_ray(const float d[3], const float pose12[12], float ray8[8])
 {
     if (!d || !pose12 || !ray8) return LS_ERR_INVALID_ARGUMENT;
     ls::sweep_ray(pose12, d[0], d[1], d[2], ray8);
+    return LS_OK;
+}
+
+int ls_debug_motion_ray(const float ray8_in[8], const float motion12[12], float ray8_out[8])
+{
+    if (!ray8_in || !motion12 || !ray8_out) return LS_ERR_INVALID_ARGUMENT;
+    ls::motion_ray(motion12, ray8_in, ray8_out);
     return LS_OK;
 }
 

@@ -8,7 +8,8 @@
 //   ls_query.cpp     ls_trace_rays / ls_occluded_rays / ls_closest_points: the query set of per-geometry hierarchies (built lazily),
 //                    batches of geometries per launch; what every query entry point shares (stream hand-over, staging, read-back)
 //   ls_gather.cpp    ls_hit_attributes: the per-geomID table of its gather kernel; ls_apply_return_model: the same table, its scratch
-//   ls_scan.cpp      ls_trace_scene_sweep, ls_trace_scene_beams: their scratch around the queries' walk (ls_sweep.hip, ls_beam.hip)
+//   ls_scan.cpp      ls_trace_scene_sweep, ls_trace_scene_beams, ls_trace_scene_sweep_moving: their scratch around the queries' walk
+//                    (ls_sweep.hip, ls_beam.hip, ls_moving.hip)
 //   ls_host_pool.cpp worker threads for host-side copies, point expansion
 //   ls_debug.cpp     include/lidarshooter_hip_debug.h (tests and bench.py only)
 #pragma once
@@ -453,7 +454,8 @@ inline bool misaligned16(const P *...p) { return (misaligned(p, 16) || ...); }
 struct RayQueryKind;
 const RayQueryKind &closest_hits();   // ls_trace_rays' kind: the walk of the frames in ls_scan.cpp
 int query_enter(ls_tracer *tr, hipStream_t s);
-int query_walk(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out, const RayQueryKind &kind);
+int query_walk(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out, const RayQueryKind &kind,
+               const float *const *motion = nullptr);   // motion: ls_trace_scene_sweep_moving's tables, one per layout entry
 int query_leave(ls_tracer *tr, hipStream_t s);
 // the host-memory variants stage in RayQuery::io: add() every piece (each starts 16-byte aligned), ensure total(), then form pointers
 struct IoPlan {

@@ -260,6 +260,15 @@ struct RayBatch {
 };
 void launch_trace_rays(hipStream_t s, uint32_t grid_blocks, const void *rays, uint32_t n, const RayBatch &batch, const WideNode *wide,
                        const TriRecord *records, uint32_t leaf_size, void *out, uint32_t *counter, uint32_t *spill);
+// ls_trace_scene_sweep_moving (ls_moving.hip): launch_trace_rays' walk over the shard's sweep records (shard-local ray q of column
+// az0 + q % naz) with geometries that move during the turn: geometry k of the batch sees the ray through the inverse of record h
+// of table[k] (H records of 12 floats, [Q | c] row-major, device memory, 4-byte aligned; nullptr: at rest) -- ls_motion.h
+struct MotionBatch {
+    const float *table[kGeomsPerLaunch];
+    uint32_t az0, naz;
+};
+void launch_trace_rays_moving(hipStream_t s, uint32_t grid_blocks, const void *rays, uint32_t n, const RayBatch &batch, const MotionBatch &mb,
+                              const WideNode *wide, const TriRecord *records, uint32_t leaf_size, void *out, uint32_t *counter, uint32_t *spill);
 // ls_occluded_rays: the same walk stopping at a ray's first hit; out = n bytes, 1 = occluded (the first launch writes every byte,
 // a later one only the rays it finds occluded)
 void launch_occluded_rays(hipStream_t s, uint32_t grid_blocks, const void *rays, uint32_t n, const RayBatch &batch, const WideNode *wide,

@@ -264,7 +264,9 @@ const RayQueryKind &closest_hits() { return kClosest; }
 // ls_scan.cpp, which put a pass of their own on either side of the walk; the gathers of ls_gather.cpp, which have no walk):
 //   query_enter  after everything already issued on the handle -- its frames in flight, its mesh copies -- on stream s (the one
 //                flush_pipeline of a call);
-//   query_walk   the query set brought up to date, the counters, one launch per batch of kGeomsPerLaunch geometries;
+//   query_walk   the query set brought up to date, the counters, one launch per batch of kGeomsPerLaunch geometries (motion: one
+//                table pointer per layout entry, nullptr for a geometry at rest -- the closest-hit walk of ls_moving.hip over
+//                the shard's sweep records instead of the kind's own);
 //   query_leave  what the handle issues next (mesh copies, commits, the next query) comes after this query; frames of the
 //                three-stream rotation that need none of that do not wait for it.
 int query_enter(ls_tracer *tr, hipStream_t s)
@@ -281,7 +283,7 @@ int query_enter(ls_tracer *tr, hipStream_t s)
     return LS_OK;
 }
 
-int query_walk(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out, const RayQueryKind &kind)
+int query_walk(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out, const RayQueryKind &kind, const float *const *motion)
 {
     ls_tracer::RayQuery &q = tr->rq;
     int rc;
@@ -305,6 +307,16 @@ int query_walk(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, voi
         for (size_t i = first; i < last; ++i) {
             ray_geom(tr, i, *order[i], sensor_frame[i], batch.g[i - first]);
             if (kind.points) point_margins(tr, i, *order[i], sensor_frame[i], batch.g[i - first], pm, i - first);
+        }
+        if (motion) {   // the sweep's records against geometries in motion: the tables follow their geometries into the batch
+            ls::MotionBatch mb;
+            std::memset(static_cast<void *>(&mb), 0, sizeof(mb));
+            for (size_t i = first; i < last; ++i) mb.table[i - first] = motion[i];
+            mb.az0 = tr->az0;
+            mb.naz = tr->naz;
+            ls::launch_trace_rays_moving(s, tr->trace_blocks, d_rays, n, batch, mb, q.wide_nodes.p, q.records.p, q.leaf, d_out, q.d_counters + b,
+                                         q.spill.p);
+            continue;
         }
         kind.launch(s, tr->trace_blocks, d_rays, n, batch, pm, q.wide_nodes.p, q.records.p, q.leaf, d_out, q.d_counters + b, q.spill.p);
     }

@@ -5,10 +5,14 @@
 //   ls_trace_scene_beams  a frame of diverging beams -- S sub-rays per ray of the shard, the same walk over them, the echoes of every
 //                         beam and an ordered pack of the selected returns (ls_beam.hip); ls_beam_pattern_rings: a sample pattern;
 //   ls_trace_scene_beams_sweep  the two together, with a weight per sample: the sub-rays through per-column poses, the same walk,
-//                         the weighted echoes and their pack (ls_beam.hip); ls_beam_weights_gaussian: a weight per sample.
+//                         the weighted echoes and their pack (ls_beam.hip); ls_beam_weights_gaussian: a weight per sample;
+//   ls_trace_scene_sweep_moving  the sweep with geometries that move during the turn: the sweep's rays and pack around the walk that
+//                         carries each ray through the inverse of a geometry's motion (ls_moving.hip); ls_motion_constant_twist: a
+//                         motion table.
 #include "ls_internal.h"
 #include "ls_beam.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace lsi {
@@ -136,6 +140,113 @@ int beams_sweep_issue(ls_tracer *tr, hipStream_t s, const ls_beam_model *model, 
                                q.beam_counts.p + nq, d_points32, d_hits, d_echo, d_n_points, capacity);
     LS_HIP(hipGetLastError());
     return LS_OK;
+}
+
+// what both entry points of the sweep over moving geometries refuse, in this order; host memory may have any alignment.  On LS_OK
+// table[i] is the motion table of layout entry i (nullptr: at rest)
+int moving_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags,
+                 const void *points32, const void *hits, const uint32_t *n_points, uint32_t capacity, bool host, std::vector<const float *> &table)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (!n_points) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null count output");
+    if (col_pose ? n_cols != tr->H : n_cols != 0u)
+        return fail(tr, LS_ERR_INVALID_ARGUMENT, "one pose per azimuth column of the full raster (LS_INFO_AZIMUTH_COUNT), or no table and n_cols 0");
+    if (flags & ~(uint32_t)LS_SWEEP_DESKEW) return fail(tr, LS_ERR_INVALID_ARGUMENT, "unknown sweep flags");
+    if (n_motions && !motions) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null motions with n_motions > 0");
+    for (uint32_t k = 0; k < n_motions; ++k)
+        if (!motions[k].col_motion) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a motion without a table");
+    for (uint32_t k = 0; k < n_motions; ++k)
+        if (motions[k].reserved) return fail(tr, LS_ERR_INVALID_ARGUMENT, "ls_geometry_motion.reserved must be 0");
+    if (n_motions > tr->geoms.size()) return fail(tr, LS_ERR_INVALID_ARGUMENT, "more motions than geometries");
+    std::vector<uint32_t> ids(n_motions);
+    for (uint32_t k = 0; k < n_motions; ++k) ids[k] = motions[k].geom;
+    std::sort(ids.begin(), ids.end());
+    if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a geometry named by two motions");
+    if (!host) {
+        bool bad = misaligned(col_pose, 4) || misaligned(n_points, 4) || misaligned16(points32, hits);
+        for (uint32_t k = 0; k < n_motions; ++k) bad = bad || misaligned(motions[k].col_motion, 4);
+        if (bad)
+            return fail(tr, LS_ERR_INVALID_ARGUMENT,
+                        "points and hit records must be 16-byte aligned, the poses, the motion tables and the count 4-byte aligned");
+    }
+    if (capacity < shard_rays(tr)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "capacity below the shard's ray count");
+    if (shard_rays(tr) > kMaxQueryRecords) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
+    tr->rq.last_built = 0;
+    if (const int rc = uncommitted(tr)) return rc;   // (nothing is written, the count included)
+    // every geomID to its layout entry: the walk takes the tables in layout order
+    table.assign(tr->layout.size(), nullptr);
+    for (uint32_t k = 0; k < n_motions; ++k) {
+        size_t i = 0;
+        while (i < tr->slot_geom_ids.size() && (uint32_t)tr->slot_geom_ids[i] != motions[k].geom) ++i;
+        if (i >= table.size()) return fail(tr, LS_ERR_UNKNOWN_GEOMETRY, "a motion names a geometry that is not in the committed scene");
+        table[i] = motions[k].col_motion;
+    }
+    return LS_OK;
+}
+
+// d_col_pose nullptr: the sensor at rest -- the nominal rays from the origin (the centre sample of a beam: ls_trace_scene's rays),
+// nothing to deskew; moving false: no motions -- the walk of ls_trace_scene_sweep
+int moving_issue(ls_tracer *tr, hipStream_t s, const float *d_col_pose, const std::vector<const float *> &d_table, bool moving, uint32_t flags,
+                 void *d_points32, void *d_hits, uint32_t *d_n_points)
+{
+    ls_tracer::RayQuery &q = tr->rq;
+    const uint32_t nq = shard_rays(tr);
+    int rc;
+    if ((rc = ensure(tr, q.sweep_rays, (size_t)nq * 32))) return rc;
+    if ((rc = ensure(tr, q.sweep_hits, (size_t)nq * 16))) return rc;
+    if ((rc = ensure(tr, q.sweep_counts, ls::sweep_block_count(nq)))) return rc;
+    const ls::SensorTables tb = tables(tr);
+    if (d_col_pose) {
+        ls::launch_sweep_rays(s, tb, d_col_pose, q.sweep_rays.p, nullptr);
+    } else {
+        ls::BeamPattern pat;
+        std::memset(static_cast<void *>(&pat), 0, sizeof(pat));
+        pat.k[0] = 1.0f;
+        ls::launch_beam_rays(s, tb, pat, 1, q.sweep_rays.p);
+    }
+    if ((rc = query_walk(tr, s, q.sweep_rays.p, nq, q.sweep_hits.p, closest_hits(), moving ? d_table.data() : nullptr))) return rc;
+    ls::launch_sweep_pack(s, tb, q.sweep_hits.p, q.sweep_counts.p, d_col_pose, d_col_pose && (flags & LS_SWEEP_DESKEW) != 0, d_points32, d_hits,
+                          d_n_points);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+// tau_h = t0 + h dt; Q_h = Rodrigues' rotation by ang_vel * tau_h, c_h = (pivot - Q_h pivot) + lin_vel * tau_h (pivot nullptr: the
+// origin); double throughout, one rounding.  A turn about a pivot that leaves an offset of zero adds nothing: -0 + 0 would be +0.
+void twist_table(const float *lin_vel, const float *ang_vel, const float *pivot, double t0, double dt, uint32_t n_cols, float *out)
+{
+    const double w[3] = {ang_vel[0], ang_vel[1], ang_vel[2]};
+    const double wn = std::sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+    for (uint32_t h = 0; h < n_cols; ++h) {
+        const double tau = t0 + (double)h * dt, angle = wn * tau;
+        double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        if (angle != 0.0) {
+            const double k[3] = {w[0] / wn, w[1] / wn, w[2] / wn}, sn = std::sin(angle), c1 = 1.0 - std::cos(angle);
+            // R = I + sin(a) K + (1 - cos(a)) K^2, K the cross-product matrix of the unit axis k
+            const double K[9] = {0, -k[2], k[1], k[2], 0, -k[0], -k[1], k[0], 0};
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    const double K2 = k[i] * k[j] - (i == j ? 1.0 : 0.0);   // (k k^T - I: |k| = 1)
+                    R[3 * i + j] = (i == j ? 1.0 : 0.0) + sn * K[3 * i + j] + c1 * K2;
+                }
+        }
+        float *p = out + 12 * (size_t)h;
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) p[4 * i + j] = (float)R[3 * i + j];
+            const double drive = (double)lin_vel[i] * tau;
+            double turn = 0.0;
+            if (pivot) turn = (double)pivot[i] - ((R[3 * i] * (double)pivot[0] + R[3 * i + 1] * (double)pivot[1]) + R[3 * i + 2] * (double)pivot[2]);
+            p[4 * i + 3] = (float)(turn != 0.0 ? turn + drive : drive);
+        }
+    }
+}
+
+bool twist_finite(const float *lin_vel, const float *ang_vel, const float *pivot, double t0, double dt)
+{
+    if (!std::isfinite(t0) || !std::isfinite(dt)) return false;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(lin_vel[k]) || !std::isfinite(ang_vel[k]) || (pivot && !std::isfinite(pivot[k]))) return false;
+    return true;
 }
 
 }  // namespace
@@ -289,31 +400,60 @@ int ls_beam_pattern_rings(float half_angle_az, float half_angle_el, uint32_t n_r
 int ls_sweep_poses_constant_twist(const float lin_vel[3], const float ang_vel[3], double t0, double dt, uint32_t n_cols, float *col_pose)
 {
     if (!lin_vel || !ang_vel || (n_cols && !col_pose)) return LS_ERR_INVALID_ARGUMENT;
-    if (!std::isfinite(t0) || !std::isfinite(dt)) return LS_ERR_INVALID_ARGUMENT;
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(lin_vel[k]) || !std::isfinite(ang_vel[k])) return LS_ERR_INVALID_ARGUMENT;
-    const double w[3] = {ang_vel[0], ang_vel[1], ang_vel[2]};
-    const double wn = std::sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
-    for (uint32_t h = 0; h < n_cols; ++h) {
-        const double tau = t0 + (double)h * dt, angle = wn * tau;
-        double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        if (angle != 0.0) {
-            const double k[3] = {w[0] / wn, w[1] / wn, w[2] / wn}, sn = std::sin(angle), c1 = 1.0 - std::cos(angle);
-            // R = I + sin(a) K + (1 - cos(a)) K^2, K the cross-product matrix of the unit axis k
-            const double K[9] = {0, -k[2], k[1], k[2], 0, -k[0], -k[1], k[0], 0};
-            for (int i = 0; i < 3; ++i)
-                for (int j = 0; j < 3; ++j) {
-                    const double K2 = k[i] * k[j] - (i == j ? 1.0 : 0.0);   // (k k^T - I: |k| = 1)
-                    R[3 * i + j] = (i == j ? 1.0 : 0.0) + sn * K[3 * i + j] + c1 * K2;
-                }
-        }
-        float *p = col_pose + 12 * (size_t)h;
-        for (int i = 0; i < 3; ++i) {
-            for (int j = 0; j < 3; ++j) p[4 * i + j] = (float)R[3 * i + j];
-            p[4 * i + 3] = (float)((double)lin_vel[i] * tau);
-        }
-    }
+    if (!twist_finite(lin_vel, ang_vel, nullptr, t0, dt)) return LS_ERR_INVALID_ARGUMENT;
+    twist_table(lin_vel, ang_vel, nullptr, t0, dt, n_cols, col_pose);
     return LS_OK;
+}
+
+// host only: the same table for a body that turns about `pivot` while it drives on: c_h = pivot - Q_h pivot + lin_vel * tau_h
+int ls_motion_constant_twist(const float lin_vel[3], const float ang_vel[3], const float pivot[3], double t0, double dt, uint32_t n_cols,
+                             float *col_motion)
+{
+    if (!lin_vel || !ang_vel || !pivot || (n_cols && !col_motion)) return LS_ERR_INVALID_ARGUMENT;
+    if (!twist_finite(lin_vel, ang_vel, pivot, t0, dt)) return LS_ERR_INVALID_ARGUMENT;
+    twist_table(lin_vel, ang_vel, pivot, t0, dt, n_cols, col_motion);
+    return LS_OK;
+}
+
+int ls_trace_scene_sweep_moving(ls_tracer *tr, void *hip_stream, const float *d_col_pose, uint32_t n_cols, const ls_geometry_motion *motions,
+                                uint32_t n_motions, uint32_t flags, void *d_points32, void *d_hits, uint32_t *d_n_points, uint32_t capacity)
+{
+    std::vector<const float *> table;
+    LS_ENTER_CHECKED(tr, moving_check(tr, d_col_pose, n_cols, motions, n_motions, flags, d_points32, d_hits, d_n_points, capacity, false, table));
+    const hipStream_t s = stream_of(tr, hip_stream);
+    int rc;
+    if ((rc = query_enter(tr, s)) || (rc = moving_issue(tr, s, d_col_pose, table, n_motions != 0, flags, d_points32, d_hits, d_n_points))) return rc;
+    return query_leave(tr, s);
+}
+
+// the poses, the motion tables and the outputs staged in q.io, on the handle's stream; the count comes back first, then as many records
+int ls_trace_scene_sweep_moving_host(ls_tracer *tr, const float *col_pose, uint32_t n_cols, const ls_geometry_motion *motions, uint32_t n_motions,
+                                     uint32_t flags, void *points32, void *hits, uint32_t *n_points, uint32_t capacity)
+{
+    std::vector<const float *> table;
+    LS_ENTER_CHECKED(tr, moving_check(tr, col_pose, n_cols, motions, n_motions, flags, points32, hits, n_points, capacity, true, table));
+    DevBuf<uint8_t> &buf = tr->rq.io;
+    const hipStream_t s = tr->stream;
+    int rc;
+    if ((rc = query_enter(tr, s))) return rc;
+    const size_t nq = shard_rays(tr), table_bytes = (size_t)tr->H * 48;
+    IoPlan io;
+    const size_t at_points = io.add(points32 ? nq * 32 : 0), at_hits = io.add(hits ? nq * 16 : 0), at_pose = io.add((size_t)n_cols * 48),
+                 at_motion = io.add((size_t)n_motions * table_bytes), at_n = io.add(4);   // (48 H: every table starts 16-byte aligned)
+    if ((rc = ensure(tr, buf, io.total()))) return rc;
+    if (col_pose) LS_HIP(hipMemcpyAsync(buf.p + at_pose, col_pose, (size_t)n_cols * 48, hipMemcpyHostToDevice, s));
+    size_t staged = 0;
+    for (const float *&t : table) {
+        if (!t) continue;
+        uint8_t *dst = buf.p + at_motion + staged++ * table_bytes;
+        LS_HIP(hipMemcpyAsync(dst, t, table_bytes, hipMemcpyHostToDevice, s));
+        t = reinterpret_cast<const float *>(dst);
+    }
+    if ((rc = moving_issue(tr, s, col_pose ? reinterpret_cast<const float *>(buf.p + at_pose) : nullptr, table, n_motions != 0, flags,
+                           points32 ? buf.p + at_points : nullptr, hits ? buf.p + at_hits : nullptr, reinterpret_cast<uint32_t *>(buf.p + at_n))))
+        return rc;
+    return fetch_counted(tr, buf.p + at_n, nq, "ls_trace_scene_sweep_moving: more points than rays",
+                         {{points32, buf.p + at_points, 32}, {hits, buf.p + at_hits, 16}}, n_points);
 }
 
 }  // extern "C"
