@@ -857,6 +857,115 @@ int ls_trace_scene_sweep_moving_host(ls_tracer *tr, const float *col_pose, uint3
 int ls_motion_constant_twist(const float lin_vel[3], const float ang_vel[3], const float pivot[3], double t0, double dt,
                              uint32_t n_cols, float *col_motion);
 
+/* ---- clouds in a driver's own PointCloud2 layout.  Every frame call above leaves the same fixed cloud: 32-byte XYZIR records
+ * (XYZIRBytes.cpp:24-40), compacted, and next to it the ls_hit records (and, for beams, the echo words).  What a driver publishes
+ * differs: Velodyne's 22-byte XYZIRT with a per-point `time` (what LIO-SAM, FAST-LIO and KISS-ICP deskew by), Ouster's organized
+ * V x H image with NaN for a miss, a `label` for segmentation ground truth, a second return.  The reference's sensor config declares
+ * such a layout (message.pointStep, message.pointFields[]: LidarDevice.cpp:559-584) and both of its tracers ignore it.  One more
+ * pass over records that are already in device memory delivers the cloud in whatever record is asked for, ready for
+ * PointCloud2::data; the frame calls, their outputs and LS_ABI_VERSION are unchanged. */
+/* sources */
+#define LS_FIELD_X 1          /* points32 x, y, z, intensity: float sources */
+#define LS_FIELD_Y 2
+#define LS_FIELD_Z 3
+#define LS_FIELD_INTENSITY 4
+#define LS_FIELD_RANGE 5      /* hit.t as it stands (the beams' reported range, the return model's noisy t'): float source */
+#define LS_FIELD_TIME 6       /* col_time[column] + chan_time[ring], one float32 sum: float source */
+#define LS_FIELD_RING 7       /* hit.ray / H        : word sources */
+#define LS_FIELD_COLUMN 8     /* hit.ray % H */
+#define LS_FIELD_RAY 9
+#define LS_FIELD_GEOM 10      /* the label */
+#define LS_FIELD_PRIM 11
+#define LS_FIELD_ECHO 12      /* the word of d_echo (NULL: 0) */
+
+typedef struct ls_cloud_field {
+    uint8_t source;      /* LS_FIELD_* */
+    uint8_t datatype;    /* sensor_msgs::PointField: 1 INT8, 2 UINT8, 3 INT16, 4 UINT16, 5 INT32, 6 UINT32, 7 FLOAT32, 8 FLOAT64 */
+    uint16_t offset;     /* any byte offset: Velodyne's XYZIRT has its float `time` at 18 */
+    float scale, bias;   /* float sources only; word sources: must be 1, 0 */
+} ls_cloud_field;
+
+#define LS_CLOUD_MAX_FIELDS 16
+#define LS_CLOUD_MAX_STEP 128
+#define LS_CLOUD_ORGANIZED 1u
+
+typedef struct ls_cloud_format {
+    uint32_t point_step;   /* 1..LS_CLOUD_MAX_STEP, any value (22 is real) */
+    uint32_t n_fields;     /* 1..LS_CLOUD_MAX_FIELDS */
+    uint32_t flags;        /* 0 or LS_CLOUD_ORGANIZED */
+    uint32_t layer;        /* organized: 0..2, which of a ray's records fills the cell (below); else must be 0 */
+    ls_cloud_field fields[LS_CLOUD_MAX_FIELDS];
+} ls_cloud_format;         /* no pointers: travels in the kernel arguments */
+
+/*   d_hits:  n ls_hit records, 16-byte aligned; required when n > 0.
+ *   d_points32: the 32-byte points that belong to them, record for record, 16-byte aligned; required when the format names X, Y, Z
+ *            or INTENSITY, and may be NULL otherwise.
+ *   d_echo:  NULL, or n words, 4-byte aligned (ls_trace_scene_beams' d_echo).
+ *   d_count: NULL, or the device count word of the call that produced the records: min(n, *d_count) records are handled -- no host
+ *            read-back (the records of ls_trace_scene_async: d_points32, d_hits, d_n_points, n = the capacity).
+ *   d_col_time: H floats indexed by the GLOBAL column, d_chan_time: V floats; device memory, 4-byte aligned, never read on the host.
+ *            NULL means all zeros (the sum is still formed); d_col_time is required when the format names TIME.  H and V are the
+ *            handle's raster: LS_INFO_AZIMUTH_COUNT and ls_total_channels.
+ * The call needs NO committed scene: it reads only the sensor's raster size, so recorded hits can be formatted too.
+ * One record, ONE operation sequence (csrc/ls_cloud_format.h; ls_debug_format_record in lidarshooter_hip_debug.h runs it on the
+ * host):
+ *   1. every byte of the point_step bytes is written; bytes no field covers are 0;
+ *   2. a float source gives f (X, Y, Z, INTENSITY, RANGE, TIME).  With scale == 1 && bias == 0 and FLOAT32 the bits of f are stored
+ *      untouched (-0 and NaN payloads included).  Otherwise g = (f * scale) + bias in float32 with no fused multiply-add (for the
+ *      other datatypes with scale 1 and bias 0, g = f); FLOAT32 stores g, FLOAT64 (double)g, a NaN g as the canonical quiet NaN
+ *      0x7FC00000 / 0x7FF8000000000000; the integers: a NaN g gives 0, otherwise r = rintf(g) (ties to even), saturated to the
+ *      datatype's range -- below its lowest the lowest, above its highest the highest, +-inf included --, then converted;
+ *   3. a word source gives a uint32 w (RING, COLUMN, RAY, GEOM, PRIM, ECHO): the integer datatypes store its low bits (a C
+ *      conversion: 0xFFFFFFFF is all ones in every width), FLOAT32 (float)w, FLOAT64 (double)w;
+ *   4. a record with hit.ray >= V * H is not of this raster: its RING, COLUMN and TIME sources are 0, and no table is indexed by
+ *      it.  Every index is checked before an address is formed from it.
+ *   Values are little-endian.
+ * Unorganized (flags = 0): record i of the output is record i of the input; min(n, *d_count) * point_step bytes are written from
+ *   d_out and nothing past them; n = 0 writes nothing.
+ * Organized (LS_CLOUD_ORGANIZED): the output is exactly V * H records, cell c = v * H + h at byte c * point_step: the FULL raster
+ *   whatever the shard (the cells of other shards are misses); n = 0 gives V * H misses.  The rank of input record i is the number
+ *   of immediately preceding records i-1, i-2, i-3 that carry the same ray, counted up to the first one that differs: 0..3.  A
+ *   record fills its ray's cell when its rank equals fmt->layer; a record of rank 3 is never used.  Every producer in the library
+ *   emits a ray's records adjacently and a beam's in ascending range: layer 0 is the nearest return, layer 1 the second (Ouster's
+ *   two range images).  If several non-adjacent records claim one cell, the cell holds one of them whole; which one is
+ *   unspecified.  A record with ray >= V * H is left out.  A cell nobody fills is a miss: X, Y, Z, INTENSITY and RANGE have f =
+ *   the canonical NaN (float types store NaN, integer types 0), GEOM and PRIM are 0xFFFFFFFF, ECHO is 0, and RING, COLUMN, RAY and
+ *   TIME are the cell's own -- a missed cell still has a ring and a firing time.
+ * LS_ERR_INVALID_ARGUMENT before any device call, in this order: a frame graph is open; a NULL handle or format; a format
+ * ls_cloud_format_check refuses; NULL hits with n > 0, or a NULL output where something is to be written; X, Y, Z or INTENSITY named
+ * without points (n > 0); TIME named without d_col_time; misaligned pointers (16 bytes for d_out, points and hits; 4 for the words
+ * and the times).  LS_ERR_OUT_OF_RANGE: n above 0xFFF00000.  The output must not overlap the inputs.  Stream order and the frame
+ * graph rule are those of ls_hit_attributes; LS_INFO_RAY_QUERY_BUILT is left as it is; frames of ls_trace_scene* are unaffected.
+ * The organized mode uses a scratch map of V * H words on the handle, grown on demand and released with the query state; calls on
+ * one handle use it one after the other.
+ * Not offered: a call of the ITracer adapter; big-endian clouds; fields with count > 1; planar (structure-of-arrays) images. */
+int ls_format_cloud(ls_tracer *tr, void *hip_stream, const ls_cloud_format *fmt,
+                    const void *d_points32, const void *d_hits, const uint32_t *d_echo,
+                    const uint32_t *d_count, uint32_t n,
+                    const float *d_col_time, const float *d_chan_time, void *d_out);
+/* The same with host memory (pageable, any alignment) in and out and no count word, on the handle's stream; returns when out is
+ * filled (n * point_step bytes, or V * H * point_step organized). */
+int ls_format_cloud_host(ls_tracer *tr, const ls_cloud_format *fmt, const void *points32, const void *hits,
+                         const uint32_t *echo, uint32_t n, const float *col_time, const float *chan_time, void *out);
+
+/* host only, no handle, no device */
+/* LS_OK, or LS_ERR_INVALID_ARGUMENT for: a NULL format; a step outside 1..LS_CLOUD_MAX_STEP or a field count outside
+ * 1..LS_CLOUD_MAX_FIELDS; an unknown source, datatype or flag bit; layer > 2, or layer != 0 without LS_CLOUD_ORGANIZED; a field that
+ * does not fit inside the step; two fields that overlap; a non-finite scale or bias, or a scale or bias other than 1 and 0 on a word
+ * source. */
+int ls_cloud_format_check(const ls_cloud_format *fmt);
+/* A format from what the reference's sensor config declares (message.pointFields[] and message.pointStep, LidarDevice.cpp:570-582):
+ * names match case-sensitively -- x, y, z, intensity; ring, channel -> RING; time, t, timestamp -> TIME; range, distance -> RANGE;
+ * label, geom -> GEOM; prim -> PRIM; ray -> RAY; column -> COLUMN; echo, return_type -> ECHO --, scale 1, bias 0, flags and layer 0.
+ * LS_ERR_UNSUPPORTED_TYPE for an unknown name or a count other than 1; LS_ERR_INVALID_ARGUMENT for NULL pointers, more than
+ * LS_CLOUD_MAX_FIELDS fields, an offset above 65535, or a result ls_cloud_format_check refuses. */
+int ls_cloud_format_from_point_fields(const char *const *names, const uint32_t *offsets, const uint8_t *datatypes,
+                                      const uint32_t *counts, uint32_t n_fields, uint32_t point_step, ls_cloud_format *out);
+/* Firing times of the azimuth columns: tau_h = t0 + h * dt evaluated in double and rounded once to float32 -- the tau of
+ * ls_sweep_poses_constant_twist and ls_motion_constant_twist.  col_time: n_cols floats.  LS_ERR_INVALID_ARGUMENT for a NULL pointer
+ * or non-finite inputs. */
+int ls_column_times(double t0, double dt, uint32_t n_cols, float *col_time);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,6 +106,14 @@ int ls_debug_beam_sweep_check(const ls_beam_model *model, const uint32_t *weight
  * runs (csrc/ls_motion.h) -> origin Q^T (o - c), tmin 0, direction Q^T d, tmax 1e16 */
 int ls_debug_motion_ray(const float ray8_in[8], const float motion12[12], float ray8_out[8]);
 
+/* one record of ls_format_cloud on the host (no device, no handle): the operation sequence k_format_cloud runs per record
+ * (csrc/ls_cloud_format.h).  point32: the 32-byte point, or NULL (zeros: the format names none of its fields); hit: the ls_hit, or
+ * NULL -- the miss cell of cell_ray (an organized cloud's cell nobody fills); echo_word; col_time_value / chan_time_value: the
+ * entries of the record's column and ring (ignored for a ray >= V * H, whose ring, column and time are 0); out_bytes: point_step
+ * bytes, all written.  LS_ERR_INVALID_ARGUMENT for NULL fmt / out_bytes or a format ls_cloud_format_check refuses. */
+int ls_debug_format_record(const ls_cloud_format *fmt, const void *point32, const ls_hit *hit, uint32_t echo_word,
+                           float col_time_value, float chan_time_value, uint32_t V, uint32_t H, uint32_t cell_ray, void *out_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,13 +58,15 @@ SYMBOLS = (
     "ls_trace_scene_beams", "ls_trace_scene_beams_host", "ls_beam_pattern_rings",
     "ls_trace_scene_beams_sweep", "ls_trace_scene_beams_sweep_host", "ls_beam_weights_gaussian",
     "ls_trace_scene_sweep_moving", "ls_trace_scene_sweep_moving_host", "ls_motion_constant_twist",
+    "ls_format_cloud", "ls_format_cloud_host", "ls_cloud_format_check", "ls_cloud_format_from_point_fields", "ls_column_times",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
 DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_scene_size", "ls_debug_download_scene",
                  "ls_debug_download_bvh", "ls_debug_sort_pairs", "ls_debug_expand_hits", "ls_debug_closest_on_triangle",
                  "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model", "ls_debug_sweep_ray",
                  "ls_debug_beam_ray", "ls_debug_beam_echoes", "ls_debug_beam_model_check",
-                 "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check", "ls_debug_motion_ray")
+                 "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check", "ls_debug_motion_ray",
+                 "ls_debug_format_record")
 
 
 class SensorDesc(C.Structure):
@@ -108,6 +110,45 @@ class GeometryMotion(C.Structure):
     """ls_geometry_motion: the geomID of a geometry that moves during the turn and its table of H records [Q | c] (an address:
     device memory for the device call, host memory for the host variant)"""
     _fields_ = [("geom", C.c_uint32), ("reserved", C.c_uint32), ("col_motion", C.c_void_p)]
+
+
+# ls_format_cloud: the sources of a cloud field, the sensor_msgs::PointField datatypes, the limits and the flag
+(LS_FIELD_X, LS_FIELD_Y, LS_FIELD_Z, LS_FIELD_INTENSITY, LS_FIELD_RANGE, LS_FIELD_TIME, LS_FIELD_RING, LS_FIELD_COLUMN, LS_FIELD_RAY,
+ LS_FIELD_GEOM, LS_FIELD_PRIM, LS_FIELD_ECHO) = range(1, 13)
+LS_INT8, LS_UINT8, LS_INT16, LS_UINT16, LS_INT32, LS_UINT32, LS_FLOAT32, LS_FLOAT64 = range(1, 9)
+LS_CLOUD_MAX_FIELDS, LS_CLOUD_MAX_STEP, LS_CLOUD_ORGANIZED = 16, 128, 1
+# name -> source of ls_cloud_format_from_point_fields (message.pointFields[].name of the reference's sensor config)
+CLOUD_FIELD_NAMES = {"x": LS_FIELD_X, "y": LS_FIELD_Y, "z": LS_FIELD_Z, "intensity": LS_FIELD_INTENSITY, "ring": LS_FIELD_RING,
+                     "channel": LS_FIELD_RING, "time": LS_FIELD_TIME, "t": LS_FIELD_TIME, "timestamp": LS_FIELD_TIME,
+                     "range": LS_FIELD_RANGE, "distance": LS_FIELD_RANGE, "label": LS_FIELD_GEOM, "geom": LS_FIELD_GEOM,
+                     "prim": LS_FIELD_PRIM, "ray": LS_FIELD_RAY, "column": LS_FIELD_COLUMN, "echo": LS_FIELD_ECHO,
+                     "return_type": LS_FIELD_ECHO}
+
+
+class CloudField(C.Structure):
+    _fields_ = [("source", C.c_uint8), ("datatype", C.c_uint8), ("offset", C.c_uint16), ("scale", C.c_float), ("bias", C.c_float)]
+
+
+class CloudFormat(C.Structure):
+    """ls_cloud_format: `fields` tuples (source, datatype, offset[, scale, bias]) -- LS_FIELD_*, a PointField datatype 1..8, a byte
+    offset, scale 1 and bias 0 by default -- in records of `point_step` bytes; organized: the V x H image of layer `layer` instead
+    of record after record.  Nothing is checked here: cloud_format_check and the calls do that."""
+    _fields_ = [("point_step", C.c_uint32), ("n_fields", C.c_uint32), ("flags", C.c_uint32), ("layer", C.c_uint32),
+                ("fields", CloudField * LS_CLOUD_MAX_FIELDS)]
+
+    def __init__(self, point_step: int = 0, fields=(), organized: bool = False, layer: int = 0):
+        super().__init__()
+        fields = list(fields)
+        if len(fields) > LS_CLOUD_MAX_FIELDS:
+            raise ValueError("ls_cloud_format holds at most LS_CLOUD_MAX_FIELDS fields")
+        self.point_step, self.n_fields, self.flags, self.layer = point_step, len(fields), LS_CLOUD_ORGANIZED if organized else 0, layer
+        for f, t in zip(self.fields, fields):
+            f.source, f.datatype, f.offset = t[0], t[1], t[2]
+            f.scale, f.bias = (t[3], t[4]) if len(t) > 3 else (1.0, 0.0)
+
+    @property
+    def organized(self) -> bool:
+        return bool(self.flags & LS_CLOUD_ORGANIZED)
 
 
 class ReturnModel(C.Structure):
@@ -270,6 +311,12 @@ def load() -> C.CDLL:
     L.ls_trace_scene_sweep_moving_host.argtypes = [vp, vp, u32, C.POINTER(GeometryMotion), u32, u32, vp, vp, u32p, u32]
     L.ls_motion_constant_twist.argtypes = [f32p, f32p, f32p, C.c_double, C.c_double, u32, f32p]
     L.ls_debug_motion_ray.argtypes = [f32p, f32p, f32p]
+    L.ls_format_cloud.argtypes = [vp, vp, C.POINTER(CloudFormat), vp, vp, vp, vp, u32, vp, vp, vp]
+    L.ls_format_cloud_host.argtypes = [vp, C.POINTER(CloudFormat), vp, vp, vp, u32, vp, vp, vp]
+    L.ls_cloud_format_check.argtypes = [C.POINTER(CloudFormat)]
+    L.ls_cloud_format_from_point_fields.argtypes = [C.POINTER(C.c_char_p), u32p, C.POINTER(C.c_uint8), u32p, u32, u32, C.POINTER(CloudFormat)]
+    L.ls_column_times.argtypes = [C.c_double, C.c_double, u32, f32p]
+    L.ls_debug_format_record.argtypes = [C.POINTER(CloudFormat), vp, vp, u32, C.c_float, C.c_float, u32, u32, u32, vp]
     L.ls_geometry_type.argtypes = [vp, C.c_char_p]
     L.ls_debug_dense_hits.argtypes = [vp, f32p, u32p]
     L.ls_debug_trace_bruteforce.argtypes = [vp, f32p, u32p]
@@ -842,6 +889,42 @@ class Tracer:
         return -1 if rc == -1 else int(self._check(rc, "ls_trace_scene_beams_sweep"))
 
     # ---- test hooks
+    def formatCloud(self, fmt: CloudFormat, hits, points=None, echo=None, col_time=None, chan_time=None):
+        """A cloud in a driver's own record (ls_format_cloud_host): `hits` HIT_DTYPE or uint32 (n, 4), `points` the uint8 (n, 32)
+        points that belong to them (None when the format names none of x, y, z, intensity), `echo` None or uint32 (n,), `col_time`
+        None or float32 (H,), `chan_time` None or float32 (V,).  -> uint8 (n, point_step), or (V * H, point_step) organized.  Needs
+        no committed scene."""
+        h = np.ascontiguousarray(hits)
+        if h.dtype != HIT_DTYPE:
+            h = np.ascontiguousarray(h, np.uint32)
+            if h.ndim != 2 or h.shape[1] != 4:
+                raise ValueError("hits: HIT_DTYPE or uint32 (n, 4)")
+        n = h.shape[0]
+        p = None if points is None else np.ascontiguousarray(points, np.uint8).reshape(-1, 32)
+        e = None if echo is None else np.ascontiguousarray(echo, np.uint32).reshape(-1)
+        ct = None if col_time is None else np.ascontiguousarray(col_time, np.float32).reshape(-1)
+        ch = None if chan_time is None else np.ascontiguousarray(chan_time, np.float32).reshape(-1)
+        V, H = int(self.L.ls_total_channels(self.h)), self.info(LS_INFO_AZIMUTH_COUNT)
+        if (p is not None and p.shape[0] != n) or (e is not None and e.shape[0] != n) or (ct is not None and ct.shape[0] != H) or \
+                (ch is not None and ch.shape[0] != V):
+            raise ValueError("points, echo: one per hit record; col_time: H floats; chan_time: V floats")
+        out = np.zeros((V * H if fmt.organized else n, max(int(fmt.point_step), 1)), np.uint8)
+        rc = self.L.ls_format_cloud_host(self.h, C.byref(fmt), p.ctypes.data if p is not None and n else None, h.ctypes.data if n else None,
+                                         e.ctypes.data if e is not None and n else None, n, None if ct is None else ct.ctypes.data,
+                                         None if ch is None else ch.ctypes.data, out.ctypes.data if out.size else None)
+        self._check(rc, "ls_format_cloud_host")
+        return out
+
+    def formatCloudDevice(self, fmt: CloudFormat, d_hits: int, n: int, d_out: int, d_points32: int = 0, d_echo: int = 0, d_count: int = 0,
+                          d_col_time: int = 0, d_chan_time: int = 0, stream=None) -> int:
+        """ls_format_cloud on device pointers (n ls_hit records, their 32-byte points and echo words in -- the latter two may be 0 --;
+        d_count != 0: a device word, min(n, *d_count) records are handled; d_col_time: H floats, d_chan_time: V floats, 0: zeros;
+        records of fmt.point_step bytes out, V * H of them organized); enqueued on `stream` (a hipStream_t as an int, None: the
+        handle's), no wait."""
+        rc = self.L.ls_format_cloud(self.h, stream, C.byref(fmt), d_points32 or None, d_hits or None, d_echo or None, d_count or None, n,
+                                    d_col_time or None, d_chan_time or None, d_out or None)
+        return int(self._check(rc, "ls_format_cloud"))
+
     def generateRaysAos(self, d_rays: int | None, d_hits: int | None):
         """LidarDevice::allRaysGPU's two buffers (Ray 32 B, Hit 24 B per ray) in device memory of the caller."""
         self._check(self.L.ls_generate_rays_aos(self.h, d_rays, d_hits), "ls_generate_rays_aos")
@@ -1058,3 +1141,52 @@ def beam_echoes_weighted(model: BeamModel, weights, min_weight, r, hit):
     if rc != 0:
         raise LidarShooterHipError(f"ls_debug_beam_echoes_weighted: status {rc}")
     return out[:n.value].copy()
+
+
+def cloud_format_check(fmt: CloudFormat) -> int:
+    """ls_cloud_format_check: 0, or LS_ERR_INVALID_ARGUMENT (-2) for a format ls_format_cloud refuses"""
+    return int(load().ls_cloud_format_check(C.byref(fmt)))
+
+
+def cloud_format_from_point_fields(point_fields, point_step: int) -> CloudFormat:
+    """ls_cloud_format_from_point_fields: the format a sensor config declares -- `point_fields` the dicts of message.pointFields[]
+    (name, offset, datatype, count), `point_step` message.pointStep -> CloudFormat; raises on an unknown name, a count other than 1 or
+    a layout ls_cloud_format_check refuses (the status is in the message)"""
+    L = load()
+    pf = list(point_fields)
+    n = len(pf)
+    names = (C.c_char_p * max(n, 1))(*[str(f["name"]).encode() for f in pf])
+    offsets = np.array([int(f["offset"]) for f in pf], np.uint32)
+    datatypes = np.array([int(f["datatype"]) for f in pf], np.uint8)
+    counts = np.array([int(f.get("count", 1)) for f in pf], np.uint32)
+    out = CloudFormat()
+    rc = L.ls_cloud_format_from_point_fields(names, _u32p(offsets), datatypes.ctypes.data_as(C.POINTER(C.c_uint8)), _u32p(counts), n, int(point_step),
+                                             C.byref(out))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_cloud_format_from_point_fields: status {rc}")
+    return out
+
+
+def column_times(t0: float, dt: float, n_cols: int):
+    """ls_column_times: the firing time of every azimuth column, tau_h = t0 + h dt in double rounded once -> float32 (n_cols,)"""
+    L = load()
+    out = np.zeros(max(int(n_cols), 1), np.float32)
+    rc = L.ls_column_times(float(t0), float(dt), int(n_cols), _f32p(out))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_column_times: status {rc}")
+    return out[:int(n_cols)]
+
+
+def format_record(fmt: CloudFormat, point32, hit, echo_word: int, col_time_value: float, chan_time_value: float, V: int, H: int,
+                  cell_ray: int = 0):
+    """ls_debug_format_record: one record of ls_format_cloud on the host -- `point32` 32 bytes or None, `hit` a HIT_DTYPE record /
+    4 words, or None: the miss cell of `cell_ray` -> uint8 (point_step,)"""
+    L = load()
+    p = None if point32 is None else np.ascontiguousarray(point32).view(np.uint8).reshape(32)
+    h = None if hit is None else np.ascontiguousarray(hit).view(np.uint8).reshape(16)
+    out = np.full(max(int(fmt.point_step), 1), 0xEE, np.uint8)
+    rc = L.ls_debug_format_record(C.byref(fmt), None if p is None else p.ctypes.data, None if h is None else h.ctypes.data, int(echo_word),
+                                  float(col_time_value), float(chan_time_value), int(V), int(H), int(cell_ray), out.ctypes.data)
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_debug_format_record: status {rc}")
+    return out[:int(fmt.point_step)]

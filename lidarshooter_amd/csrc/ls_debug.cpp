@@ -8,6 +8,7 @@
 #include "ls_sweep.h"
 #include "ls_motion.h"
 #include "ls_beam.h"
+#include "ls_cloud_format.h"
 
 #include <algorithm>
 
@@ -258,6 +259,19 @@ int ls_debug_beam_sweep_check(const ls_beam_model *model, const uint32_t *weight
     int status = LS_OK;
     if (ls::beam_model_invalid(model, shard_rays, capacity, &status)) return status;
     return ls::beam_weights_invalid(weights, model->n_samples) ? LS_ERR_INVALID_ARGUMENT : LS_OK;
+}
+
+// cloud_sources, then cloud_format_record: what a lane of k_format_cloud does for its record, or for the miss cell of cell_ray
+int ls_debug_format_record(const ls_cloud_format *fmt, const void *point32, const ls_hit *hit, uint32_t echo_word, float col_time_value,
+                           float chan_time_value, uint32_t V, uint32_t H, uint32_t cell_ray, void *out_bytes)
+{
+    if (!out_bytes || ls_cloud_format_check(fmt) != LS_OK) return LS_ERR_INVALID_ARGUMENT;
+    uint32_t p8[8], h4[4] = {cell_ray, 0u, 0u, 0u};
+    if (point32) std::memcpy(p8, point32, 32);
+    if (hit) std::memcpy(h4, hit, 16);
+    const ls::CloudSources src = ls::cloud_sources(point32 ? p8 : nullptr, h4, !hit, echo_word, col_time_value, chan_time_value, V, H);
+    ls::cloud_format_record(*fmt, src, static_cast<uint8_t *>(out_bytes));
+    return LS_OK;
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 //   ls_query.cpp     ls_trace_rays / ls_occluded_rays / ls_closest_points: the query set of per-geometry hierarchies (built lazily),
 //                    batches of geometries per launch; what every query entry point shares (stream hand-over, staging, read-back)
 //   ls_gather.cpp    ls_hit_attributes: the per-geomID table of its gather kernel; ls_apply_return_model: the same table, its scratch
+//   ls_cloud.cpp     ls_format_cloud: the records of a frame as a cloud in a driver's own record (ls_format.hip), its format helpers
 //   ls_scan.cpp      ls_trace_scene_sweep, ls_trace_scene_beams, ls_trace_scene_sweep_moving: their scratch around the queries' walk
 //                    (ls_sweep.hip, ls_beam.hip, ls_moving.hip)
 //   ls_host_pool.cpp worker threads for host-side copies, point expansion
@@ -294,6 +295,8 @@ struct ls_tracer {
         lsi::DevBuf<uint8_t> beam_rays, beam_hits;
         lsi::DevBuf<uint4> beam_blocks;
         lsi::DevBuf<uint32_t> beam_counts;
+        // ls_format_cloud, organized: which record fills each of the V * H cells (one call at a time, as the sweep)
+        lsi::DevBuf<uint32_t> cloud_map;
         std::vector<RayQuerySlot> built;       // per layout entry
         std::vector<int> layout_ids;           // geometry ids of the layout the slots were made for ...
         std::vector<uint32_t> layout_firsts;   // ... and their first vertex, first triangle in it

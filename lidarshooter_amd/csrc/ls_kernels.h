@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 struct ls_return_model;   // include/lidarshooter_hip.h
+struct ls_cloud_format;
 
 namespace ls {
 
@@ -336,6 +337,28 @@ void launch_beam_sweep_pack(hipStream_t s, const SensorTables &tb, const BeamPat
                             float separation, uint32_t min_count, uint32_t min_weight, uint32_t returns, const float *pose, bool deskew,
                             const void *dense, void *blocks, uint32_t *wsum, uint32_t *cnt, uint32_t *block_counts, void *points32, void *hits,
                             uint32_t *echo, uint32_t *n_points, uint32_t capacity);
+// ls_format_cloud (ls_format.hip): n ls_hit records (min(n, *d_count) with a device count), their 32-byte points and echo words
+// (either may be nullptr) and the firing-time tables (col_time[H], chan_time[V]; nullptr: zeros) through the format's fields
+// (ls_cloud_format.h; the format travels by value in the kernel arguments) into records of point_step bytes at `out` (16-byte
+// aligned).  map = nullptr: output record i is input record i.  Otherwise the organized cloud: launch_cloud_map fills the V * H
+// words of map with kCloudNoRecord, then stores i at map[hit[i].ray] for every record whose rank equals `layer`, and the format
+// kernel writes one record per CELL -- record map[c], or the miss of cell c.
+// Two forms of the same kernel: kCloudFormNaive, one lane per record storing its fields straight to out + i * point_step;
+// kCloudFormStaged, a workgroup's lanes write their records into a tile in LDS, and after one barrier the tile -- one contiguous,
+// 16-byte aligned run of the output -- goes out in 16-byte stores, lane after lane.  kCloudFormShipped is what the entry points
+// use (EXPERIMENTS.md says what measurement decided it; tools/micro/format_forms.hip times both).
+struct CloudInputs {
+    const void *points32, *hits;
+    const uint32_t *echo, *d_count;
+    uint32_t n;
+    const float *col_time, *chan_time;
+    uint32_t V, H;
+};
+constexpr int kCloudFormNaive = 0, kCloudFormStaged = 1;
+constexpr int kCloudFormShipped = kCloudFormStaged;
+void launch_cloud_map(hipStream_t s, const void *hits, const uint32_t *d_count, uint32_t n, uint32_t layer, uint32_t cells, uint32_t *map);
+void launch_format_cloud(hipStream_t s, const ls_cloud_format &fmt, const CloudInputs &in, const uint32_t *map, void *out,
+                         int form = kCloudFormShipped);
 void launch_rowcount(hipStream_t s, const uint32_t *gid, uint32_t nrays, uint32_t *row_counts, uint32_t *queue_heads = nullptr);   // queue_heads: zeroed for the next k_trace
 // Progress of a synchronous frame whose compact points go straight to pinned host memory (ls_trace_scene_begin /
 // ls_trace_scene_expand): the device publishes, with system-scope release, (1) the frame's hit count as the pack pass
