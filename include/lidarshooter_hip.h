@@ -839,8 +839,9 @@ typedef struct ls_geometry_motion {
  * count included), then LS_ERR_UNKNOWN_GEOMETRY for a geom that is not in the committed scene.  Stream order, the shard handling,
  * LS_INFO_RAY_QUERY_BUILT and the query hierarchies are those of ls_trace_scene_sweep, whose scratch the call uses: a commit after
  * which only poses changed still builds nothing.
- * Not offered: a d_rays_out; these records through ls_hit_attributes / ls_apply_return_model (their exact test would need the
- * geometry's own ray); beams; deforming meshes; a call of the ITracer adapter. */
+ * These records go through ls_hit_attributes_moving / ls_apply_return_model_moving below, which rebuild per record the ray its
+ * geometry saw; ls_hit_attributes / ls_apply_return_model know one ray per record and call most of a moving geometry's invalid.
+ * Not offered: a d_rays_out; beams; deforming meshes; a call of the ITracer adapter. */
 int ls_trace_scene_sweep_moving(ls_tracer *tr, void *hip_stream, const float *d_col_pose, uint32_t n_cols,
                                 const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags,
                                 void *d_points32, void *d_hits, uint32_t *d_n_points, uint32_t capacity);
@@ -856,6 +857,67 @@ int ls_trace_scene_sweep_moving_host(ls_tracer *tr, const float *col_pose, uint3
  * records of 12 floats.  LS_ERR_INVALID_ARGUMENT for NULL pointers or non-finite inputs. */
 int ls_motion_constant_twist(const float lin_vel[3], const float ang_vel[3], const float pivot[3], double t0, double dt,
                              uint32_t n_cols, float *col_motion);
+
+/* ---- hit attributes and sensor returns for the records of a sweep: ls_hit_attributes and ls_apply_return_model for a frame of
+ * ls_trace_scene_sweep_moving (or ls_trace_scene_sweep, or ls_trace_scene), whose every geometry saw a ray of its own.  The caller
+ * passes the tables the frame was traced with; per record the call rebuilds the ray the record's geometry saw, runs the exact test
+ * with it, and carries the normal back into the sensor frame.  No hierarchy is built or walked, no 32-byte ray record exists, and
+ * the points keep their ring.
+ *   d_col_pose, n_cols, motions, n_motions, flags: exactly the arguments of ls_trace_scene_sweep_moving (a NULL pose table with
+ *            n_cols 0: the sensor at rest; motions in HOST memory, their tables in device memory -- host memory for _host --, H records
+ *            indexed by the GLOBAL column whatever the shard; geometries not named are at rest; flags 0 or LS_SWEEP_DESKEW).
+ *   d_hits, d_count, n: as ls_hit_attributes; hit.ray is the global ray index v * H + h of the handle's raster.  The calls do not
+ *            depend on the shard.
+ * Per handled record, ONE float32 operation sequence, composed of the existing ones and one new one:
+ *   1. the ray the column cast: with the nominal d from the factor tables, (o, d') = ls_debug_sweep_ray's record for pose[h]; (0, d)
+ *      without a pose table;
+ *   2. the ray geometry hit.geom saw: (o_g, d_g) = ls_debug_motion_ray's record for table[h] of that geometry, and the record is
+ *      invalid when o_g or d_g is not finite or d_g is zero (the walk skipped the geometry there); (o, d') for a geometry at rest;
+ *   3. validity as ls_hit_attributes with the caller ray (o_g, d_g): geom, prim and the vertex indices in range, corners through the
+ *      frame's transform, the exact test with t bit-equal to hit.t, a quad's first half for which that holds; every index -- the
+ *      ray, the geomID, the element, the vertices, the column -- is checked before an address is formed from it;
+ *   4. the 48-byte record of ls_hit_attributes, offsets unchanged: cos_inc, u, v, tri, flags as that call gives them for (o_g, d_g);
+ *      the normal n_g of a geometry at rest as it is, of a moving one carried forward, n_i = (Q[i][0] n_g,0 + Q[i][1] n_g,1) +
+ *      Q[i][2] n_g,2 (csrc/ls_motion.h; ls_debug_motion_normal runs it on the host; an identity record gives n_g back numerically, a
+ *      -0 component may come back as +0); px, py, pz = t * d with the nominal d and no sum -- the bits of the frame's points32 --,
+ *      with LS_SWEEP_DESKEW under a pose table o_h + t * d'_h per axis -- the deskewed frame's bits --; ray = hit.ray.  An invalid
+ *      record: flags 0 and zeros everywhere but `ray`;
+ *   5. ls_apply_return_model_moving: steps 2-8 of ls_apply_return_model on the valid records, with len = sqrtf((d'x d'x + d'y d'y) +
+ *      d'z d'z) of the ray the COLUMN cast (the sensor ranges along its own ray, not along d_g), the noise keyed by hit.ray and
+ *      frame_index, the point t' * d (flags 0) or o_h + t' * d' per axis (LS_SWEEP_DESKEW), ring = hit.ray / H, d_hits_out with t';
+ *      the kept records compacted in input order, model, reflectivities and outputs as ls_apply_return_model.
+ * With no pose table and no motions the bytes of ls_hit_attributes / ls_apply_return_model with d_rays = NULL; with tables that do not
+ * belong to the frame the records of the geometries concerned are invalid.
+ * LS_ERR_INVALID_ARGUMENT before any device call, in this order: (the return model: the model and the reflectivities, as
+ * ls_apply_return_model;) a frame graph is open; NULL hit records or output with n > 0, a NULL d_n_out; ls_trace_scene_sweep_moving's
+ * checks of the pose table, the flags and the motions, in its order; misaligned pointers (records and points 16 bytes; words, tables
+ * and reflectivities 4).  Then LS_ERR_OUT_OF_RANGE for an n above the query-record limit, then the commit state as
+ * ls_hit_attributes (-1 writes nothing), then LS_ERR_UNKNOWN_GEOMETRY for a motion whose geom is not in the committed scene.  n = 0
+ * gives *d_n_out = 0.  Stream order, scratch and the frame graph rule are those of ls_hit_attributes / ls_apply_return_model;
+ * LS_INFO_RAY_QUERY_BUILT is left as it is: nothing is built.
+ * Not offered: beam echoes through these calls (their t is a reported range); deforming meshes; a call of the ITracer adapter. */
+int ls_hit_attributes_moving(ls_tracer *tr, void *hip_stream, const float *d_col_pose, uint32_t n_cols,
+                             const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags,
+                             const void *d_hits, const uint32_t *d_count, uint32_t n, void *d_out);
+/* The same with host memory (pageable) in and out and no count word, on the handle's stream: the pose table and the motion tables
+ * are copied to the device; returns when out is filled. */
+int ls_hit_attributes_moving_host(ls_tracer *tr, const float *col_pose, uint32_t n_cols,
+                                  const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags,
+                                  const void *hits, uint32_t n, void *out);
+int ls_apply_return_model_moving(ls_tracer *tr, void *hip_stream, const ls_return_model *model, uint32_t frame_index,
+                                 const float *d_col_pose, uint32_t n_cols,
+                                 const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags,
+                                 const void *d_hits, const uint32_t *d_count, uint32_t n,
+                                 const float *d_reflectivity, uint32_t n_reflectivity,
+                                 void *d_points32, void *d_hits_out, uint32_t *d_n_out);
+/* The same with host memory (pageable) in and out and no count word, on the handle's stream; returns when the outputs are filled
+ * (*n_out records of each). */
+int ls_apply_return_model_moving_host(ls_tracer *tr, const ls_return_model *model, uint32_t frame_index,
+                                      const float *col_pose, uint32_t n_cols,
+                                      const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags,
+                                      const void *hits, uint32_t n,
+                                      const float *reflectivity, uint32_t n_reflectivity,
+                                      void *points32, void *hits_out, uint32_t *n_out);
 
 /* ---- clouds in a driver's own PointCloud2 layout.  Every frame call above leaves the same fixed cloud: 32-byte XYZIR records
  * (XYZIRBytes.cpp:24-40), compacted, and next to it the ls_hit records (and, for beams, the echo words).  What a driver publishes

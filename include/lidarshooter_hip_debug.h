@@ -105,6 +105,10 @@ int ls_debug_beam_sweep_check(const ls_beam_model *model, const uint32_t *weight
  * record (12 floats, [Q | c] row-major), on the host (no device, no handle): the float32 operation sequence k_trace_rays_moving
  * runs (csrc/ls_motion.h) -> origin Q^T (o - c), tmin 0, direction Q^T d, tmax 1e16 */
 int ls_debug_motion_ray(const float ray8_in[8], const float motion12[12], float ray8_out[8]);
+/* the normal of a moving geometry back in the sensor frame (ls_hit_attributes_moving): the normal n3 found on the geometry where it
+ * was committed, carried forward by one motion record, on the host (no device, no handle): the float32 operation sequence
+ * k_hit_attributes_moving runs (csrc/ls_motion.h) -> out_i = (Q[i][0] n_0 + Q[i][1] n_1) + Q[i][2] n_2 */
+int ls_debug_motion_normal(const float n3[3], const float motion12[12], float out3[3]);
 
 /* one record of ls_format_cloud on the host (no device, no handle): the operation sequence k_format_cloud runs per record
  * (csrc/ls_cloud_format.h).  point32: the 32-byte point, or NULL (zeros: the format names none of its fields); hit: the ls_hit, or

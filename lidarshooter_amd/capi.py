@@ -58,6 +58,7 @@ SYMBOLS = (
     "ls_trace_scene_beams", "ls_trace_scene_beams_host", "ls_beam_pattern_rings",
     "ls_trace_scene_beams_sweep", "ls_trace_scene_beams_sweep_host", "ls_beam_weights_gaussian",
     "ls_trace_scene_sweep_moving", "ls_trace_scene_sweep_moving_host", "ls_motion_constant_twist",
+    "ls_hit_attributes_moving", "ls_hit_attributes_moving_host", "ls_apply_return_model_moving", "ls_apply_return_model_moving_host",
     "ls_format_cloud", "ls_format_cloud_host", "ls_cloud_format_check", "ls_cloud_format_from_point_fields", "ls_column_times",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
@@ -66,7 +67,7 @@ DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_s
                  "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model", "ls_debug_sweep_ray",
                  "ls_debug_beam_ray", "ls_debug_beam_echoes", "ls_debug_beam_model_check",
                  "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check", "ls_debug_motion_ray",
-                 "ls_debug_format_record")
+                 "ls_debug_motion_normal", "ls_debug_format_record")
 
 
 class SensorDesc(C.Structure):
@@ -311,6 +312,13 @@ def load() -> C.CDLL:
     L.ls_trace_scene_sweep_moving_host.argtypes = [vp, vp, u32, C.POINTER(GeometryMotion), u32, u32, vp, vp, u32p, u32]
     L.ls_motion_constant_twist.argtypes = [f32p, f32p, f32p, C.c_double, C.c_double, u32, f32p]
     L.ls_debug_motion_ray.argtypes = [f32p, f32p, f32p]
+    L.ls_hit_attributes_moving.argtypes = [vp, vp, vp, u32, C.POINTER(GeometryMotion), u32, u32, vp, vp, u32, vp]
+    L.ls_hit_attributes_moving_host.argtypes = [vp, vp, u32, C.POINTER(GeometryMotion), u32, u32, vp, u32, vp]
+    L.ls_apply_return_model_moving.argtypes = [vp, vp, C.POINTER(ReturnModel), u32, vp, u32, C.POINTER(GeometryMotion), u32, u32, vp, vp, u32, vp, u32,
+                                               vp, vp, vp]
+    L.ls_apply_return_model_moving_host.argtypes = [vp, C.POINTER(ReturnModel), u32, vp, u32, C.POINTER(GeometryMotion), u32, u32, vp, u32, vp, u32,
+                                                    vp, vp, u32p]
+    L.ls_debug_motion_normal.argtypes = [f32p, f32p, f32p]
     L.ls_format_cloud.argtypes = [vp, vp, C.POINTER(CloudFormat), vp, vp, vp, vp, u32, vp, vp, vp]
     L.ls_format_cloud_host.argtypes = [vp, C.POINTER(CloudFormat), vp, vp, vp, u32, vp, vp, vp]
     L.ls_cloud_format_check.argtypes = [C.POINTER(CloudFormat)]
@@ -821,6 +829,96 @@ class Tracer:
                                                 d_points32 or None, d_hits or None, d_n_points or None, capacity)
         return -1 if rc == -1 else int(self._check(rc, "ls_trace_scene_sweep_moving"))
 
+    @staticmethod
+    def _hit_array(hits):
+        h = np.ascontiguousarray(hits)
+        if h.dtype != HIT_DTYPE:
+            h = np.ascontiguousarray(h, np.uint32)
+            if h.ndim != 2 or h.shape[1] != 4:
+                raise ValueError("hits: HIT_DTYPE or uint32 (n, 4)")
+        return h
+
+    def _host_tables(self, col_pose, motions):
+        """the pose table and the motion tables of traceSweepMoving as the _host entry points take them -> (pose or None, the
+        ls_geometry_motion array or None, its length, what keeps the tables alive)"""
+        pose = None if col_pose is None else np.ascontiguousarray(col_pose, np.float32)
+        if pose is not None and (pose.ndim != 2 or pose.shape[1] != 12):
+            raise ValueError("col_pose: float32 (H, 12)")
+        tabs = {int(g): np.ascontiguousarray(t, np.float32) for g, t in dict(motions).items()}
+        H = self.info(LS_INFO_AZIMUTH_COUNT)
+        if any(t.shape != (H, 12) for t in tabs.values()):
+            raise ValueError("motions: float32 (H, 12) per geometry")
+        arr = (GeometryMotion * max(1, len(tabs)))()
+        for m, (g, t) in zip(arr, tabs.items()):
+            m.geom, m.reserved, m.col_motion = g, 0, t.ctypes.data
+        return pose, (arr if tabs else None), len(tabs), tabs
+
+    @staticmethod
+    def _device_motions(motions):
+        items = list(dict(motions).items())
+        arr = (GeometryMotion * max(1, len(items)))()
+        for m, (g, addr) in zip(arr, items):
+            m.geom, m.reserved, m.col_motion = int(g), 0, int(addr)
+        return (arr if items else None), len(items)
+
+    def hitAttributesMoving(self, hits, col_pose, motions, flags: int = 0):
+        """Surface attributes of the records of a sweep frame (ls_hit_attributes_moving_host): `hits` a HIT_DTYPE array of
+        traceSweepMoving (hit.ray the global ray index), `col_pose`, `motions` and `flags` what that frame was traced with.  ->
+        (rc, HIT_ATTR_DTYPE[n]): the normal in the sensor frame, p the frame's point; rc = -1 (no commit, empty scene): every
+        record invalid."""
+        h = self._hit_array(hits)
+        n = h.shape[0]
+        pose, arr, n_motions, keep = self._host_tables(col_pose, motions)
+        out = np.zeros(n, HIT_ATTR_DTYPE)
+        rc = self.L.ls_hit_attributes_moving_host(self.h, None if pose is None else pose.ctypes.data, 0 if pose is None else pose.shape[0], arr,
+                                                  n_motions, flags, h.ctypes.data if n else None, n, out.ctypes.data if n else None)
+        if rc == -1:
+            out["ray"] = h["ray"] if h.dtype == HIT_DTYPE else h[:, 0]
+            return -1, out
+        self._check(rc, "ls_hit_attributes_moving_host")
+        return int(rc), out
+
+    def hitAttributesMovingDevice(self, d_hits: int, n: int, d_out: int, d_col_pose: int = 0, n_cols: int = 0, motions=(), flags: int = 0,
+                                  d_count: int = 0, stream=None) -> int:
+        """ls_hit_attributes_moving on device pointers: hitAttributesDevice's records with the tables of traceSweepMovingDevice
+        (d_col_pose 0 with n_cols 0: the sensor at rest; `motions` a dict geomID -> device address of H 48-byte records); enqueued on
+        `stream` (a hipStream_t as an int, None: the handle's), no wait.  -> 0, or -1 on an empty / uncommitted scene (d_out not
+        written)."""
+        arr, n_motions = self._device_motions(motions)
+        rc = self.L.ls_hit_attributes_moving(self.h, stream, d_col_pose or None, n_cols, arr, n_motions, flags, d_hits or None, d_count or None, n,
+                                             d_out or None)
+        return -1 if rc == -1 else int(self._check(rc, "ls_hit_attributes_moving"))
+
+    def applyReturnModelMoving(self, model: ReturnModel, hits, col_pose, motions, flags: int = 0, reflectivity=None, frame_index: int = 0):
+        """Sensor returns from the records of a sweep frame (ls_apply_return_model_moving_host): `hits`, `col_pose`, `motions` and
+        `flags` as hitAttributesMoving takes them, `reflectivity` None or float32 per geomID.  -> (rc, points uint8[k, 32] with
+        their ring, hits HIT_DTYPE[k] with the noisy t): the kept returns in input order; rc = -1: none."""
+        h = self._hit_array(hits)
+        n = h.shape[0]
+        pose, arr, n_motions, keep = self._host_tables(col_pose, motions)
+        rho = None if reflectivity is None else np.ascontiguousarray(reflectivity, np.float32).reshape(-1)
+        pts, out, k = np.zeros((n, 32), np.uint8), np.zeros(n, HIT_DTYPE), C.c_uint32(0)
+        rc = self.L.ls_apply_return_model_moving_host(self.h, C.byref(model), frame_index, None if pose is None else pose.ctypes.data,
+                                                      0 if pose is None else pose.shape[0], arr, n_motions, flags, h.ctypes.data if n else None, n,
+                                                      rho.ctypes.data if rho is not None and rho.size else None, 0 if rho is None else rho.size,
+                                                      pts.ctypes.data if n else None, out.ctypes.data if n else None, C.byref(k))
+        if rc == -1:
+            return -1, pts[:0], out[:0]
+        self._check(rc, "ls_apply_return_model_moving_host")
+        return int(rc), pts[:k.value].copy(), out[:k.value].copy()
+
+    def applyReturnModelMovingDevice(self, model: ReturnModel, d_hits: int, n: int, d_n_out: int, d_points32: int = 0, d_hits_out: int = 0,
+                                     d_col_pose: int = 0, n_cols: int = 0, motions=(), flags: int = 0, d_count: int = 0, d_reflectivity: int = 0,
+                                     n_reflectivity: int = 0, frame_index: int = 0, stream=None) -> int:
+        """ls_apply_return_model_moving on device pointers: applyReturnModelDevice's records and outputs with the tables of
+        traceSweepMovingDevice; enqueued on `stream` (a hipStream_t as an int, None: the handle's), no wait.  -> 0, or -1 on an
+        empty / uncommitted scene (nothing written)."""
+        arr, n_motions = self._device_motions(motions)
+        rc = self.L.ls_apply_return_model_moving(self.h, stream, C.byref(model), frame_index, d_col_pose or None, n_cols, arr, n_motions, flags,
+                                                 d_hits or None, d_count or None, n, d_reflectivity or None, n_reflectivity, d_points32 or None,
+                                                 d_hits_out or None, d_n_out or None)
+        return -1 if rc == -1 else int(self._check(rc, "ls_apply_return_model_moving"))
+
     def traceBeamsHost(self, model: BeamModel, points: bool = True, hits: bool = True, echo: bool = True):
         """A frame of diverging beams with multi-echo returns (ls_trace_scene_beams_host): model.n_samples sub-rays per ray of the
         shard, the returns of every beam in ascending ray index and range.  An output asked for with False comes back None.
@@ -1064,6 +1162,18 @@ def motion_ray(ray8, motion12):
     rc = L.ls_debug_motion_ray(_f32p(r), _f32p(p), _f32p(out))
     if rc != 0:
         raise LidarShooterHipError(f"ls_debug_motion_ray: status {rc}")
+    return out
+
+
+def motion_normal(n3, motion12):
+    """ls_debug_motion_normal: the normal n3 found on a geometry where it was committed, carried forward by one motion record into
+    the sensor frame, on the host -> float32[3]"""
+    L = load()
+    nn, p = np.ascontiguousarray(n3, np.float32).reshape(3), np.ascontiguousarray(motion12, np.float32).reshape(12)
+    out = np.zeros(3, np.float32)
+    rc = L.ls_debug_motion_normal(_f32p(nn), _f32p(p), _f32p(out))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_debug_motion_normal: status {rc}")
     return out
 
 

@@ -160,6 +160,13 @@ int ls_debug_motion_ray(const float ray8_in[8], const float motion12[12], float 
     return LS_OK;
 }
 
+int ls_debug_motion_normal(const float n3[3], const float motion12[12], float out3[3])
+{
+    if (!n3 || !motion12 || !out3) return LS_ERR_INVALID_ARGUMENT;
+    ls::motion_normal(motion12, n3, out3);
+    return LS_OK;
+}
+
 int ls_debug_beam_ray(float sin_theta, float cos_theta, float cos_phi, float sin_phi, const float abk[3], float ray8[8])
 {
     if (!abk || !ray8) return LS_ERR_INVALID_ARGUMENT;

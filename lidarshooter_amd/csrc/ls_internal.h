@@ -7,7 +7,8 @@
 //   ls_trace.cpp     traceScene: output buffers, frames in flight, the per-frame launch sequence, stage timings
 //   ls_query.cpp     ls_trace_rays / ls_occluded_rays / ls_closest_points: the query set of per-geometry hierarchies (built lazily),
 //                    batches of geometries per launch; what every query entry point shares (stream hand-over, staging, read-back)
-//   ls_gather.cpp    ls_hit_attributes: the per-geomID table of its gather kernel; ls_apply_return_model: the same table, its scratch
+//   ls_gather.cpp    ls_hit_attributes: the per-geomID table of its gather kernel; ls_apply_return_model: the same table, its scratch;
+//                    their _moving pairs for the records of ls_trace_scene_sweep_moving (ls_attr_moving.hip): a motion table per geomID
 //   ls_cloud.cpp     ls_format_cloud: the records of a frame as a cloud in a driver's own record (ls_format.hip), its format helpers
 //   ls_scan.cpp      ls_trace_scene_sweep, ls_trace_scene_beams, ls_trace_scene_sweep_moving: their scratch around the queries' walk
 //                    (ls_sweep.hip, ls_beam.hip, ls_moving.hip)
@@ -316,6 +317,13 @@ struct ls_tracer {
         // 256 (every call is ordered through the handle's stream: one call uses them at a time)
         lsi::DevBuf<uint4> park;
         lsi::DevBuf<uint32_t> block_counts;
+        // ls_hit_attributes_moving / ls_apply_return_model_moving: a motion-table pointer per geomID next to `table` (nullptr: at
+        // rest), uploaded the same way by the call that finds it out of date
+        lsi::DevBuf<const float *> motion;
+        std::vector<const float *> motion_current;
+        const float **h_motion_stage = nullptr;
+        size_t motion_stage_cap = 0;
+        hipEvent_t ev_motion_stage = nullptr;
     } ha;
     uint64_t upload_seq = 0;
 
@@ -475,6 +483,9 @@ struct Fetch {
 // on the handle's stream: the count word comes back first (above limit: LS_ERR_HIP with this message), then the outputs; returns
 // when they are filled and *n_out is the count
 int fetch_counted(ls_tracer *tr, const void *d_count, size_t limit, const char *overflow, std::initializer_list<Fetch> outs, uint32_t *n_out);
+// ls_scan.cpp: what ls_trace_scene_sweep_moving refuses of its pose table, flags and motions, in its order (nothing of it needs a
+// commit or the device) -- shared with the gathers over its records (ls_gather.cpp)
+int motion_args_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags);
 #pragma GCC visibility pop
 // ls_gather.cpp
 void hit_attr_release(ls_tracer *tr);

@@ -308,6 +308,20 @@ size_t returns_block_count(uint32_t n);
 void launch_returns(hipStream_t s, const void *hits, const uint32_t *d_count, uint32_t n, const void *rays, uint32_t n_rays, const SensorTables &tb,
                     const AttrGeom *table, uint32_t n_table, const ls_return_model &model, uint32_t frame_index, const float *refl,
                     uint32_t n_refl, void *park, uint32_t *block_counts, void *points32, void *hits_out, uint32_t *n_out);
+// ls_hit_attributes_moving / ls_apply_return_model_moving (ls_attr_moving.hip): the same two gathers over the records of a frame
+// whose sensor and geometries moved during the turn.  hit.ray always indexes the handle's full raster.  pose: the sensor's table of
+// launch_sweep_rays (nullptr: at rest); motion: n_table device pointers next to `table`, indexed by geomID like it -- that geometry's
+// table of launch_trace_rays_moving (H records, 4-byte aligned), nullptr: at rest.  deskew: the points through their column's pose
+// (nothing changes without a table).  launch_returns_eval_moving parks what launch_returns' first kernel parks (park: 2 n 16-byte
+// records, block_counts: returns_block_count(n) words); launch_returns_pack (ls_returns.hip) is that call's second kernel on its
+// own: the ordered compaction of parked records, ring = hit.ray / ring_div (0: ring 0).
+void launch_hit_attributes_moving(hipStream_t s, const void *hits, const uint32_t *d_count, uint32_t n, const SensorTables &tb, const AttrGeom *table,
+                                  const float *const *motion, uint32_t n_table, const float *pose, bool deskew, void *out);
+void launch_returns_eval_moving(hipStream_t s, const void *hits, const uint32_t *d_count, uint32_t n, const SensorTables &tb, const AttrGeom *table,
+                                const float *const *motion, uint32_t n_table, const float *pose, bool deskew, const ls_return_model &model,
+                                uint32_t frame_index, const float *refl, uint32_t n_refl, void *park, uint32_t *block_counts);
+void launch_returns_pack(hipStream_t s, const void *park, const uint32_t *block_counts, const uint32_t *d_count, uint32_t n, uint32_t ring_div,
+                         void *points32, void *hits_out, uint32_t *n_out);
 // ls_trace_scene_sweep (ls_sweep.hip): the shard's rays through the per-column pose table (H records of 12 floats, [R | o] row-major,
 // indexed by the global column) as 32-byte records -- shard-local order in `rays` (what launch_trace_rays reads), and at their
 // global index in rays_out (nullable); then, over the walk's dense ls_hit records of those rays, the ordered pack: 32-byte

@@ -1,6 +1,7 @@
 // ls_motion.h -- the arithmetic of ls_trace_scene_sweep_moving (include/lidarshooter_hip.h) that the kernel
 // (k_trace_rays_moving, ls_moving.hip) and the host (ls_debug_motion_ray, ls_debug.cpp) both compile: ONE float32 operation
-// sequence per (ray, moving geometry).
+// sequence per (ray, moving geometry).  The gather over such a frame's records (ls_attr_moving.hip) rebuilds the same ray with it
+// and carries a normal the other way (motion_normal, below).
 //
 // A motion record is 12 floats, row-major [Q | c]: p[4 i + j] = Q[i][j], p[4 i + 3] = c[i] -- the rigid displacement x_h = Q x_0 + c
 // of a geometry at the moment a column fires, relative to where it was committed, in the handle's sensor frame.  A moved
@@ -38,6 +39,18 @@ LS_SWEEP_HD bool motion_ray_usable(const float *r)
     const float s = ((r[0] - r[0]) + (r[1] - r[1])) + (r[2] - r[2]);   // 0, or a NaN when an entry is not finite
     const float u = ((r[4] - r[4]) + (r[5] - r[5])) + (r[6] - r[6]);
     return s == 0.0f && u == 0.0f && (r[4] != 0.0f || r[5] != 0.0f || r[6] != 0.0f);
+}
+
+// ls_hit_attributes_moving (k_hit_attributes_moving, ls_attr_moving.hip; ls_debug_motion_normal): the way back for a direction.  The
+// unit normal n_g found on the geometry where it was committed, carried forward by the motion record p into the sensor frame:
+//   n_i = (Q[i][0] n_g,0 + Q[i][1] n_g,1) + Q[i][2] n_g,2      two sums, three products, each rounded once
+// An identity record gives n_g back numerically (a -0 component may come back as +0: 0 * y + -0 is +0).  out3 may be n3.
+LS_SWEEP_HD void motion_normal(const float *p, const float *n3, float *out3)
+{
+    const float n0 = n3[0], n1 = n3[1], n2 = n3[2];
+    out3[0] = (p[0] * n0 + p[1] * n1) + p[2] * n2;
+    out3[1] = (p[4] * n0 + p[5] * n1) + p[6] * n2;
+    out3[2] = (p[8] * n0 + p[9] * n1) + p[10] * n2;
 }
 
 }  // namespace ls

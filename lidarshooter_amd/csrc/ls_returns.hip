@@ -159,4 +159,15 @@ void launch_returns(hipStream_t s, const void *hits, const uint32_t *d_count, ui
                        static_cast<float4 *>(points32), static_cast<uint4 *>(hits_out), n_out);
 }
 
+// k_returns_pack alone, over records another kernel parked in k_returns_eval's layout (k_returns_eval_moving, ls_attr_moving.hip)
+void launch_returns_pack(hipStream_t s, const void *park, const uint32_t *block_counts, const uint32_t *d_count, uint32_t n, uint32_t ring_div,
+                         void *points32, void *hits_out, uint32_t *n_out)
+{
+    if (!n) return;
+    const float4 *park_point = static_cast<const float4 *>(park);
+    const uint4 *park_hit = reinterpret_cast<const uint4 *>(park_point + n);
+    hipLaunchKernelGGL(k_returns_pack, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, park_point, park_hit, block_counts, d_count, n, ring_div,
+                       static_cast<float4 *>(points32), static_cast<uint4 *>(hits_out), n_out);
+}
+
 }  // namespace ls

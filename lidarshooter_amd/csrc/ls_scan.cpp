@@ -17,6 +17,24 @@
 
 namespace lsi {
 
+int motion_args_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags)
+{
+    if (col_pose ? n_cols != tr->H : n_cols != 0u)
+        return fail(tr, LS_ERR_INVALID_ARGUMENT, "one pose per azimuth column of the full raster (LS_INFO_AZIMUTH_COUNT), or no table and n_cols 0");
+    if (flags & ~(uint32_t)LS_SWEEP_DESKEW) return fail(tr, LS_ERR_INVALID_ARGUMENT, "unknown sweep flags");
+    if (n_motions && !motions) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null motions with n_motions > 0");
+    for (uint32_t k = 0; k < n_motions; ++k)
+        if (!motions[k].col_motion) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a motion without a table");
+    for (uint32_t k = 0; k < n_motions; ++k)
+        if (motions[k].reserved) return fail(tr, LS_ERR_INVALID_ARGUMENT, "ls_geometry_motion.reserved must be 0");
+    if (n_motions > tr->geoms.size()) return fail(tr, LS_ERR_INVALID_ARGUMENT, "more motions than geometries");
+    std::vector<uint32_t> ids(n_motions);
+    for (uint32_t k = 0; k < n_motions; ++k) ids[k] = motions[k].geom;
+    std::sort(ids.begin(), ids.end());
+    if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a geometry named by two motions");
+    return LS_OK;
+}
+
 namespace {
 
 // what both sweep entry points refuse, in this order (none of it needs a commit); host memory may have any alignment
@@ -149,19 +167,7 @@ int moving_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, const ls
 {
     if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
     if (!n_points) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null count output");
-    if (col_pose ? n_cols != tr->H : n_cols != 0u)
-        return fail(tr, LS_ERR_INVALID_ARGUMENT, "one pose per azimuth column of the full raster (LS_INFO_AZIMUTH_COUNT), or no table and n_cols 0");
-    if (flags & ~(uint32_t)LS_SWEEP_DESKEW) return fail(tr, LS_ERR_INVALID_ARGUMENT, "unknown sweep flags");
-    if (n_motions && !motions) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null motions with n_motions > 0");
-    for (uint32_t k = 0; k < n_motions; ++k)
-        if (!motions[k].col_motion) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a motion without a table");
-    for (uint32_t k = 0; k < n_motions; ++k)
-        if (motions[k].reserved) return fail(tr, LS_ERR_INVALID_ARGUMENT, "ls_geometry_motion.reserved must be 0");
-    if (n_motions > tr->geoms.size()) return fail(tr, LS_ERR_INVALID_ARGUMENT, "more motions than geometries");
-    std::vector<uint32_t> ids(n_motions);
-    for (uint32_t k = 0; k < n_motions; ++k) ids[k] = motions[k].geom;
-    std::sort(ids.begin(), ids.end());
-    if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a geometry named by two motions");
+    if (const int rc = motion_args_check(tr, col_pose, n_cols, motions, n_motions, flags)) return rc;
     if (!host) {
         bool bad = misaligned(col_pose, 4) || misaligned(n_points, 4) || misaligned16(points32, hits);
         for (uint32_t k = 0; k < n_motions; ++k) bad = bad || misaligned(motions[k].col_motion, 4);
