@@ -348,20 +348,52 @@ def _u32p(a):
 IDENTITY_AFFINE = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32)
 
 
+def _floats(a, n):
+    return (C.c_float * n)(*[float(x) for x in np.asarray(a, np.float32).reshape(n)])
+
+
+def _sensor_desc(vert, h_begin, h_end, h_count, Rinv, t) -> SensorDesc:
+    """ls_sensor_desc over `vert`, a contiguous float32 array the caller keeps alive"""
+    sd = SensorDesc()
+    sd.vertical_deg, sd.n_vertical = _f32p(vert), vert.shape[0]
+    sd.h_begin, sd.h_end, sd.h_count = float(h_begin), float(h_end), int(h_count)
+    sd.Rinv, sd.t = _floats(Rinv, 9), _floats(t, 3)
+    return sd
+
+
+def _sensor_tables(tabs, h_begin_deg, h_step_deg, Rinv, t) -> SensorTables:
+    """ls_sensor_tables over `tabs` (sin_theta, cos_theta, elevation_deg, sin_phi, cos_phi), contiguous float32 arrays the caller
+    keeps alive"""
+    st = SensorTables()
+    st.sin_theta, st.cos_theta, st.elevation_deg, st.sin_phi, st.cos_phi = [_f32p(a) for a in tabs]
+    st.n_vertical, st.h_count = tabs[0].shape[0], tabs[3].shape[0]
+    st.h_begin_deg, st.h_step_deg = float(h_begin_deg), float(h_step_deg)
+    st.Rinv, st.t = _floats(Rinv, 9), _floats(t, 3)
+    return st
+
+
+class _Outputs:
+    """The outputs of a host-memory call that counts its records: of points uint8 (n, 32), hits HIT_DTYPE (n,) and echo words uint32
+    (n,), in this order, those asked for with True (None stands for one that is not); `k` takes the count."""
+    _KINDS = (((32,), np.uint8), ((), HIT_DTYPE), ((), np.uint32))
+
+    def __init__(self, n: int, *wanted: bool):
+        self.arrays = tuple(np.zeros((n,) + shape, dtype) if w else None for w, (shape, dtype) in zip(wanted, self._KINDS))
+        self.ptrs = tuple(a.ctypes.data if a is not None and n else None for a in self.arrays)
+        self.k = C.c_uint32(0)
+
+    def first(self, k: int) -> tuple:
+        return tuple(None if a is None else a[:k].copy() for a in self.arrays)
+
+
 class Tracer:
     """Thin object wrapper over an ls_tracer handle; method names follow ITracer."""
 
     def __init__(self, vertical_deg, h_begin, h_end, h_count, Rinv, t, device: int = 0):
         self.L = load()
         self._vert = np.ascontiguousarray(vertical_deg, np.float32)
-        sd = SensorDesc()
-        sd.vertical_deg = _f32p(self._vert)
-        sd.n_vertical = self._vert.shape[0]
-        sd.h_begin, sd.h_end, sd.h_count = float(h_begin), float(h_end), int(h_count)
-        sd.Rinv = (C.c_float * 9)(*[float(x) for x in np.asarray(Rinv, np.float32).reshape(9)])
-        sd.t = (C.c_float * 3)(*[float(x) for x in np.asarray(t, np.float32).reshape(3)])
-        self.V, self.H = int(sd.n_vertical), int(h_count)
-        self.az0, self.naz = 0, self.H
+        sd = _sensor_desc(self._vert, h_begin, h_end, h_count, Rinv, t)
+        self._raster(sd.n_vertical, h_count)
         h = C.c_void_p()
         rc = self.L.ls_tracer_create(C.byref(sd), device, C.byref(h))
         if rc != 0:
@@ -375,14 +407,8 @@ class Tracer:
         self = cls.__new__(cls)
         self.L = load()
         self._tabs = [np.ascontiguousarray(a, np.float32) for a in (sin_theta, cos_theta, elevation_deg, sin_phi, cos_phi)]
-        st = SensorTables()
-        st.sin_theta, st.cos_theta, st.elevation_deg, st.sin_phi, st.cos_phi = [_f32p(a) for a in self._tabs]
-        st.n_vertical, st.h_count = self._tabs[0].shape[0], self._tabs[3].shape[0]
-        st.h_begin_deg, st.h_step_deg = float(h_begin_deg), float(h_step_deg)
-        st.Rinv = (C.c_float * 9)(*[float(x) for x in np.asarray(Rinv, np.float32).reshape(9)])
-        st.t = (C.c_float * 3)(*[float(x) for x in np.asarray(t, np.float32).reshape(3)])
-        self.V, self.H = int(st.n_vertical), int(st.h_count)
-        self.az0, self.naz = 0, self.H
+        st = _sensor_tables(self._tabs, h_begin_deg, h_step_deg, Rinv, t)
+        self._raster(st.n_vertical, st.h_count)
         h = C.c_void_p()
         rc = self.L.ls_tracer_create_tables(C.byref(st), device, C.byref(h))
         if rc != 0:
@@ -390,32 +416,24 @@ class Tracer:
         self.h = h
         return self
 
+    def _raster(self, V, H):
+        self.V, self.H = int(V), int(H)
+        self.az0, self.naz = 0, self.H
+
     def setSensorTables(self, sin_theta, cos_theta, elevation_deg, sin_phi, cos_phi, h_begin_deg, h_step_deg, Rinv, t):
         """ls_tracer_set_sensor_tables: another sensor, given as factor tables, for this handle (its geometries stay)"""
         tabs = [np.ascontiguousarray(a, np.float32) for a in (sin_theta, cos_theta, elevation_deg, sin_phi, cos_phi)]
-        st = SensorTables()
-        st.sin_theta, st.cos_theta, st.elevation_deg, st.sin_phi, st.cos_phi = [_f32p(a) for a in tabs]
-        st.n_vertical, st.h_count = tabs[0].shape[0], tabs[3].shape[0]
-        st.h_begin_deg, st.h_step_deg = float(h_begin_deg), float(h_step_deg)
-        st.Rinv = (C.c_float * 9)(*[float(x) for x in np.asarray(Rinv, np.float32).reshape(9)])
-        st.t = (C.c_float * 3)(*[float(x) for x in np.asarray(t, np.float32).reshape(3)])
+        st = _sensor_tables(tabs, h_begin_deg, h_step_deg, Rinv, t)
         self._check(self.L.ls_tracer_set_sensor_tables(self.h, C.byref(st)), "ls_tracer_set_sensor_tables")
         self._tabs = tabs
-        self.V, self.H = int(st.n_vertical), int(st.h_count)
-        self.az0, self.naz = 0, self.H
+        self._raster(st.n_vertical, st.h_count)
 
     def setSensor(self, vertical_deg, h_begin, h_end, h_count, Rinv, t):
         """ITracer::setSensorConfig: another sensor for this handle, its geometries stay (ls_tracer_set_sensor)"""
         self._vert = np.ascontiguousarray(vertical_deg, np.float32)
-        sd = SensorDesc()
-        sd.vertical_deg = _f32p(self._vert)
-        sd.n_vertical = self._vert.shape[0]
-        sd.h_begin, sd.h_end, sd.h_count = float(h_begin), float(h_end), int(h_count)
-        sd.Rinv = (C.c_float * 9)(*[float(x) for x in np.asarray(Rinv, np.float32).reshape(9)])
-        sd.t = (C.c_float * 3)(*[float(x) for x in np.asarray(t, np.float32).reshape(3)])
+        sd = _sensor_desc(self._vert, h_begin, h_end, h_count, Rinv, t)
         self._check(self.L.ls_tracer_set_sensor(self.h, C.byref(sd)), "ls_tracer_set_sensor")
-        self.V, self.H = int(sd.n_vertical), int(h_count)
-        self.az0, self.naz = 0, self.H
+        self._raster(sd.n_vertical, h_count)
 
     # ---- lifetime
     def close(self):
@@ -695,25 +713,78 @@ class Tracer:
         rc = self.L.ls_closest_points(self.h, stream, d_points, n, d_out)
         return -1 if rc == -1 else int(self._check(rc, "ls_closest_points"))
 
-    def hitAttributes(self, hits, rays=None):
-        """Surface attributes of hit records (ls_hit_attributes_host): `hits` a HIT_DTYPE array (a frame's, or traceRays'), `rays`
-        None -- the handle's own sensor rays, hit.ray the global ray index -- or the rays given to traceRays (float32 (n, 8) or
-        RAY_DTYPE).  -> (rc, HIT_ATTR_DTYPE[n]); rc = -1 (no commit, empty scene): every record invalid."""
+    @staticmethod
+    def _hit_array(hits):
         h = np.ascontiguousarray(hits)
         if h.dtype != HIT_DTYPE:
             h = np.ascontiguousarray(h, np.uint32)
             if h.ndim != 2 or h.shape[1] != 4:
                 raise ValueError("hits: HIT_DTYPE or uint32 (n, 4)")
-        n = h.shape[0]
-        r = None if rays is None else self._ray_array(rays)
-        out = np.zeros(n, HIT_ATTR_DTYPE)
-        rc = self.L.ls_hit_attributes_host(self.h, None if r is None else (r.ctypes.data if r.shape[0] else h.ctypes.data),
-                                           0 if r is None else r.shape[0], h.ctypes.data if n else None, n, out.ctypes.data if n else None)
+        return h
+
+    @staticmethod
+    def _pose_array(col_pose):
+        pose = np.ascontiguousarray(col_pose, np.float32)
+        if pose.ndim != 2 or pose.shape[1] != 12:
+            raise ValueError("col_pose: float32 (H, 12)")
+        return pose
+
+    def _host_tables(self, col_pose, motions):
+        """the pose table and the motion tables of traceSweepMoving as the _host entry points take them -> (the pose table's
+        address or None, its length, the ls_geometry_motion array or None, its length, what keeps the tables alive)"""
+        pose = None if col_pose is None else self._pose_array(col_pose)
+        tabs = {int(g): np.ascontiguousarray(t, np.float32) for g, t in dict(motions).items()}
+        H = self.info(LS_INFO_AZIMUTH_COUNT)
+        if any(t.shape != (H, 12) for t in tabs.values()):
+            raise ValueError("motions: float32 (H, 12) per geometry")
+        arr, n_motions = self._device_motions({g: t.ctypes.data for g, t in tabs.items()})
+        return None if pose is None else pose.ctypes.data, 0 if pose is None else pose.shape[0], arr, n_motions, (pose, tabs)
+
+    @staticmethod
+    def _device_motions(motions):
+        items = list(dict(motions).items())
+        arr = (GeometryMotion * max(1, len(items)))()
+        for m, (g, addr) in zip(arr, items):
+            m.geom, m.reserved, m.col_motion = int(g), 0, int(addr)
+        return (arr if items else None), len(items)
+
+    @staticmethod
+    def _rays_arg(r, h):
+        """the caller's rays as the gathers take them -> (address, count): none -- the handle's own sensor rays -- is (None, 0);
+        rays given, but none of them, keep an address"""
+        return (None, 0) if r is None else (r.ctypes.data if r.shape[0] else h.ctypes.data, r.shape[0])
+
+    @staticmethod
+    def _refl_arg(reflectivity):
+        """-> (address or None, count, what keeps it alive)"""
+        rho = None if reflectivity is None else np.ascontiguousarray(reflectivity, np.float32).reshape(-1)
+        return rho.ctypes.data if rho is not None and rho.size else None, 0 if rho is None else rho.size, rho
+
+    def _records(self, rc, what, o: _Outputs, count: bool = True):
+        """what a call with _Outputs returns: (rc[, k], the first k records of every output); rc = -1: none of them"""
+        if rc != -1:
+            self._check(rc, what)
+        k = 0 if rc == -1 else int(o.k.value)
+        return (int(rc),) + ((k,) if count else ()) + o.first(k)
+
+    def _attributes(self, rc, what, h, out):
+        """what the attribute calls return: (rc, out); rc = -1: every record invalid, with its ray"""
         if rc == -1:
             out["ray"] = h["ray"] if h.dtype == HIT_DTYPE else h[:, 0]
             return -1, out
-        self._check(rc, "ls_hit_attributes_host")
+        self._check(rc, what)
         return int(rc), out
+
+    def hitAttributes(self, hits, rays=None):
+        """Surface attributes of hit records (ls_hit_attributes_host): `hits` a HIT_DTYPE array (a frame's, or traceRays'), `rays`
+        None -- the handle's own sensor rays, hit.ray the global ray index -- or the rays given to traceRays (float32 (n, 8) or
+        RAY_DTYPE).  -> (rc, HIT_ATTR_DTYPE[n]); rc = -1 (no commit, empty scene): every record invalid."""
+        h = self._hit_array(hits)
+        n = h.shape[0]
+        r = None if rays is None else self._ray_array(rays)
+        out = np.zeros(n, HIT_ATTR_DTYPE)
+        rc = self.L.ls_hit_attributes_host(self.h, *self._rays_arg(r, h), h.ctypes.data if n else None, n, out.ctypes.data if n else None)
+        return self._attributes(rc, "ls_hit_attributes_host", h, out)
 
     def hitAttributesDevice(self, d_hits: int, n: int, d_out: int, d_rays: int = 0, n_rays: int = 0, d_count: int = 0, stream=None) -> int:
         """ls_hit_attributes on device pointers (n 16-byte ls_hit records in, 48-byte records out; d_rays = 0: the handle's sensor
@@ -726,23 +797,14 @@ class Tracer:
         """Sensor returns from hit records (ls_apply_return_model_host): `hits` and `rays` as hitAttributes takes them, `reflectivity`
         None or float32 per geomID.  -> (rc, points uint8[k, 32], hits HIT_DTYPE[k] with the noisy t): the kept returns in input
         order; rc = -1 (no commit, empty scene): none."""
-        h = np.ascontiguousarray(hits)
-        if h.dtype != HIT_DTYPE:
-            h = np.ascontiguousarray(h, np.uint32)
-            if h.ndim != 2 or h.shape[1] != 4:
-                raise ValueError("hits: HIT_DTYPE or uint32 (n, 4)")
+        h = self._hit_array(hits)
         n = h.shape[0]
         r = None if rays is None else self._ray_array(rays)
-        rho = None if reflectivity is None else np.ascontiguousarray(reflectivity, np.float32).reshape(-1)
-        pts, out, k = np.zeros((n, 32), np.uint8), np.zeros(n, HIT_DTYPE), C.c_uint32(0)
-        rc = self.L.ls_apply_return_model_host(self.h, C.byref(model), frame_index,
-                                               None if r is None else (r.ctypes.data if r.shape[0] else h.ctypes.data), 0 if r is None else r.shape[0],
-                                               h.ctypes.data if n else None, n, rho.ctypes.data if rho is not None and rho.size else None,
-                                               0 if rho is None else rho.size, pts.ctypes.data if n else None, out.ctypes.data if n else None, C.byref(k))
-        if rc == -1:
-            return -1, pts[:0], out[:0]
-        self._check(rc, "ls_apply_return_model_host")
-        return int(rc), pts[:k.value].copy(), out[:k.value].copy()
+        rho, n_rho, keep = self._refl_arg(reflectivity)
+        o = _Outputs(n, True, True)
+        rc = self.L.ls_apply_return_model_host(self.h, C.byref(model), frame_index, *self._rays_arg(r, h), h.ctypes.data if n else None, n, rho, n_rho,
+                                               *o.ptrs, C.byref(o.k))
+        return self._records(rc, "ls_apply_return_model_host", o, count=False)
 
     def applyReturnModelDevice(self, model: ReturnModel, d_hits: int, n: int, d_n_out: int, d_points32: int = 0, d_hits_out: int = 0, d_rays: int = 0,
                                n_rays: int = 0, d_count: int = 0, d_reflectivity: int = 0, n_reflectivity: int = 0, frame_index: int = 0,
@@ -761,23 +823,15 @@ class Tracer:
         `points` / `hits` False: that output is not asked for (None comes back); `rays_out` None, or a RAY_DTYPE / float32 (V * H, 8)
         array of the full raster whose shard records are overwritten in place.  -> (rc, k, points uint8[k, 32] or None, hits
         HIT_DTYPE[k] or None); rc = -1 (no commit, empty scene): no record."""
-        pose = np.ascontiguousarray(col_pose, np.float32)
-        if pose.ndim != 2 or pose.shape[1] != 12:
-            raise ValueError("col_pose: float32 (H, 12)")
+        pose = self._pose_array(col_pose)
         if rays_out is not None and not (isinstance(rays_out, np.ndarray) and rays_out.flags.c_contiguous and rays_out.flags.writeable and
                                          rays_out.nbytes == 32 * int(self.L.ls_total_channels(self.h)) * self.info(LS_INFO_AZIMUTH_COUNT)):
             raise ValueError("rays_out: a writable contiguous array of V * H 32-byte records")
         n = self.getTotalRays()
-        pts = np.zeros((n, 32), np.uint8) if points else None
-        out = np.zeros(n, HIT_DTYPE) if hits else None
-        k = C.c_uint32(0)
-        rc = self.L.ls_trace_scene_sweep_host(self.h, pose.ctypes.data if pose.size else None, pose.shape[0], flags,
-                                              pts.ctypes.data if points else None, out.ctypes.data if hits else None, C.byref(k), n,
+        o = _Outputs(n, points, hits)
+        rc = self.L.ls_trace_scene_sweep_host(self.h, pose.ctypes.data if pose.size else None, pose.shape[0], flags, *o.ptrs, C.byref(o.k), n,
                                               None if rays_out is None else rays_out.ctypes.data)
-        if rc == -1:
-            return -1, 0, (pts[:0] if points else None), (out[:0] if hits else None)
-        self._check(rc, "ls_trace_scene_sweep_host")
-        return int(rc), int(k.value), (pts[:k.value].copy() if points else None), (out[:k.value].copy() if hits else None)
+        return self._records(rc, "ls_trace_scene_sweep_host", o)
 
     def traceSweepDevice(self, d_col_pose: int, n_cols: int, d_n_points: int, capacity: int, d_points32: int = 0, d_hits: int = 0,
                          d_rays_out: int = 0, flags: int = 0, stream=None) -> int:
@@ -794,72 +848,21 @@ class Tracer:
         None: the sensor at rest; `motions` a dict geomID -> float32 (H, 12) table [Q | c] row-major, the rigid displacement of that
         geometry when azimuth column h fires, relative to where it was committed, in the frame-start sensor frame (geometries not
         named are at rest).  -> (rc, k, points uint8[k, 32] or None, hits HIT_DTYPE[k] or None); rc = -1: no record."""
-        pose = None if col_pose is None else np.ascontiguousarray(col_pose, np.float32)
-        if pose is not None and (pose.ndim != 2 or pose.shape[1] != 12):
-            raise ValueError("col_pose: float32 (H, 12)")
-        tabs = {int(g): np.ascontiguousarray(t, np.float32) for g, t in dict(motions).items()}
-        H = self.info(LS_INFO_AZIMUTH_COUNT)
-        if any(t.shape != (H, 12) for t in tabs.values()):
-            raise ValueError("motions: float32 (H, 12) per geometry")
-        arr = (GeometryMotion * max(1, len(tabs)))()
-        for m, (g, t) in zip(arr, tabs.items()):
-            m.geom, m.reserved, m.col_motion = g, 0, t.ctypes.data
+        *tables, keep = self._host_tables(col_pose, motions)
         n = self.getTotalRays()
-        pts = np.zeros((n, 32), np.uint8) if points else None
-        out = np.zeros(n, HIT_DTYPE) if hits else None
-        k = C.c_uint32(0)
-        rc = self.L.ls_trace_scene_sweep_moving_host(self.h, None if pose is None else pose.ctypes.data, 0 if pose is None else pose.shape[0],
-                                                     arr if tabs else None, len(tabs), flags, pts.ctypes.data if points else None,
-                                                     out.ctypes.data if hits else None, C.byref(k), n)
-        if rc == -1:
-            return -1, 0, (pts[:0] if points else None), (out[:0] if hits else None)
-        self._check(rc, "ls_trace_scene_sweep_moving_host")
-        return int(rc), int(k.value), (pts[:k.value].copy() if points else None), (out[:k.value].copy() if hits else None)
+        o = _Outputs(n, points, hits)
+        rc = self.L.ls_trace_scene_sweep_moving_host(self.h, *tables, flags, *o.ptrs, C.byref(o.k), n)
+        return self._records(rc, "ls_trace_scene_sweep_moving_host", o)
 
     def traceSweepMovingDevice(self, d_col_pose: int, n_cols: int, motions, d_n_points: int, capacity: int, d_points32: int = 0,
                                d_hits: int = 0, flags: int = 0, stream=None) -> int:
         """ls_trace_scene_sweep_moving on device pointers: traceSweepDevice (d_col_pose 0 with n_cols 0: the sensor at rest) with
         `motions`, a dict geomID -> device address of that geometry's H 48-byte records; enqueued on `stream` (a hipStream_t as an
         int, None: the handle's), no wait.  -> 0, or -1 on an empty / uncommitted scene (nothing written)."""
-        items = list(dict(motions).items())
-        arr = (GeometryMotion * max(1, len(items)))()
-        for m, (g, addr) in zip(arr, items):
-            m.geom, m.reserved, m.col_motion = int(g), 0, int(addr)
-        rc = self.L.ls_trace_scene_sweep_moving(self.h, stream, d_col_pose or None, n_cols, arr if items else None, len(items), flags,
-                                                d_points32 or None, d_hits or None, d_n_points or None, capacity)
+        arr, n_motions = self._device_motions(motions)
+        rc = self.L.ls_trace_scene_sweep_moving(self.h, stream, d_col_pose or None, n_cols, arr, n_motions, flags, d_points32 or None, d_hits or None,
+                                                d_n_points or None, capacity)
         return -1 if rc == -1 else int(self._check(rc, "ls_trace_scene_sweep_moving"))
-
-    @staticmethod
-    def _hit_array(hits):
-        h = np.ascontiguousarray(hits)
-        if h.dtype != HIT_DTYPE:
-            h = np.ascontiguousarray(h, np.uint32)
-            if h.ndim != 2 or h.shape[1] != 4:
-                raise ValueError("hits: HIT_DTYPE or uint32 (n, 4)")
-        return h
-
-    def _host_tables(self, col_pose, motions):
-        """the pose table and the motion tables of traceSweepMoving as the _host entry points take them -> (pose or None, the
-        ls_geometry_motion array or None, its length, what keeps the tables alive)"""
-        pose = None if col_pose is None else np.ascontiguousarray(col_pose, np.float32)
-        if pose is not None and (pose.ndim != 2 or pose.shape[1] != 12):
-            raise ValueError("col_pose: float32 (H, 12)")
-        tabs = {int(g): np.ascontiguousarray(t, np.float32) for g, t in dict(motions).items()}
-        H = self.info(LS_INFO_AZIMUTH_COUNT)
-        if any(t.shape != (H, 12) for t in tabs.values()):
-            raise ValueError("motions: float32 (H, 12) per geometry")
-        arr = (GeometryMotion * max(1, len(tabs)))()
-        for m, (g, t) in zip(arr, tabs.items()):
-            m.geom, m.reserved, m.col_motion = g, 0, t.ctypes.data
-        return pose, (arr if tabs else None), len(tabs), tabs
-
-    @staticmethod
-    def _device_motions(motions):
-        items = list(dict(motions).items())
-        arr = (GeometryMotion * max(1, len(items)))()
-        for m, (g, addr) in zip(arr, items):
-            m.geom, m.reserved, m.col_motion = int(g), 0, int(addr)
-        return (arr if items else None), len(items)
 
     def hitAttributesMoving(self, hits, col_pose, motions, flags: int = 0):
         """Surface attributes of the records of a sweep frame (ls_hit_attributes_moving_host): `hits` a HIT_DTYPE array of
@@ -868,15 +871,10 @@ class Tracer:
         record invalid."""
         h = self._hit_array(hits)
         n = h.shape[0]
-        pose, arr, n_motions, keep = self._host_tables(col_pose, motions)
+        *tables, keep = self._host_tables(col_pose, motions)
         out = np.zeros(n, HIT_ATTR_DTYPE)
-        rc = self.L.ls_hit_attributes_moving_host(self.h, None if pose is None else pose.ctypes.data, 0 if pose is None else pose.shape[0], arr,
-                                                  n_motions, flags, h.ctypes.data if n else None, n, out.ctypes.data if n else None)
-        if rc == -1:
-            out["ray"] = h["ray"] if h.dtype == HIT_DTYPE else h[:, 0]
-            return -1, out
-        self._check(rc, "ls_hit_attributes_moving_host")
-        return int(rc), out
+        rc = self.L.ls_hit_attributes_moving_host(self.h, *tables, flags, h.ctypes.data if n else None, n, out.ctypes.data if n else None)
+        return self._attributes(rc, "ls_hit_attributes_moving_host", h, out)
 
     def hitAttributesMovingDevice(self, d_hits: int, n: int, d_out: int, d_col_pose: int = 0, n_cols: int = 0, motions=(), flags: int = 0,
                                   d_count: int = 0, stream=None) -> int:
@@ -895,17 +893,12 @@ class Tracer:
         their ring, hits HIT_DTYPE[k] with the noisy t): the kept returns in input order; rc = -1: none."""
         h = self._hit_array(hits)
         n = h.shape[0]
-        pose, arr, n_motions, keep = self._host_tables(col_pose, motions)
-        rho = None if reflectivity is None else np.ascontiguousarray(reflectivity, np.float32).reshape(-1)
-        pts, out, k = np.zeros((n, 32), np.uint8), np.zeros(n, HIT_DTYPE), C.c_uint32(0)
-        rc = self.L.ls_apply_return_model_moving_host(self.h, C.byref(model), frame_index, None if pose is None else pose.ctypes.data,
-                                                      0 if pose is None else pose.shape[0], arr, n_motions, flags, h.ctypes.data if n else None, n,
-                                                      rho.ctypes.data if rho is not None and rho.size else None, 0 if rho is None else rho.size,
-                                                      pts.ctypes.data if n else None, out.ctypes.data if n else None, C.byref(k))
-        if rc == -1:
-            return -1, pts[:0], out[:0]
-        self._check(rc, "ls_apply_return_model_moving_host")
-        return int(rc), pts[:k.value].copy(), out[:k.value].copy()
+        *tables, keep = self._host_tables(col_pose, motions)
+        rho, n_rho, keep_rho = self._refl_arg(reflectivity)
+        o = _Outputs(n, True, True)
+        rc = self.L.ls_apply_return_model_moving_host(self.h, C.byref(model), frame_index, *tables, flags, h.ctypes.data if n else None, n, rho, n_rho,
+                                                      *o.ptrs, C.byref(o.k))
+        return self._records(rc, "ls_apply_return_model_moving_host", o, count=False)
 
     def applyReturnModelMovingDevice(self, model: ReturnModel, d_hits: int, n: int, d_n_out: int, d_points32: int = 0, d_hits_out: int = 0,
                                      d_col_pose: int = 0, n_cols: int = 0, motions=(), flags: int = 0, d_count: int = 0, d_reflectivity: int = 0,
@@ -925,17 +918,9 @@ class Tracer:
         -> (rc, k, points uint8[k, 32] or None, hits HIT_DTYPE[k] or None -- t the reported range --, echo words uint32[k] or
         None); rc = -1 (no commit, empty scene): no record."""
         cap = model.n_returns * self.getTotalRays()
-        pts = np.zeros((cap, 32), np.uint8) if points else None
-        out = np.zeros(cap, HIT_DTYPE) if hits else None
-        ew = np.zeros(cap, np.uint32) if echo else None
-        k = C.c_uint32(0)
-        rc = self.L.ls_trace_scene_beams_host(self.h, C.byref(model), pts.ctypes.data if points else None, out.ctypes.data if hits else None,
-                                              ew.ctypes.data if echo else None, C.byref(k), cap)
-        if rc == -1:
-            return -1, 0, (pts[:0] if points else None), (out[:0] if hits else None), (ew[:0] if echo else None)
-        self._check(rc, "ls_trace_scene_beams_host")
-        n = int(k.value)
-        return int(rc), n, (pts[:n].copy() if points else None), (out[:n].copy() if hits else None), (ew[:n].copy() if echo else None)
+        o = _Outputs(cap, points, hits, echo)
+        rc = self.L.ls_trace_scene_beams_host(self.h, C.byref(model), *o.ptrs, C.byref(o.k), cap)
+        return self._records(rc, "ls_trace_scene_beams_host", o)
 
     def traceBeamsDevice(self, model: BeamModel, d_n_points: int, capacity: int, d_points32: int = 0, d_hits: int = 0, d_echo: int = 0,
                          stream=None) -> int:
@@ -955,23 +940,13 @@ class Tracer:
         w = None if weights is None else np.ascontiguousarray(weights, np.uint32).reshape(-1)
         if w is not None and w.shape[0] != model.n_samples:
             raise ValueError("weights: one per sample of the model")
-        pose = None if col_pose is None else np.ascontiguousarray(col_pose, np.float32)
-        if pose is not None and (pose.ndim != 2 or pose.shape[1] != 12):
-            raise ValueError("col_pose: float32 (H, 12)")
+        pose = None if col_pose is None else self._pose_array(col_pose)
         cap = model.n_returns * self.getTotalRays()
-        pts = np.zeros((cap, 32), np.uint8) if points else None
-        out = np.zeros(cap, HIT_DTYPE) if hits else None
-        ew = np.zeros(cap, np.uint32) if echo else None
-        k = C.c_uint32(0)
+        o = _Outputs(cap, points, hits, echo)
         rc = self.L.ls_trace_scene_beams_sweep_host(self.h, C.byref(model), None if w is None else _u32p(w), int(min_weight),
                                                     pose.ctypes.data if pose is not None and pose.size else None, 0 if pose is None else pose.shape[0],
-                                                    flags, pts.ctypes.data if points else None, out.ctypes.data if hits else None,
-                                                    ew.ctypes.data if echo else None, C.byref(k), cap)
-        if rc == -1:
-            return -1, 0, (pts[:0] if points else None), (out[:0] if hits else None), (ew[:0] if echo else None)
-        self._check(rc, "ls_trace_scene_beams_sweep_host")
-        n = int(k.value)
-        return int(rc), n, (pts[:n].copy() if points else None), (out[:n].copy() if hits else None), (ew[:n].copy() if echo else None)
+                                                    flags, *o.ptrs, C.byref(o.k), cap)
+        return self._records(rc, "ls_trace_scene_beams_sweep_host", o)
 
     def traceBeamsSweepDevice(self, model: BeamModel, d_n_points: int, capacity: int, d_points32: int = 0, d_hits: int = 0, d_echo: int = 0,
                               weights=None, min_weight: int = 0, d_col_pose: int = 0, n_cols: int = 0, flags: int = 0, stream=None) -> int:
@@ -992,11 +967,7 @@ class Tracer:
         points that belong to them (None when the format names none of x, y, z, intensity), `echo` None or uint32 (n,), `col_time`
         None or float32 (H,), `chan_time` None or float32 (V,).  -> uint8 (n, point_step), or (V * H, point_step) organized.  Needs
         no committed scene."""
-        h = np.ascontiguousarray(hits)
-        if h.dtype != HIT_DTYPE:
-            h = np.ascontiguousarray(h, np.uint32)
-            if h.ndim != 2 or h.shape[1] != 4:
-                raise ValueError("hits: HIT_DTYPE or uint32 (n, 4)")
+        h = self._hit_array(hits)
         n = h.shape[0]
         p = None if points is None else np.ascontiguousarray(points, np.uint8).reshape(-1, 32)
         e = None if echo is None else np.ascontiguousarray(echo, np.uint32).reshape(-1)

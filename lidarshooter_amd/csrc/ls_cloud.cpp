@@ -92,9 +92,7 @@ int ls_format_cloud(ls_tracer *tr, void *hip_stream, const ls_cloud_format *fmt,
     LS_ENTER_CHECKED(tr, format_check(tr, fmt, d_points32, d_hits, d_echo, d_count, n, d_col_time, d_chan_time, d_out, false));
     if (!n && !(fmt->flags & LS_CLOUD_ORGANIZED)) return LS_OK;
     const hipStream_t s = stream_of(tr, hip_stream);
-    int rc;
-    if ((rc = query_enter(tr, s)) || (rc = format_issue(tr, s, fmt, d_points32, d_hits, d_echo, d_count, n, d_col_time, d_chan_time, d_out))) return rc;
-    return query_leave(tr, s);
+    return query_run(tr, s, [&] { return format_issue(tr, s, fmt, d_points32, d_hits, d_echo, d_count, n, d_col_time, d_chan_time, d_out); });
 }
 
 // records, tables and the cloud staged in q.io, on the handle's stream; returns when out is filled
@@ -104,30 +102,19 @@ int ls_format_cloud_host(ls_tracer *tr, const ls_cloud_format *fmt, const void *
     LS_ENTER_CHECKED(tr, format_check(tr, fmt, points32, hits, echo, nullptr, n, col_time, chan_time, out, true));
     const bool organized = (fmt->flags & LS_CLOUD_ORGANIZED) != 0;
     if (!n && !organized) return LS_OK;
-    DevBuf<uint8_t> &buf = tr->rq.io;
     const hipStream_t s = tr->stream;
     int rc;
     if ((rc = query_enter(tr, s))) return rc;
-    IoPlan io;
-    const size_t hit_bytes = (size_t)n * 16, point_bytes = points32 ? (size_t)n * 32 : 0, echo_bytes = echo ? (size_t)n * 4 : 0,
-                 col_bytes = col_time ? (size_t)tr->H * 4 : 0, chan_bytes = chan_time ? (size_t)tr->V * 4 : 0,
-                 out_bytes = (organized ? (size_t)tr->V * tr->H : (size_t)n) * fmt->point_step;
-    const size_t at_hits = io.add(hit_bytes), at_points = io.add(point_bytes), at_echo = io.add(echo_bytes), at_col = io.add(col_bytes),
-                 at_chan = io.add(chan_bytes), at_out = io.add(out_bytes);
-    if ((rc = ensure(tr, buf, io.total()))) return rc;
-    if (hit_bytes) LS_HIP(hipMemcpyAsync(buf.p + at_hits, hits, hit_bytes, hipMemcpyHostToDevice, s));
-    if (point_bytes) LS_HIP(hipMemcpyAsync(buf.p + at_points, points32, point_bytes, hipMemcpyHostToDevice, s));
-    if (echo_bytes) LS_HIP(hipMemcpyAsync(buf.p + at_echo, echo, echo_bytes, hipMemcpyHostToDevice, s));
-    if (col_bytes) LS_HIP(hipMemcpyAsync(buf.p + at_col, col_time, col_bytes, hipMemcpyHostToDevice, s));
-    if (chan_bytes) LS_HIP(hipMemcpyAsync(buf.p + at_chan, chan_time, chan_bytes, hipMemcpyHostToDevice, s));
-    if ((rc = format_issue(tr, s, fmt, point_bytes ? buf.p + at_points : nullptr, buf.p + at_hits,
-                           echo_bytes ? reinterpret_cast<const uint32_t *>(buf.p + at_echo) : nullptr, nullptr, n,
-                           col_bytes ? reinterpret_cast<const float *>(buf.p + at_col) : nullptr,
-                           chan_bytes ? reinterpret_cast<const float *>(buf.p + at_chan) : nullptr, buf.p + at_out)))
+    Staging st;
+    const int p_hits = st.in(hits, (size_t)n * 16), p_points = st.in(points32, (size_t)n * 32), p_echo = st.in(echo, (size_t)n * 4),
+              p_col = st.in(col_time, (size_t)tr->H * 4), p_chan = st.in(chan_time, (size_t)tr->V * 4),
+              p_out = st.out(out, organized ? (size_t)tr->V * tr->H : (size_t)n, fmt->point_step);
+    Staged io;
+    if ((rc = st.commit(tr, s, io))) return rc;
+    if ((rc = format_issue(tr, s, fmt, io.dev(p_points), io.dev(p_hits), io.dev<const uint32_t>(p_echo), nullptr, n, io.dev<const float>(p_col),
+                           io.dev<const float>(p_chan), io.dev(p_out))))
         return rc;
-    LS_HIP(hipMemcpyAsync(out, buf.p + at_out, out_bytes, hipMemcpyDeviceToHost, s));
-    LS_HIP(hipStreamSynchronize(s));
-    return LS_OK;
+    return io.fetch(tr);
 }
 
 int ls_cloud_format_check(const ls_cloud_format *fmt) { return cloud_format_invalid(fmt) ? LS_ERR_INVALID_ARGUMENT : LS_OK; }

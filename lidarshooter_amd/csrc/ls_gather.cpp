@@ -4,6 +4,9 @@
 // geometries each saw a ray of their own (ls_hit_attributes_moving, ls_apply_return_model_moving: ls_attr_moving.hip, with a
 // motion-table pointer per geomID next to the gather's table).  Their place among what the handle issues is that of the queries on the
 // hierarchies (query_enter / query_leave, ls_query.cpp); LS_INFO_RAY_QUERY_BUILT is left as it is.
+//
+// A static call and its _moving pair share their check, their issue function and their host-memory variant: `mv` is nullptr for the
+// static call (which has caller rays instead, or the sensor's own), the tables of the frame for the moving one.
 #include "ls_internal.h"
 #include "ls_return_model.h"
 
@@ -14,11 +17,10 @@ namespace lsi {
 namespace {
 
 // the table k_hit_attributes reads, one entry per geomID up to the highest committed one (free ids stay zero), from the committed
-// layout and the geometries' current buffers and poses (committed_geometry's checks); uploaded on s when it differs from what
-// the device holds
-int attr_table_prepare(ls_tracer *tr, hipStream_t s)
+// layout and the geometries' current buffers and poses (committed_geometry's checks), and for a moving call the motion-table pointer
+// per geomID next to it, as long as it is; each uploaded on s when it differs from what the device holds
+int tables_prepare(ls_tracer *tr, hipStream_t s, const Moving *mv)
 {
-    ls_tracer::HitAttr &a = tr->ha;
     const size_t n = tr->layout.size();
     int max_id = -1;
     for (size_t i = 0; i < n; ++i) max_id = std::max(max_id, tr->slot_geom_ids[i]);
@@ -40,66 +42,95 @@ int attr_table_prepare(ls_tracer *tr, hipStream_t s)
         std::memcpy(e.m.rinv, tr->rinv, sizeof(e.m.rinv));
         std::memcpy(e.m.t, tr->t, sizeof(e.m.t));
     }
-    const size_t bytes = tab.size() * sizeof(ls::AttrGeom);
-    if (tab.size() == a.current.size() && (!bytes || std::memcmp(tab.data(), a.current.data(), bytes) == 0)) return LS_OK;
-    a.current.clear();   // (whatever fails from here on, the next call refreshes: ensure may give the table another buffer)
-    int rc;
-    if ((rc = ensure(tr, a.table, tab.size()))) return rc;
-    if (!a.ev_stage) LS_HIP(hipEventCreateWithFlags(&a.ev_stage, hipEventDisableTiming));
-    LS_HIP(hipEventSynchronize(a.ev_stage));   // (the copy of an earlier refresh may still be reading the staging buffer)
-    if (a.stage_cap < tab.size()) {
-        if (a.h_stage) LS_HIP(hipHostFree(a.h_stage));
-        a.h_stage = nullptr;
-        a.stage_cap = 0;
-        LS_HIP(hipHostMalloc(reinterpret_cast<void **>(&a.h_stage), bytes + bytes / 8, hipHostMallocDefault));
-        a.stage_cap = (bytes + bytes / 8) / sizeof(ls::AttrGeom);
-    }
-    std::memcpy(static_cast<void *>(a.h_stage), tab.data(), bytes);
-    LS_HIP(hipMemcpyAsync(a.table.p, a.h_stage, bytes, hipMemcpyHostToDevice, s));
-    LS_HIP(hipEventRecord(a.ev_stage, s));
-    a.current.swap(tab);
-    return LS_OK;
+    if (const int rc = tr->ha.table.upload_if_changed(tr, s, tab)) return rc;
+    if (!mv) return LS_OK;
+    std::vector<const float *> by_id = mv->per_geom(tr->ha.table.current.size());
+    return tr->ha.motion.upload_if_changed(tr, s, by_id);
 }
 
+// what the moving calls refuse after their own NULL checks, in this order: ls_trace_scene_sweep_moving's pose table, flags and
+// motions; misaligned device pointers (p16: records and points, p4: words and reflectivities; the tables 4 bytes); too many records;
+// the commit state; a motion for a geometry that is not in the committed scene
+int moving_check(ls_tracer *tr, Moving &mv, uint32_t n, std::initializer_list<const void *> p16, std::initializer_list<const void *> p4, bool host)
+{
+    if (const int rc = moving_args_check(tr, mv)) return rc;
+    if (!host && moving_misaligned(p16, p4, mv))
+        return fail(tr, LS_ERR_INVALID_ARGUMENT,
+                    "hit records, attribute records and points must be 16-byte aligned, the counts, the poses, the motion tables and the "
+                    "reflectivities 4-byte aligned");
+    if (n > kMaxQueryRecords) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many hit records in one call");
+    if (const int rc = uncommitted(tr)) return rc;   // (before n = 0: the same answer whatever n)
+    return moving_resolve(tr, mv);
+}
 
-// ---- ls_hit_attributes --------------------------------------------------------------------------------------------------------
+// the caller's rays in a host-memory variant: NULL stands for the sensor's own rays, so rays given with n_rays = 0 keep an address
+// (the hit records': it is never read)
+const void *staged_rays(const Staged &io, int p_rays, int p_hits, const void *rays) { return io.dev(rays && !io.dev(p_rays) ? p_hits : p_rays); }
 
-// what the device entry point and the host-memory variant (any alignment; the ray count is checked too) refuse, in this order
-int attr_check(ls_tracer *tr, const void *rays, uint32_t n_rays, const void *hits, const uint32_t *count, uint32_t n, const void *out, bool host)
+// ---- ls_hit_attributes, ls_hit_attributes_moving ------------------------------------------------------------------------------
+
+// what the device entry points and the host-memory variants (any alignment; the ray count is checked too) refuse, in this order
+int attr_check(ls_tracer *tr, const void *rays, uint32_t n_rays, Moving *mv, const void *hits, const uint32_t *count, uint32_t n, const void *out,
+               bool host)
 {
     if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
     if (n && (!hits || !out)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null hit records or output");
+    if (mv) return moving_check(tr, *mv, n, {hits, out}, {count}, host);
     if (!host && (misaligned16(rays, hits, out) || misaligned(count, 4)))
         return fail(tr, LS_ERR_INVALID_ARGUMENT, "rays, hit records and attribute records must be 16-byte aligned, the count 4-byte aligned");
     if (n > kMaxQueryRecords || (host && rays && n_rays > kMaxQueryRecords)) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many hit records in one call");
     return uncommitted(tr);   // (before n = 0: the same answer whatever n)
 }
 
-int attr_issue(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n_rays, const void *d_hits, const uint32_t *d_count, uint32_t n, void *d_out)
+int attr_issue(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n_rays, const Moving *mv, const void *d_hits, const uint32_t *d_count,
+               uint32_t n, void *d_out)
 {
-    int rc;
-    if ((rc = attr_table_prepare(tr, s))) return rc;
-    ls::launch_hit_attributes(s, d_hits, d_count, n, d_rays, n_rays, tables(tr), tr->ha.table.p, (uint32_t)tr->ha.current.size(), d_out);
+    const ls_tracer::HitAttr &a = tr->ha;
+    if (const int rc = tables_prepare(tr, s, mv)) return rc;
+    const uint32_t n_geoms = (uint32_t)a.table.current.size();
+    if (mv)
+        ls::launch_hit_attributes_moving(s, d_hits, d_count, n, tables(tr), a.table.dev.p, a.motion.dev.p, n_geoms, mv->col_pose,
+                                         (mv->flags & LS_SWEEP_DESKEW) != 0, d_out);
+    else
+        ls::launch_hit_attributes(s, d_hits, d_count, n, d_rays, n_rays, tables(tr), a.table.dev.p, n_geoms, d_out);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
 
-// ---- ls_apply_return_model ----------------------------------------------------------------------------------------------------
+// records, rays or tables, and results staged in q.io, on the handle's stream; returns when out is filled
+int attr_host(ls_tracer *tr, const void *rays, uint32_t n_rays, Moving *mv, const void *hits, uint32_t n, void *out)
+{
+    const hipStream_t s = tr->stream;
+    int rc;
+    if ((rc = query_enter(tr, s))) return rc;
+    Staging st;
+    const int p_hits = st.in(hits, (size_t)n * 16), p_rays = st.in(rays, (size_t)n_rays * 32), p_out = st.out(out, n, 48);
+    if (mv) mv->stage(tr, st);
+    Staged io;
+    if ((rc = st.commit(tr, s, io))) return rc;
+    if (mv) mv->use_staged(io);
+    if ((rc = attr_issue(tr, s, staged_rays(io, p_rays, p_hits, rays), n_rays, mv, io.dev(p_hits), nullptr, n, io.dev(p_out)))) return rc;
+    return io.fetch(tr);
+}
 
-// what both entry points refuse, in this order: the model and the reflectivities first, before anything touches the device
-int returns_check(ls_tracer *tr, const ls_return_model *model, const void *rays, uint32_t n_rays, const void *hits, const uint32_t *count, uint32_t n,
-                  const float *refl, uint32_t n_refl, const void *points32, const void *hits_out, const uint32_t *n_out, bool host)
+// ---- ls_apply_return_model, ls_apply_return_model_moving ----------------------------------------------------------------------
+
+// what the entry points refuse, in this order: the model and the reflectivities first, before anything touches the device
+int returns_check(ls_tracer *tr, const ls_return_model *model, const void *rays, uint32_t n_rays, Moving *mv, const void *hits, const uint32_t *count,
+                  uint32_t n, const float *refl, uint32_t n_refl, const void *points32, const void *hits_out, const uint32_t *n_out, bool host)
 {
     if (const char *why = n_refl && !refl ? "null reflectivities" : ls::return_model_invalid(model)) return fail(tr, LS_ERR_INVALID_ARGUMENT, why);
     if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
     if (!n_out || (n && !hits)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null hit records or count output");
+    if (mv) return moving_check(tr, *mv, n, {hits, points32, hits_out}, {count, n_out, refl}, host);
     if (!host && (misaligned16(rays, hits, points32, hits_out) || misaligned(count, 4) || misaligned(n_out, 4) || misaligned(refl, 4)))
         return fail(tr, LS_ERR_INVALID_ARGUMENT, "rays, hit records and points must be 16-byte aligned, counts and reflectivities 4-byte aligned");
     if (n > kMaxQueryRecords || (host && rays && n_rays > kMaxQueryRecords)) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many hit records in one call");
     return uncommitted(tr);
 }
 
-int returns_issue(ls_tracer *tr, hipStream_t s, const ls_return_model *model, uint32_t frame_index, const void *d_rays, uint32_t n_rays,
+// the static call keeps its fused launch, the moving one evaluates and packs
+int returns_issue(ls_tracer *tr, hipStream_t s, const ls_return_model *model, uint32_t frame_index, const void *d_rays, uint32_t n_rays, const Moving *mv,
                   const void *d_hits, const uint32_t *d_count, uint32_t n, const float *d_refl, uint32_t n_refl, void *d_points32, void *d_hits_out,
                   uint32_t *d_n_out)
 {
@@ -109,143 +140,46 @@ int returns_issue(ls_tracer *tr, hipStream_t s, const ls_return_model *model, ui
         LS_HIP(hipMemsetAsync(d_n_out, 0, 4, s));   // no record: no return
         return LS_OK;
     }
-    if ((rc = attr_table_prepare(tr, s))) return rc;
-    if ((rc = ensure(tr, a.park, 2 * (size_t)n))) return rc;
-    if ((rc = ensure(tr, a.block_counts, ls::returns_block_count(n)))) return rc;
-    ls::launch_returns(s, d_hits, d_count, n, d_rays, n_rays, tables(tr), a.table.p, (uint32_t)a.current.size(), *model, frame_index,
-                       n_refl ? d_refl : nullptr, n_refl, a.park.p, a.block_counts.p, d_points32, d_hits_out, d_n_out);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
-}
-
-// ---- ls_hit_attributes_moving / ls_apply_return_model_moving ------------------------------------------------------------------
-
-// what the four entry points refuse after their own NULL checks, in this order: ls_trace_scene_sweep_moving's pose table, flags and
-// motions; misaligned device pointers (p16: records and points, p4: words and reflectivities; the tables 4 bytes); too many records;
-// the commit state; a motion for a geometry that is not in the committed scene.  On LS_OK by_id[g] is the motion table of geomID g
-// (nullptr: at rest), as long as the table attr_table_prepare makes
-int moving_args_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags,
-                      uint32_t n, std::initializer_list<const void *> p16, std::initializer_list<const void *> p4, bool host,
-                      std::vector<const float *> &by_id)
-{
-    if (const int rc = motion_args_check(tr, col_pose, n_cols, motions, n_motions, flags)) return rc;
-    if (!host) {
-        bool bad = misaligned(col_pose, 4);
-        for (const void *p : p16) bad = bad || misaligned(p, 16);
-        for (const void *p : p4) bad = bad || misaligned(p, 4);
-        for (uint32_t k = 0; k < n_motions; ++k) bad = bad || misaligned(motions[k].col_motion, 4);
-        if (bad)
-            return fail(tr, LS_ERR_INVALID_ARGUMENT,
-                        "hit records, attribute records and points must be 16-byte aligned, the counts, the poses, the motion tables and the "
-                        "reflectivities 4-byte aligned");
-    }
-    if (n > kMaxQueryRecords) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many hit records in one call");
-    if (const int rc = uncommitted(tr)) return rc;   // (before n = 0: the same answer whatever n)
-    int max_id = -1;
-    for (const int id : tr->slot_geom_ids) max_id = std::max(max_id, id);
-    by_id.assign((size_t)(max_id + 1), nullptr);
-    for (uint32_t k = 0; k < n_motions; ++k) {
-        if (std::find(tr->slot_geom_ids.begin(), tr->slot_geom_ids.end(), (int)motions[k].geom) == tr->slot_geom_ids.end() ||
-            motions[k].geom >= by_id.size())
-            return fail(tr, LS_ERR_UNKNOWN_GEOMETRY, "a motion names a geometry that is not in the committed scene");
-        by_id[motions[k].geom] = motions[k].col_motion;
-    }
-    return LS_OK;
-}
-
-int attr_moving_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags,
-                      const void *hits, const uint32_t *count, uint32_t n, const void *out, bool host, std::vector<const float *> &by_id)
-{
-    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
-    if (n && (!hits || !out)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null hit records or output");
-    return moving_args_check(tr, col_pose, n_cols, motions, n_motions, flags, n, {hits, out}, {count}, host, by_id);
-}
-
-// the model and the reflectivities first, as ls_apply_return_model
-int returns_moving_check(ls_tracer *tr, const ls_return_model *model, const float *col_pose, uint32_t n_cols, const ls_geometry_motion *motions,
-                         uint32_t n_motions, uint32_t flags, const void *hits, const uint32_t *count, uint32_t n, const float *refl, uint32_t n_refl,
-                         const void *points32, const void *hits_out, const uint32_t *n_out, bool host, std::vector<const float *> &by_id)
-{
-    if (const char *why = n_refl && !refl ? "null reflectivities" : ls::return_model_invalid(model)) return fail(tr, LS_ERR_INVALID_ARGUMENT, why);
-    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
-    if (!n_out || (n && !hits)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null hit records or count output");
-    return moving_args_check(tr, col_pose, n_cols, motions, n_motions, flags, n, {hits, points32, hits_out}, {count, n_out, refl}, host, by_id);
-}
-
-// the pointer array k_hit_attributes_moving reads next to the AttrGeom table, one entry per geomID (by_id, cut or padded to that
-// table's length: the kernels check a geomID against one bound); uploaded on s when it differs from what the device holds
-int motion_table_prepare(ls_tracer *tr, hipStream_t s, std::vector<const float *> &by_id)
-{
-    ls_tracer::HitAttr &a = tr->ha;
-    by_id.resize(a.current.size(), nullptr);
-    if (by_id == a.motion_current && a.motion.p) return LS_OK;
-    a.motion_current.clear();   // (whatever fails from here on, the next call refreshes)
-    const size_t bytes = by_id.size() * sizeof(const float *);
-    int rc;
-    if ((rc = ensure(tr, a.motion, by_id.size()))) return rc;
-    if (!a.ev_motion_stage) LS_HIP(hipEventCreateWithFlags(&a.ev_motion_stage, hipEventDisableTiming));
-    LS_HIP(hipEventSynchronize(a.ev_motion_stage));   // (the copy of an earlier refresh may still be reading the staging buffer)
-    if (a.motion_stage_cap < by_id.size()) {
-        if (a.h_motion_stage) LS_HIP(hipHostFree(a.h_motion_stage));
-        a.h_motion_stage = nullptr;
-        a.motion_stage_cap = 0;
-        LS_HIP(hipHostMalloc(reinterpret_cast<void **>(&a.h_motion_stage), bytes + bytes / 8, hipHostMallocDefault));
-        a.motion_stage_cap = (bytes + bytes / 8) / sizeof(const float *);
-    }
-    std::memcpy(static_cast<void *>(a.h_motion_stage), by_id.data(), bytes);
-    LS_HIP(hipMemcpyAsync(a.motion.p, a.h_motion_stage, bytes, hipMemcpyHostToDevice, s));
-    LS_HIP(hipEventRecord(a.ev_motion_stage, s));
-    a.motion_current = by_id;
-    return LS_OK;
-}
-
-int attr_moving_issue(ls_tracer *tr, hipStream_t s, const float *d_col_pose, std::vector<const float *> &by_id, uint32_t flags, const void *d_hits,
-                      const uint32_t *d_count, uint32_t n, void *d_out)
-{
-    int rc;
-    if ((rc = attr_table_prepare(tr, s)) || (rc = motion_table_prepare(tr, s, by_id))) return rc;
-    ls::launch_hit_attributes_moving(s, d_hits, d_count, n, tables(tr), tr->ha.table.p, tr->ha.motion.p, (uint32_t)tr->ha.current.size(), d_col_pose,
-                                     (flags & LS_SWEEP_DESKEW) != 0, d_out);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
-}
-
-int returns_moving_issue(ls_tracer *tr, hipStream_t s, const ls_return_model *model, uint32_t frame_index, const float *d_col_pose,
-                         std::vector<const float *> &by_id, uint32_t flags, const void *d_hits, const uint32_t *d_count, uint32_t n,
-                         const float *d_refl, uint32_t n_refl, void *d_points32, void *d_hits_out, uint32_t *d_n_out)
-{
-    ls_tracer::HitAttr &a = tr->ha;
-    int rc;
-    if (!n) {
-        LS_HIP(hipMemsetAsync(d_n_out, 0, 4, s));   // no record: no return
-        return LS_OK;
-    }
-    if ((rc = attr_table_prepare(tr, s)) || (rc = motion_table_prepare(tr, s, by_id))) return rc;
+    if ((rc = tables_prepare(tr, s, mv))) return rc;
     if ((rc = ensure(tr, a.park, 2 * (size_t)n))) return rc;
     if ((rc = ensure(tr, a.block_counts, ls::returns_block_count(n)))) return rc;
     const ls::SensorTables tb = tables(tr);
-    ls::launch_returns_eval_moving(s, d_hits, d_count, n, tb, a.table.p, a.motion.p, (uint32_t)a.current.size(), d_col_pose,
-                                   (flags & LS_SWEEP_DESKEW) != 0, *model, frame_index, n_refl ? d_refl : nullptr, n_refl, a.park.p, a.block_counts.p);
-    ls::launch_returns_pack(s, a.park.p, a.block_counts.p, d_count, n, tb.H, d_points32, d_hits_out, d_n_out);
+    const uint32_t n_geoms = (uint32_t)a.table.current.size();
+    if (!n_refl) d_refl = nullptr;
+    if (mv) {
+        ls::launch_returns_eval_moving(s, d_hits, d_count, n, tb, a.table.dev.p, a.motion.dev.p, n_geoms, mv->col_pose,
+                                       (mv->flags & LS_SWEEP_DESKEW) != 0, *model, frame_index, d_refl, n_refl, a.park.p, a.block_counts.p);
+        ls::launch_returns_pack(s, a.park.p, a.block_counts.p, d_count, n, tb.H, d_points32, d_hits_out, d_n_out);
+    } else {
+        ls::launch_returns(s, d_hits, d_count, n, d_rays, n_rays, tb, a.table.dev.p, n_geoms, *model, frame_index, d_refl, n_refl, a.park.p,
+                           a.block_counts.p, d_points32, d_hits_out, d_n_out);
+    }
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
 
-// the host-memory variants' tables in q.io: the pose table at at_pose, the named geometries' tables behind at_motion (48 H bytes
-// each: every table starts 16-byte aligned); by_id then names the device copies
-int stage_tables(ls_tracer *tr, hipStream_t s, uint8_t *base, size_t at_pose, size_t at_motion, const float *col_pose, uint32_t n_cols,
-                 std::vector<const float *> &by_id)
+// inputs, rays or tables, and results staged in q.io, on the handle's stream; the count comes back first, then as many records
+int returns_host(ls_tracer *tr, const char *overflow, const ls_return_model *model, uint32_t frame_index, const void *rays, uint32_t n_rays, Moving *mv,
+                 const void *hits, uint32_t n, const float *refl, uint32_t n_refl, void *points32, void *hits_out, uint32_t *n_out)
 {
-    const size_t table_bytes = (size_t)tr->H * 48;
-    if (col_pose) LS_HIP(hipMemcpyAsync(base + at_pose, col_pose, (size_t)n_cols * 48, hipMemcpyHostToDevice, s));
-    size_t staged = 0;
-    for (const float *&t : by_id) {
-        if (!t) continue;
-        uint8_t *dst = base + at_motion + staged++ * table_bytes;
-        LS_HIP(hipMemcpyAsync(dst, t, table_bytes, hipMemcpyHostToDevice, s));
-        t = reinterpret_cast<const float *>(dst);
+    if (!n) {
+        *n_out = 0;
+        return LS_OK;
     }
-    return LS_OK;
+    const hipStream_t s = tr->stream;
+    int rc;
+    if ((rc = query_enter(tr, s))) return rc;
+    Staging st;
+    const int p_hits = st.in(hits, (size_t)n * 16), p_rays = st.in(rays, (size_t)n_rays * 32), p_refl = st.in(refl, (size_t)n_refl * 4),
+              p_points = st.out(points32, n, 32), p_out = st.out(hits_out, n, 16), p_n = st.scratch(4);
+    if (mv) mv->stage(tr, st);
+    Staged io;
+    if ((rc = st.commit(tr, s, io))) return rc;
+    if (mv) mv->use_staged(io);
+    if ((rc = returns_issue(tr, s, model, frame_index, staged_rays(io, p_rays, p_hits, rays), n_rays, mv, io.dev(p_hits), nullptr, n,
+                            io.dev<const float>(p_refl), n_refl, io.dev(p_points), io.dev(p_out), io.dev<uint32_t>(p_n))))
+        return rc;
+    return io.fetch_counted(tr, p_n, n, overflow, n_out);
 }
 
 }  // namespace
@@ -253,19 +187,9 @@ int stage_tables(ls_tracer *tr, hipStream_t s, uint8_t *base, size_t at_pose, si
 void hit_attr_release(ls_tracer *tr)
 {
     ls_tracer::HitAttr &a = tr->ha;
-    if (a.ev_stage) { (void)hipEventSynchronize(a.ev_stage); (void)hipEventDestroy(a.ev_stage); }
-    if (a.h_stage) (void)hipHostFree(a.h_stage);
-    if (a.ev_motion_stage) { (void)hipEventSynchronize(a.ev_motion_stage); (void)hipEventDestroy(a.ev_motion_stage); }
-    if (a.h_motion_stage) (void)hipHostFree(a.h_motion_stage);
-    release(a.table); release(a.park); release(a.block_counts); release(a.motion);
-    a.ev_stage = nullptr;
-    a.h_stage = nullptr;
-    a.stage_cap = 0;
-    a.current.clear();
-    a.ev_motion_stage = nullptr;
-    a.h_motion_stage = nullptr;
-    a.motion_stage_cap = 0;
-    a.motion_current.clear();
+    a.table.release();
+    a.motion.release();
+    release(a.park); release(a.block_counts);
 }
 
 }  // namespace lsi
@@ -280,111 +204,58 @@ int ls_hit_attributes(ls_tracer *tr, void *hip_stream, const void *d_rays, uint3
     LS_ENTER(tr);
     const hipStream_t s = stream_of(tr, hip_stream);
     int rc;
-    if ((rc = attr_check(tr, d_rays, n_rays, d_hits, d_count, n, d_out, false)) || !n) return rc;
-    if ((rc = query_enter(tr, s)) || (rc = attr_issue(tr, s, d_rays, n_rays, d_hits, d_count, n, d_out))) return rc;
-    return query_leave(tr, s);
+    if ((rc = attr_check(tr, d_rays, n_rays, nullptr, d_hits, d_count, n, d_out, false)) || !n) return rc;
+    return query_run(tr, s, [&] { return attr_issue(tr, s, d_rays, n_rays, nullptr, d_hits, d_count, n, d_out); });
 }
 
-// hit records, rays and results staged in q.io, on the handle's stream; returns when out is filled
 int ls_hit_attributes_host(ls_tracer *tr, const void *rays, uint32_t n_rays, const void *hits, uint32_t n, void *out)
 {
     LS_ENTER(tr);
-    DevBuf<uint8_t> &buf = tr->rq.io;
-    const hipStream_t s = tr->stream;
     int rc;
-    if ((rc = attr_check(tr, rays, n_rays, hits, nullptr, n, out, true)) || !n) return rc;
-    if ((rc = query_enter(tr, s))) return rc;
-    IoPlan io;
-    const size_t ray_bytes = rays ? (size_t)n_rays * 32 : 0;
-    const size_t at_hits = io.add((size_t)n * 16), at_rays = io.add(ray_bytes), at_out = io.add((size_t)n * 48);
-    if ((rc = ensure(tr, buf, io.total()))) return rc;
-    LS_HIP(hipMemcpyAsync(buf.p + at_hits, hits, (size_t)n * 16, hipMemcpyHostToDevice, s));
-    if (ray_bytes) LS_HIP(hipMemcpyAsync(buf.p + at_rays, rays, ray_bytes, hipMemcpyHostToDevice, s));
-    if ((rc = attr_issue(tr, s, rays ? buf.p + at_rays : nullptr, n_rays, buf.p + at_hits, nullptr, n, buf.p + at_out))) return rc;
-    LS_HIP(hipMemcpyAsync(out, buf.p + at_out, (size_t)n * 48, hipMemcpyDeviceToHost, s));
-    LS_HIP(hipStreamSynchronize(s));
-    return LS_OK;
+    if ((rc = attr_check(tr, rays, n_rays, nullptr, hits, nullptr, n, out, true)) || !n) return rc;
+    return attr_host(tr, rays, n_rays, nullptr, hits, n, out);
 }
 
 int ls_apply_return_model(ls_tracer *tr, void *hip_stream, const ls_return_model *model, uint32_t frame_index, const void *d_rays, uint32_t n_rays,
                           const void *d_hits, const uint32_t *d_count, uint32_t n, const float *d_reflectivity, uint32_t n_reflectivity,
                           void *d_points32, void *d_hits_out, uint32_t *d_n_out)
 {
-    LS_ENTER_CHECKED(tr, returns_check(tr, model, d_rays, n_rays, d_hits, d_count, n, d_reflectivity, n_reflectivity, d_points32, d_hits_out, d_n_out,
-                                       false));
+    LS_ENTER_CHECKED(tr, returns_check(tr, model, d_rays, n_rays, nullptr, d_hits, d_count, n, d_reflectivity, n_reflectivity, d_points32, d_hits_out,
+                                       d_n_out, false));
     const hipStream_t s = stream_of(tr, hip_stream);
-    int rc;
-    if ((rc = query_enter(tr, s)) || (rc = returns_issue(tr, s, model, frame_index, d_rays, n_rays, d_hits, d_count, n, d_reflectivity, n_reflectivity,
-                                                         d_points32, d_hits_out, d_n_out)))
-        return rc;
-    return query_leave(tr, s);
+    return query_run(tr, s, [&] {
+        return returns_issue(tr, s, model, frame_index, d_rays, n_rays, nullptr, d_hits, d_count, n, d_reflectivity, n_reflectivity, d_points32,
+                             d_hits_out, d_n_out);
+    });
 }
 
-// inputs and results staged in q.io, on the handle's stream; the count comes back first, then as many records
 int ls_apply_return_model_host(ls_tracer *tr, const ls_return_model *model, uint32_t frame_index, const void *rays, uint32_t n_rays,
                                const void *hits, uint32_t n, const float *reflectivity, uint32_t n_reflectivity, void *points32, void *hits_out,
                                uint32_t *n_out)
 {
-    LS_ENTER_CHECKED(tr, returns_check(tr, model, rays, n_rays, hits, nullptr, n, reflectivity, n_reflectivity, points32, hits_out, n_out, true));
-    if (!n) {
-        *n_out = 0;
-        return LS_OK;
-    }
-    DevBuf<uint8_t> &buf = tr->rq.io;
-    const hipStream_t s = tr->stream;
-    int rc;
-    if ((rc = query_enter(tr, s))) return rc;
-    IoPlan io;
-    const size_t ray_bytes = rays ? (size_t)n_rays * 32 : 0;
-    const size_t at_hits = io.add((size_t)n * 16), at_rays = io.add(ray_bytes), at_points = io.add(points32 ? (size_t)n * 32 : 0),
-                 at_out = io.add(hits_out ? (size_t)n * 16 : 0), at_refl = io.add((size_t)n_reflectivity * 4), at_n = io.add(4);
-    if ((rc = ensure(tr, buf, io.total()))) return rc;
-    LS_HIP(hipMemcpyAsync(buf.p + at_hits, hits, (size_t)n * 16, hipMemcpyHostToDevice, s));
-    if (ray_bytes) LS_HIP(hipMemcpyAsync(buf.p + at_rays, rays, ray_bytes, hipMemcpyHostToDevice, s));
-    if (n_reflectivity) LS_HIP(hipMemcpyAsync(buf.p + at_refl, reflectivity, (size_t)n_reflectivity * 4, hipMemcpyHostToDevice, s));
-    if ((rc = returns_issue(tr, s, model, frame_index, rays ? buf.p + at_rays : nullptr, n_rays, buf.p + at_hits, nullptr, n,
-                            reinterpret_cast<const float *>(buf.p + at_refl), n_reflectivity, points32 ? buf.p + at_points : nullptr,
-                            hits_out ? buf.p + at_out : nullptr, reinterpret_cast<uint32_t *>(buf.p + at_n))))
-        return rc;
-    return fetch_counted(tr, buf.p + at_n, n, "ls_apply_return_model: more returns than records",
-                         {{points32, buf.p + at_points, 32}, {hits_out, buf.p + at_out, 16}}, n_out);
+    LS_ENTER_CHECKED(tr, returns_check(tr, model, rays, n_rays, nullptr, hits, nullptr, n, reflectivity, n_reflectivity, points32, hits_out, n_out,
+                                       true));
+    return returns_host(tr, "ls_apply_return_model: more returns than records", model, frame_index, rays, n_rays, nullptr, hits, n, reflectivity,
+                        n_reflectivity, points32, hits_out, n_out);
 }
 
 int ls_hit_attributes_moving(ls_tracer *tr, void *hip_stream, const float *d_col_pose, uint32_t n_cols, const ls_geometry_motion *motions,
                              uint32_t n_motions, uint32_t flags, const void *d_hits, const uint32_t *d_count, uint32_t n, void *d_out)
 {
-    std::vector<const float *> by_id;
-    LS_ENTER_CHECKED(tr, attr_moving_check(tr, d_col_pose, n_cols, motions, n_motions, flags, d_hits, d_count, n, d_out, false, by_id));
+    Moving mv = {d_col_pose, n_cols, motions, n_motions, flags};
+    LS_ENTER_CHECKED(tr, attr_check(tr, nullptr, 0, &mv, d_hits, d_count, n, d_out, false));
     if (!n) return LS_OK;
     const hipStream_t s = stream_of(tr, hip_stream);
-    int rc;
-    if ((rc = query_enter(tr, s)) || (rc = attr_moving_issue(tr, s, d_col_pose, by_id, flags, d_hits, d_count, n, d_out))) return rc;
-    return query_leave(tr, s);
+    return query_run(tr, s, [&] { return attr_issue(tr, s, nullptr, 0, &mv, d_hits, d_count, n, d_out); });
 }
 
-// hit records, the tables and the results staged in q.io, on the handle's stream; returns when out is filled
 int ls_hit_attributes_moving_host(ls_tracer *tr, const float *col_pose, uint32_t n_cols, const ls_geometry_motion *motions, uint32_t n_motions,
                                   uint32_t flags, const void *hits, uint32_t n, void *out)
 {
-    std::vector<const float *> by_id;
-    LS_ENTER_CHECKED(tr, attr_moving_check(tr, col_pose, n_cols, motions, n_motions, flags, hits, nullptr, n, out, true, by_id));
+    Moving mv = {col_pose, n_cols, motions, n_motions, flags};
+    LS_ENTER_CHECKED(tr, attr_check(tr, nullptr, 0, &mv, hits, nullptr, n, out, true));
     if (!n) return LS_OK;
-    DevBuf<uint8_t> &buf = tr->rq.io;
-    const hipStream_t s = tr->stream;
-    int rc;
-    if ((rc = query_enter(tr, s))) return rc;
-    IoPlan io;
-    const size_t at_hits = io.add((size_t)n * 16), at_out = io.add((size_t)n * 48), at_pose = io.add((size_t)n_cols * 48),
-                 at_motion = io.add((size_t)n_motions * tr->H * 48);
-    if ((rc = ensure(tr, buf, io.total()))) return rc;
-    LS_HIP(hipMemcpyAsync(buf.p + at_hits, hits, (size_t)n * 16, hipMemcpyHostToDevice, s));
-    if ((rc = stage_tables(tr, s, buf.p, at_pose, at_motion, col_pose, n_cols, by_id))) return rc;
-    if ((rc = attr_moving_issue(tr, s, col_pose ? reinterpret_cast<const float *>(buf.p + at_pose) : nullptr, by_id, flags, buf.p + at_hits, nullptr, n,
-                                buf.p + at_out)))
-        return rc;
-    LS_HIP(hipMemcpyAsync(out, buf.p + at_out, (size_t)n * 48, hipMemcpyDeviceToHost, s));
-    LS_HIP(hipStreamSynchronize(s));
-    return LS_OK;
+    return attr_host(tr, nullptr, 0, &mv, hits, n, out);
 }
 
 int ls_apply_return_model_moving(ls_tracer *tr, void *hip_stream, const ls_return_model *model, uint32_t frame_index, const float *d_col_pose,
@@ -392,48 +263,24 @@ int ls_apply_return_model_moving(ls_tracer *tr, void *hip_stream, const ls_retur
                                  const uint32_t *d_count, uint32_t n, const float *d_reflectivity, uint32_t n_reflectivity, void *d_points32,
                                  void *d_hits_out, uint32_t *d_n_out)
 {
-    std::vector<const float *> by_id;
-    LS_ENTER_CHECKED(tr, returns_moving_check(tr, model, d_col_pose, n_cols, motions, n_motions, flags, d_hits, d_count, n, d_reflectivity,
-                                              n_reflectivity, d_points32, d_hits_out, d_n_out, false, by_id));
+    Moving mv = {d_col_pose, n_cols, motions, n_motions, flags};
+    LS_ENTER_CHECKED(tr, returns_check(tr, model, nullptr, 0, &mv, d_hits, d_count, n, d_reflectivity, n_reflectivity, d_points32, d_hits_out, d_n_out,
+                                       false));
     const hipStream_t s = stream_of(tr, hip_stream);
-    int rc;
-    if ((rc = query_enter(tr, s)) || (rc = returns_moving_issue(tr, s, model, frame_index, d_col_pose, by_id, flags, d_hits, d_count, n, d_reflectivity,
-                                                                n_reflectivity, d_points32, d_hits_out, d_n_out)))
-        return rc;
-    return query_leave(tr, s);
+    return query_run(tr, s, [&] {
+        return returns_issue(tr, s, model, frame_index, nullptr, 0, &mv, d_hits, d_count, n, d_reflectivity, n_reflectivity, d_points32, d_hits_out,
+                             d_n_out);
+    });
 }
 
-// inputs, tables and results staged in q.io, on the handle's stream; the count comes back first, then as many records
 int ls_apply_return_model_moving_host(ls_tracer *tr, const ls_return_model *model, uint32_t frame_index, const float *col_pose, uint32_t n_cols,
                                       const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags, const void *hits, uint32_t n,
                                       const float *reflectivity, uint32_t n_reflectivity, void *points32, void *hits_out, uint32_t *n_out)
 {
-    std::vector<const float *> by_id;
-    LS_ENTER_CHECKED(tr, returns_moving_check(tr, model, col_pose, n_cols, motions, n_motions, flags, hits, nullptr, n, reflectivity, n_reflectivity,
-                                              points32, hits_out, n_out, true, by_id));
-    if (!n) {
-        *n_out = 0;
-        return LS_OK;
-    }
-    DevBuf<uint8_t> &buf = tr->rq.io;
-    const hipStream_t s = tr->stream;
-    int rc;
-    if ((rc = query_enter(tr, s))) return rc;
-    IoPlan io;
-    const size_t at_hits = io.add((size_t)n * 16), at_points = io.add(points32 ? (size_t)n * 32 : 0), at_out = io.add(hits_out ? (size_t)n * 16 : 0),
-                 at_refl = io.add((size_t)n_reflectivity * 4), at_pose = io.add((size_t)n_cols * 48),
-                 at_motion = io.add((size_t)n_motions * tr->H * 48), at_n = io.add(4);
-    if ((rc = ensure(tr, buf, io.total()))) return rc;
-    LS_HIP(hipMemcpyAsync(buf.p + at_hits, hits, (size_t)n * 16, hipMemcpyHostToDevice, s));
-    if (n_reflectivity) LS_HIP(hipMemcpyAsync(buf.p + at_refl, reflectivity, (size_t)n_reflectivity * 4, hipMemcpyHostToDevice, s));
-    if ((rc = stage_tables(tr, s, buf.p, at_pose, at_motion, col_pose, n_cols, by_id))) return rc;
-    if ((rc = returns_moving_issue(tr, s, model, frame_index, col_pose ? reinterpret_cast<const float *>(buf.p + at_pose) : nullptr, by_id, flags,
-                                   buf.p + at_hits, nullptr, n, reinterpret_cast<const float *>(buf.p + at_refl), n_reflectivity,
-                                   points32 ? buf.p + at_points : nullptr, hits_out ? buf.p + at_out : nullptr,
-                                   reinterpret_cast<uint32_t *>(buf.p + at_n))))
-        return rc;
-    return fetch_counted(tr, buf.p + at_n, n, "ls_apply_return_model_moving: more returns than records",
-                         {{points32, buf.p + at_points, 32}, {hits_out, buf.p + at_out, 16}}, n_out);
+    Moving mv = {col_pose, n_cols, motions, n_motions, flags};
+    LS_ENTER_CHECKED(tr, returns_check(tr, model, nullptr, 0, &mv, hits, nullptr, n, reflectivity, n_reflectivity, points32, hits_out, n_out, true));
+    return returns_host(tr, "ls_apply_return_model_moving: more returns than records", model, frame_index, nullptr, 0, &mv, hits, n, reflectivity,
+                        n_reflectivity, points32, hits_out, n_out);
 }
 
 }  // extern "C"

@@ -95,6 +95,20 @@ struct DevBuf {
     size_t cap = 0;  // elements
 };
 
+// a small device table a call refreshes when it finds it out of date: uploaded through a pinned staging block of its own, so that
+// the caller's stream never waits for the host (T: plain data, compared byte for byte)
+template <typename T>
+struct StagedTable {
+    DevBuf<T> dev;
+    std::vector<T> current;        // what dev holds (empty after a refresh that failed: the next call uploads again)
+    T *h_stage = nullptr;          // pinned staging of the upload ...
+    size_t stage_cap = 0;
+    hipEvent_t ev_stage = nullptr; // ... recorded behind the last copy that reads it
+    // on s, when `table` differs from `current` or dev does not exist; `table` is left in an unspecified state
+    int upload_if_changed(ls_tracer *tr, hipStream_t s, std::vector<T> &table);
+    void release();
+};
+
 }  // namespace lsi
 
 struct ls_tracer {
@@ -285,7 +299,7 @@ struct ls_tracer {
         uint32_t *d_maxabs = nullptr;          // kMaxGeoms words
         uint32_t *d_counters = nullptr;        // ray counter of each launch (kMaxGeoms / kGeomsPerLaunch words)
         lsi::DevBuf<uint32_t> spill;
-        lsi::DevBuf<uint8_t> io;               // the host-memory variants' staging (IoPlan)
+        lsi::DevBuf<uint8_t> io;               // the host-memory variants' staging (Staging)
         // ls_trace_scene_sweep: the shard's ray records (32 bytes each, ascending ray index), the walk's dense hit records (16
         // bytes each) and the hit count of every 256 of them (every call is ordered through the handle's stream: one at a time)
         lsi::DevBuf<uint8_t> sweep_rays, sweep_hits;
@@ -308,22 +322,14 @@ struct ls_tracer {
     // ls_hit_attributes (ls_gather.cpp): the per-geomID table k_hit_attributes reads, refreshed by the call that finds it out of
     // date (a pose, a vertex or index buffer, the registry or the sensor pose changed)
     struct HitAttr {
-        lsi::DevBuf<ls::AttrGeom> table;       // device, indexed by geomID
-        std::vector<ls::AttrGeom> current;     // what it holds
-        ls::AttrGeom *h_stage = nullptr;       // pinned staging of the upload ...
-        size_t stage_cap = 0;
-        hipEvent_t ev_stage = nullptr;         // ... recorded behind the last copy that reads it
+        lsi::StagedTable<ls::AttrGeom> table;      // indexed by geomID
         // ls_apply_return_model: the evaluated records between its two kernels (2 x 16 bytes each) and the kept count of every
         // 256 (every call is ordered through the handle's stream: one call uses them at a time)
         lsi::DevBuf<uint4> park;
         lsi::DevBuf<uint32_t> block_counts;
         // ls_hit_attributes_moving / ls_apply_return_model_moving: a motion-table pointer per geomID next to `table` (nullptr: at
-        // rest), uploaded the same way by the call that finds it out of date
-        lsi::DevBuf<const float *> motion;
-        std::vector<const float *> motion_current;
-        const float **h_motion_stage = nullptr;
-        size_t motion_stage_cap = 0;
-        hipEvent_t ev_motion_stage = nullptr;
+        // rest), as long as it is
+        lsi::StagedTable<const float *> motion;
     } ha;
     uint64_t upload_seq = 0;
 
@@ -377,6 +383,42 @@ inline void release(DevBuf<T> &b)
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr;
     b.cap = 0;
+}
+
+template <typename T>
+int StagedTable<T>::upload_if_changed(ls_tracer *tr, hipStream_t s, std::vector<T> &table)
+{
+    const size_t bytes = table.size() * sizeof(T);
+    if (dev.p && table.size() == current.size() && (!bytes || std::memcmp(table.data(), current.data(), bytes) == 0)) return LS_OK;
+    current.clear();   // (whatever fails from here on, the next call refreshes: ensure may give the table another buffer)
+    int rc;
+    if ((rc = ensure(tr, dev, table.size()))) return rc;
+    if (!ev_stage) LS_HIP(hipEventCreateWithFlags(&ev_stage, hipEventDisableTiming));
+    LS_HIP(hipEventSynchronize(ev_stage));   // (the copy of an earlier refresh may still be reading the staging buffer)
+    if (stage_cap < table.size()) {
+        if (h_stage) LS_HIP(hipHostFree(h_stage));
+        h_stage = nullptr;
+        stage_cap = 0;
+        LS_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_stage), bytes + bytes / 8, hipHostMallocDefault));
+        stage_cap = (bytes + bytes / 8) / sizeof(T);
+    }
+    std::memcpy(static_cast<void *>(h_stage), table.data(), bytes);
+    LS_HIP(hipMemcpyAsync(dev.p, h_stage, bytes, hipMemcpyHostToDevice, s));
+    LS_HIP(hipEventRecord(ev_stage, s));
+    current.swap(table);
+    return LS_OK;
+}
+
+template <typename T>
+void StagedTable<T>::release()
+{
+    if (ev_stage) { (void)hipEventSynchronize(ev_stage); (void)hipEventDestroy(ev_stage); }
+    if (h_stage) (void)hipHostFree(h_stage);
+    lsi::release(dev);
+    ev_stage = nullptr;
+    h_stage = nullptr;
+    stage_cap = 0;
+    current.clear();
 }
 
 constexpr float kProjectMarginDeg = 0.005f;  // AZIMUTH slack of the footprints, ~8.7e-5 rad: 5x the polynomial atan2 error (1e-3 deg) + table / test rounding
@@ -468,24 +510,86 @@ int query_enter(ls_tracer *tr, hipStream_t s);
 int query_walk(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out, const RayQueryKind &kind,
                const float *const *motion = nullptr);   // motion: ls_trace_scene_sweep_moving's tables, one per layout entry
 int query_leave(ls_tracer *tr, hipStream_t s);
-// the host-memory variants stage in RayQuery::io: add() every piece (each starts 16-byte aligned), ensure total(), then form pointers
-struct IoPlan {
-    size_t bytes = 0;
-    size_t add(size_t n) { const size_t at = bytes; bytes += (n + 15) & ~(size_t)15; return at; }
-    size_t total() const { return bytes; }
+// the tail of every device entry point: the query's place on s around what it issues
+template <typename Issue>
+inline int query_run(ls_tracer *tr, hipStream_t s, Issue &&issue)
+{
+    int rc;
+    if ((rc = query_enter(tr, s)) || (rc = issue())) return rc;
+    return query_leave(tr, s);
+}
+// The host-memory variants stage in RayQuery::io, on the handle's stream.  A call declares every piece first -- in(): copied to the
+// device by commit(); out(): `records` records of `bytes` each, read back afterwards; scratch(): neither -- and a null or empty
+// piece is absent: no room, no copy, nullptr for an address.  commit() sizes q.io (a growing buffer: the frame path's frames in
+// flight never read it), starts the copies and fills in the Staged, which alone gives a piece's device address: no pointer can be
+// formed before the buffer has its final place.  Every piece starts 16-byte aligned.
+struct StagePiece {
+    void *host;
+    size_t at, bytes, record;   // record != 0: an output, in records of this size
+    bool copy_in;
 };
-// one output of a counted read-back: `bytes` of every record the device counted; rows != 0: rows x bytes at this pitch, whatever the count
-struct Fetch {
-    void *dst;   // (NULL: not wanted)
-    const uint8_t *src;
-    size_t bytes, rows = 0, pitch = 0;
+// a scratch piece read back as `rows` rows of `bytes` at `pitch`, from byte `first` of the piece to byte `first` of dst (NULL: not wanted)
+struct StridedRows {
+    void *dst;
+    int piece;
+    size_t first, bytes, rows, pitch;
 };
-// on the handle's stream: the count word comes back first (above limit: LS_ERR_HIP with this message), then the outputs; returns
-// when they are filled and *n_out is the count
-int fetch_counted(ls_tracer *tr, const void *d_count, size_t limit, const char *overflow, std::initializer_list<Fetch> outs, uint32_t *n_out);
-// ls_scan.cpp: what ls_trace_scene_sweep_moving refuses of its pose table, flags and motions, in its order (nothing of it needs a
-// commit or the device) -- shared with the gathers over its records (ls_gather.cpp)
-int motion_args_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags);
+class Staged {
+public:
+    template <typename T = uint8_t>
+    T *dev(int piece) const { return pieces[(size_t)piece].bytes ? reinterpret_cast<T *>(base + pieces[(size_t)piece].at) : nullptr; }
+    int fetch(ls_tracer *tr) const;   // every output whole; returns when they are filled
+    // the count word (a scratch piece) comes back first (above limit: LS_ERR_HIP with this message), then as many records of every
+    // output and, whatever the count, `strided`; returns when they are filled and *n_out is the count
+    int fetch_counted(ls_tracer *tr, int count, size_t limit, const char *overflow, uint32_t *n_out, const StridedRows *strided = nullptr) const;
+
+private:
+    friend class Staging;
+    std::vector<StagePiece> pieces;
+    uint8_t *base = nullptr;
+};
+class Staging {
+public:
+    int in(const void *src, size_t bytes) { return add(const_cast<void *>(src), src ? bytes : 0, 0, true); }
+    int out(void *dst, size_t records, size_t bytes) { return add(dst, dst ? records * bytes : 0, bytes, false); }
+    int scratch(size_t bytes) { return add(nullptr, bytes, 0, false); }
+    int commit(ls_tracer *tr, hipStream_t s, Staged &io);
+
+private:
+    int add(void *host, size_t bytes, size_t record, bool copy_in)
+    {
+        pieces.push_back({host, total, bytes, record, copy_in});
+        total += (bytes + 15) & ~(size_t)15;
+        return (int)pieces.size() - 1;
+    }
+    std::vector<StagePiece> pieces;
+    size_t total = 0;
+};
+// ls_scan.cpp: the pose table, the flags and the motions of ls_trace_scene_sweep_moving and of the gathers over its records
+// (ls_gather.cpp), as the caller gave them (host or device addresses; no table: the sensor at rest); after moving_resolve the layout
+// entry of every motion.  The walk takes the motion tables per layout entry, the gathers per geomID (nullptr: at rest).  A
+// host-memory variant declares the tables in its Staging (stage) and goes on with their device copies (use_staged)
+struct Moving {
+    const float *col_pose;
+    uint32_t n_cols;
+    const ls_geometry_motion *motions;
+    uint32_t n_motions, flags;
+    struct Entry { size_t slot; uint32_t geom; const float *table; int piece; };
+    std::vector<Entry> e;
+    int pose_piece = -1;
+    std::vector<const float *> per_slot(size_t n) const;
+    std::vector<const float *> per_geom(size_t n) const;   // (a geomID beyond n is left out: the kernels check against one bound)
+    void stage(const ls_tracer *tr, Staging &st);
+    void use_staged(const Staged &io);
+};
+// what every call refuses of them, in this order (nothing of it needs a commit or the device): the pose table's length and the flags
+// (pose_flags_check: these two alone), then the motions
+int pose_flags_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, uint32_t flags);
+int moving_args_check(ls_tracer *tr, const Moving &mv);
+// the device entry points' alignment test: p16 to 16 bytes; p4, the pose table and every motion table to 4
+bool moving_misaligned(std::initializer_list<const void *> p16, std::initializer_list<const void *> p4, const Moving &mv);
+// the last refusal, after uncommitted(): LS_ERR_UNKNOWN_GEOMETRY for a motion of a geometry that is not in the committed scene
+int moving_resolve(ls_tracer *tr, Moving &mv);
 #pragma GCC visibility pop
 // ls_gather.cpp
 void hit_attr_release(ls_tracer *tr);

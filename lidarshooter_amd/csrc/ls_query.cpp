@@ -1,8 +1,8 @@
 // ls_query.cpp -- the queries on the hierarchies and their host-memory variants: ls_trace_rays (closest hits of caller-supplied rays
 // against the committed scene), ls_occluded_rays (whether each ray hits anything: the same walk, stopping at a hit) and
 // ls_closest_points (the nearest surface point to each caller point: a distance-ordered walk, ls_points.hip); and what every query
-// entry point shares (ls_gather.cpp, ls_scan.cpp): the stream hand-over and the walk (query_enter / query_walk / query_leave), the
-// counted read-back (fetch_counted), stream_of.
+// entry point shares (ls_gather.cpp, ls_scan.cpp, ls_cloud.cpp): the stream hand-over and the walk (query_enter / query_walk /
+// query_leave), the host-memory variants' staging and read-back (Staging / Staged), stream_of.
 //
 // The query set (ls_tracer::RayQuery) is a hierarchy set of its own -- one hierarchy per geometry, built by the kernels of
 // the instanced commit (hier_layout / hier_build, ls_commit.cpp) into buffers nothing in the frame path reads or writes,
@@ -337,18 +337,38 @@ int query_leave(ls_tracer *tr, hipStream_t s)
 
 hipStream_t stream_of(const ls_tracer *tr, void *hip_stream) { return hip_stream ? static_cast<hipStream_t>(hip_stream) : tr->stream; }
 
-int fetch_counted(ls_tracer *tr, const void *d_count, size_t limit, const char *overflow, std::initializer_list<Fetch> outs, uint32_t *n_out)
+int Staging::commit(ls_tracer *tr, hipStream_t s, Staged &io)
+{
+    DevBuf<uint8_t> &buf = tr->rq.io;
+    if (const int rc = ensure(tr, buf, total)) return rc;
+    io.base = buf.p;
+    io.pieces.swap(pieces);
+    for (const StagePiece &p : io.pieces)
+        if (p.copy_in && p.bytes) LS_HIP(hipMemcpyAsync(io.base + p.at, p.host, p.bytes, hipMemcpyHostToDevice, s));
+    return LS_OK;
+}
+
+int Staged::fetch(ls_tracer *tr) const
+{
+    const hipStream_t s = tr->stream;
+    for (const StagePiece &p : pieces)
+        if (p.record && p.bytes) LS_HIP(hipMemcpyAsync(p.host, base + p.at, p.bytes, hipMemcpyDeviceToHost, s));
+    LS_HIP(hipStreamSynchronize(s));
+    return LS_OK;
+}
+
+int Staged::fetch_counted(ls_tracer *tr, int count_piece, size_t limit, const char *overflow, uint32_t *n_out, const StridedRows *strided) const
 {
     const hipStream_t s = tr->stream;
     uint32_t count = 0;
-    LS_HIP(hipMemcpyAsync(&count, d_count, 4, hipMemcpyDeviceToHost, s));
+    LS_HIP(hipMemcpyAsync(&count, dev(count_piece), 4, hipMemcpyDeviceToHost, s));
     LS_HIP(hipStreamSynchronize(s));
     if (count > limit) return fail(tr, LS_ERR_HIP, overflow);
-    for (const Fetch &f : outs) {
-        if (!f.dst) continue;
-        if (f.rows) LS_HIP(hipMemcpy2DAsync(f.dst, f.pitch, f.src, f.pitch, f.bytes, f.rows, hipMemcpyDeviceToHost, s));
-        else if (count) LS_HIP(hipMemcpyAsync(f.dst, f.src, (size_t)count * f.bytes, hipMemcpyDeviceToHost, s));
-    }
+    for (const StagePiece &p : pieces)
+        if (p.record && p.bytes && count) LS_HIP(hipMemcpyAsync(p.host, base + p.at, (size_t)count * p.record, hipMemcpyDeviceToHost, s));
+    if (strided && strided->dst)
+        LS_HIP(hipMemcpy2DAsync(static_cast<uint8_t *>(strided->dst) + strided->first, strided->pitch, dev(strided->piece) + strided->first,
+                                strided->pitch, strided->bytes, strided->rows, hipMemcpyDeviceToHost, s));
     LS_HIP(hipStreamSynchronize(s));
     *n_out = count;
     return LS_OK;
@@ -372,26 +392,21 @@ int rays_device(ls_tracer *tr, void *hip_stream, const void *d_in, uint32_t n, v
     const hipStream_t s = stream_of(tr, hip_stream);
     int rc;
     if ((rc = rays_check(tr, d_in, n, d_out, kind, false)) || !n) return rc;
-    if ((rc = query_enter(tr, s)) || (rc = query_walk(tr, s, d_in, n, d_out, kind))) return rc;
-    return query_leave(tr, s);
+    return query_run(tr, s, [&] { return query_walk(tr, s, d_in, n, d_out, kind); });
 }
 
 // the host-memory variant: queries and results staged in q.io, on the handle's stream; returns when out is filled
 int rays_host(ls_tracer *tr, const void *in, uint32_t n, void *out, const RayQueryKind &kind)
 {
-    ls_tracer::RayQuery &q = tr->rq;
     const hipStream_t s = tr->stream;
     int rc;
     if ((rc = rays_check(tr, in, n, out, kind, true)) || !n) return rc;
     if ((rc = query_enter(tr, s))) return rc;
-    IoPlan io;
-    const size_t at_in = io.add((size_t)n * kind.in_bytes), at_out = io.add((size_t)n * kind.out_bytes);
-    if ((rc = ensure(tr, q.io, io.total()))) return rc;   // (a growing buffer: the frame path's frames in flight never read it)
-    LS_HIP(hipMemcpyAsync(q.io.p + at_in, in, (size_t)n * kind.in_bytes, hipMemcpyHostToDevice, s));
-    if ((rc = query_walk(tr, s, q.io.p + at_in, n, q.io.p + at_out, kind))) return rc;
-    LS_HIP(hipMemcpyAsync(out, q.io.p + at_out, (size_t)n * kind.out_bytes, hipMemcpyDeviceToHost, s));
-    LS_HIP(hipStreamSynchronize(s));
-    return LS_OK;
+    Staging st;
+    const int p_in = st.in(in, (size_t)n * kind.in_bytes), p_out = st.out(out, n, kind.out_bytes);
+    Staged io;
+    if ((rc = st.commit(tr, s, io)) || (rc = query_walk(tr, s, io.dev(p_in), n, io.dev(p_out), kind))) return rc;
+    return io.fetch(tr);
 }
 
 }  // namespace

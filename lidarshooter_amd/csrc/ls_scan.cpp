@@ -17,11 +17,19 @@
 
 namespace lsi {
 
-int motion_args_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags)
+int pose_flags_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, uint32_t flags)
 {
     if (col_pose ? n_cols != tr->H : n_cols != 0u)
         return fail(tr, LS_ERR_INVALID_ARGUMENT, "one pose per azimuth column of the full raster (LS_INFO_AZIMUTH_COUNT), or no table and n_cols 0");
     if (flags & ~(uint32_t)LS_SWEEP_DESKEW) return fail(tr, LS_ERR_INVALID_ARGUMENT, "unknown sweep flags");
+    return LS_OK;
+}
+
+int moving_args_check(ls_tracer *tr, const Moving &mv)
+{
+    const ls_geometry_motion *motions = mv.motions;
+    const uint32_t n_motions = mv.n_motions;
+    if (const int rc = pose_flags_check(tr, mv.col_pose, mv.n_cols, mv.flags)) return rc;
     if (n_motions && !motions) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null motions with n_motions > 0");
     for (uint32_t k = 0; k < n_motions; ++k)
         if (!motions[k].col_motion) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a motion without a table");
@@ -35,7 +43,64 @@ int motion_args_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, con
     return LS_OK;
 }
 
+bool moving_misaligned(std::initializer_list<const void *> p16, std::initializer_list<const void *> p4, const Moving &mv)
+{
+    bool bad = misaligned(mv.col_pose, 4);
+    for (const void *p : p16) bad = bad || misaligned(p, 16);
+    for (const void *p : p4) bad = bad || misaligned(p, 4);
+    for (uint32_t k = 0; k < mv.n_motions; ++k) bad = bad || misaligned(mv.motions[k].col_motion, 4);
+    return bad;
+}
+
+int moving_resolve(ls_tracer *tr, Moving &mv)
+{
+    const std::vector<int> &ids = tr->slot_geom_ids;   // geometry ids in layout order
+    for (uint32_t k = 0; k < mv.n_motions; ++k) {
+        const size_t slot = (size_t)(std::find(ids.begin(), ids.end(), (int)mv.motions[k].geom) - ids.begin());
+        if (slot >= tr->layout.size()) return fail(tr, LS_ERR_UNKNOWN_GEOMETRY, "a motion names a geometry that is not in the committed scene");
+        mv.e.push_back({slot, mv.motions[k].geom, mv.motions[k].col_motion, -1});
+    }
+    return LS_OK;
+}
+
+std::vector<const float *> Moving::per_slot(size_t n) const
+{
+    std::vector<const float *> t(n, nullptr);
+    for (const Entry &x : e) t[x.slot] = x.table;
+    return t;
+}
+
+std::vector<const float *> Moving::per_geom(size_t n) const
+{
+    std::vector<const float *> t(n, nullptr);
+    for (const Entry &x : e)
+        if (x.geom < n) t[x.geom] = x.table;
+    return t;
+}
+
+// the pose table (H records of 48 bytes, or none) and the named geometries' tables (48 H bytes each: every one starts 16-byte aligned)
+void Moving::stage(const ls_tracer *tr, Staging &st)
+{
+    pose_piece = st.in(col_pose, (size_t)n_cols * 48);
+    for (Entry &x : e) x.piece = st.in(x.table, (size_t)tr->H * 48);
+}
+
+void Moving::use_staged(const Staged &io)
+{
+    col_pose = io.dev<const float>(pose_piece);
+    for (Entry &x : e) x.table = io.dev<const float>(x.piece);
+}
+
 namespace {
+
+// the last refusals of the sweeps, in this order: the shard's rays against the capacity and the limit of one call, the commit state
+int shard_check(ls_tracer *tr, uint32_t capacity)
+{
+    if (capacity < shard_rays(tr)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "capacity below the shard's ray count");
+    if (shard_rays(tr) > kMaxQueryRecords) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
+    tr->rq.last_built = 0;
+    return uncommitted(tr);   // (nothing is written, the count included)
+}
 
 // what both sweep entry points refuse, in this order (none of it needs a commit); host memory may have any alignment
 int sweep_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, uint32_t flags, const void *points32, const void *hits, const uint32_t *n_points,
@@ -47,174 +112,158 @@ int sweep_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, uint32_t 
     if (flags & ~(uint32_t)LS_SWEEP_DESKEW) return fail(tr, LS_ERR_INVALID_ARGUMENT, "unknown sweep flags");
     if (!host && (misaligned(col_pose, 4) || misaligned(n_points, 4) || misaligned16(points32, hits, rays_out)))
         return fail(tr, LS_ERR_INVALID_ARGUMENT, "points, hit records and rays must be 16-byte aligned, the poses and the count 4-byte aligned");
-    if (capacity < shard_rays(tr)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "capacity below the shard's ray count");
-    if (shard_rays(tr) > kMaxQueryRecords) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
-    tr->rq.last_built = 0;
-    return uncommitted(tr);   // (nothing is written, the count included)
+    return shard_check(tr, capacity);
 }
 
-int sweep_issue(ls_tracer *tr, hipStream_t s, const float *d_col_pose, uint32_t flags, void *d_points32, void *d_hits, uint32_t *d_n_points,
-                void *d_rays_out)
+// what both entry points of the sweep over moving geometries refuse, in this order; host memory may have any alignment
+int sweep_moving_check(ls_tracer *tr, Moving &mv, const void *points32, const void *hits, const uint32_t *n_points, uint32_t capacity, bool host)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (!n_points) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null count output");
+    if (const int rc = moving_args_check(tr, mv)) return rc;
+    if (!host && moving_misaligned({points32, hits}, {n_points}, mv))
+        return fail(tr, LS_ERR_INVALID_ARGUMENT, "points and hit records must be 16-byte aligned, the poses, the motion tables and the count 4-byte aligned");
+    if (const int rc = shard_check(tr, capacity)) return rc;
+    return moving_resolve(tr, mv);
+}
+
+// Both sweeps: the shard's rays, the closest-hit walk over them, the ordered pack.  No pose table: the sensor at rest -- the nominal
+// rays from the origin (the centre sample of a beam: ls_trace_scene's rays), nothing to deskew; no motions: the walk of
+// ls_trace_scene_sweep; d_rays_out: that call's
+int sweep_issue(ls_tracer *tr, hipStream_t s, const Moving &mv, void *d_points32, void *d_hits, uint32_t *d_n_points, void *d_rays_out)
 {
     ls_tracer::RayQuery &q = tr->rq;
     const uint32_t nq = shard_rays(tr);
-    int rc;
-    if ((rc = ensure(tr, q.sweep_rays, (size_t)nq * 32))) return rc;
-    if ((rc = ensure(tr, q.sweep_hits, (size_t)nq * 16))) return rc;
-    if ((rc = ensure(tr, q.sweep_counts, ls::sweep_block_count(nq)))) return rc;
-    const ls::SensorTables tb = tables(tr);
-    ls::launch_sweep_rays(s, tb, d_col_pose, q.sweep_rays.p, d_rays_out);
-    if ((rc = query_walk(tr, s, q.sweep_rays.p, nq, q.sweep_hits.p, closest_hits()))) return rc;
-    ls::launch_sweep_pack(s, tb, q.sweep_hits.p, q.sweep_counts.p, d_col_pose, (flags & LS_SWEEP_DESKEW) != 0, d_points32, d_hits, d_n_points);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
-}
-
-// what both beam entry points refuse, in this order, before anything touches the device; host memory may have any alignment
-int beams_check(ls_tracer *tr, const ls_beam_model *model, const void *points32, const void *hits, const uint32_t *echo, const uint32_t *n_points,
-                uint32_t capacity, bool host)
-{
-    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
-    if (!n_points) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null count output");
-    int status = LS_OK;
-    if (const char *why = ls::beam_model_invalid(model, shard_rays(tr), capacity, &status)) return fail(tr, status, why);
-    if (!host && (misaligned16(points32, hits) || misaligned(echo, 4) || misaligned(n_points, 4)))
-        return fail(tr, LS_ERR_INVALID_ARGUMENT, "points and hit records must be 16-byte aligned, the echo words and the count 4-byte aligned");
-    tr->rq.last_built = 0;
-    return uncommitted(tr);   // (nothing is written, the count included)
-}
-
-int beams_issue(ls_tracer *tr, hipStream_t s, const ls_beam_model *model, void *d_points32, void *d_hits, uint32_t *d_echo, uint32_t *d_n_points,
-                uint32_t capacity)
-{
-    ls_tracer::RayQuery &q = tr->rq;
-    const uint32_t nq = shard_rays(tr), S = model->n_samples, n = nq * S;   // n <= 2^27
-    ls::BeamPattern pat;   // the caller's pattern, read here and now: it travels in the kernel arguments
-    std::memset(static_cast<void *>(&pat), 0, sizeof(pat));
-    for (uint32_t k = 0; k < S; ++k) {
-        pat.a[k] = model->pattern[3 * k];
-        pat.b[k] = model->pattern[3 * k + 1];
-        pat.k[k] = model->pattern[3 * k + 2];
-    }
-    int rc;
-    if ((rc = ensure(tr, q.beam_rays, (size_t)n * 32))) return rc;
-    if ((rc = ensure(tr, q.beam_hits, (size_t)n * 16))) return rc;
-    if ((rc = ensure(tr, q.beam_blocks, 3 * (size_t)nq))) return rc;
-    if ((rc = ensure(tr, q.beam_counts, (size_t)nq + ls::beam_block_count(nq)))) return rc;
-    const ls::SensorTables tb = tables(tr);
-    ls::launch_beam_rays(s, tb, pat, S, q.beam_rays.p);
-    if ((rc = query_walk(tr, s, q.beam_rays.p, n, q.beam_hits.p, closest_hits()))) return rc;
-    ls::launch_beam_pack(s, tb, pat, S, model->echo_separation, model->min_count, model->returns, q.beam_hits.p, q.beam_blocks.p, q.beam_counts.p,
-                         q.beam_counts.p + nq, d_points32, d_hits, d_echo, d_n_points, capacity);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
-}
-
-// what both entry points of the beams under a sweep refuse, in this order, before anything touches the device; host memory may have
-// any alignment
-int beams_sweep_check(ls_tracer *tr, const ls_beam_model *model, const uint32_t *weights, const float *col_pose, uint32_t n_cols, uint32_t flags,
-                      const void *points32, const void *hits, const uint32_t *echo, const uint32_t *n_points, uint32_t capacity, bool host)
-{
-    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
-    if (!n_points) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null count output");
-    int status = LS_OK;
-    if (const char *why = ls::beam_model_invalid(model, shard_rays(tr), capacity, &status)) return fail(tr, status, why);
-    if (const char *why = ls::beam_weights_invalid(weights, model->n_samples)) return fail(tr, LS_ERR_INVALID_ARGUMENT, why);
-    if (col_pose ? n_cols != tr->H : n_cols != 0u)
-        return fail(tr, LS_ERR_INVALID_ARGUMENT, "one pose per azimuth column of the full raster (LS_INFO_AZIMUTH_COUNT), or no table and n_cols 0");
-    if (flags & ~(uint32_t)LS_SWEEP_DESKEW) return fail(tr, LS_ERR_INVALID_ARGUMENT, "unknown sweep flags");
-    if (!host && (misaligned16(points32, hits) || misaligned(echo, 4) || misaligned(n_points, 4) || misaligned(col_pose, 4)))
-        return fail(tr, LS_ERR_INVALID_ARGUMENT,
-                    "points and hit records must be 16-byte aligned, the echo words, the count and the poses 4-byte aligned");
-    tr->rq.last_built = 0;
-    return uncommitted(tr);   // (nothing is written, the count included)
-}
-
-int beams_sweep_issue(ls_tracer *tr, hipStream_t s, const ls_beam_model *model, const uint32_t *weights, uint32_t min_weight, const float *d_col_pose,
-                      uint32_t flags, void *d_points32, void *d_hits, uint32_t *d_echo, uint32_t *d_n_points, uint32_t capacity)
-{
-    ls_tracer::RayQuery &q = tr->rq;
-    const uint32_t nq = shard_rays(tr), S = model->n_samples, n = nq * S;   // n <= 2^27
-    ls::BeamPattern pat;   // the caller's pattern and weights, read here and now: they travel in the kernel arguments
-    std::memset(static_cast<void *>(&pat), 0, sizeof(pat));
-    for (uint32_t k = 0; k < S; ++k) {
-        pat.a[k] = model->pattern[3 * k];
-        pat.b[k] = model->pattern[3 * k + 1];
-        pat.k[k] = model->pattern[3 * k + 2];
-    }
-    uint32_t w_total = 0;
-    const ls::BeamWeights wts = ls::beam_weights_by_value(weights, S, &w_total);
-    const size_t n_blocks = ls::beam_block_count(nq);
-    int rc;
-    if ((rc = ensure(tr, q.beam_rays, (size_t)n * 32))) return rc;
-    if ((rc = ensure(tr, q.beam_hits, (size_t)n * 16))) return rc;
-    if ((rc = ensure(tr, q.beam_blocks, 3 * (size_t)nq))) return rc;
-    if ((rc = ensure(tr, q.beam_counts, (size_t)nq + n_blocks + 3 * (size_t)nq))) return rc;   // counts, block counts, a strength per record
-    const ls::SensorTables tb = tables(tr);
-    ls::launch_beam_sweep_rays(s, tb, pat, S, d_col_pose, q.beam_rays.p);
-    if ((rc = query_walk(tr, s, q.beam_rays.p, n, q.beam_hits.p, closest_hits()))) return rc;
-    ls::launch_beam_sweep_pack(s, tb, pat, wts, w_total, S, model->echo_separation, model->min_count, min_weight, model->returns, d_col_pose,
-                               (flags & LS_SWEEP_DESKEW) != 0, q.beam_hits.p, q.beam_blocks.p, q.beam_counts.p + nq + n_blocks, q.beam_counts.p,
-                               q.beam_counts.p + nq, d_points32, d_hits, d_echo, d_n_points, capacity);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
-}
-
-// what both entry points of the sweep over moving geometries refuse, in this order; host memory may have any alignment.  On LS_OK
-// table[i] is the motion table of layout entry i (nullptr: at rest)
-int moving_check(ls_tracer *tr, const float *col_pose, uint32_t n_cols, const ls_geometry_motion *motions, uint32_t n_motions, uint32_t flags,
-                 const void *points32, const void *hits, const uint32_t *n_points, uint32_t capacity, bool host, std::vector<const float *> &table)
-{
-    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
-    if (!n_points) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null count output");
-    if (const int rc = motion_args_check(tr, col_pose, n_cols, motions, n_motions, flags)) return rc;
-    if (!host) {
-        bool bad = misaligned(col_pose, 4) || misaligned(n_points, 4) || misaligned16(points32, hits);
-        for (uint32_t k = 0; k < n_motions; ++k) bad = bad || misaligned(motions[k].col_motion, 4);
-        if (bad)
-            return fail(tr, LS_ERR_INVALID_ARGUMENT,
-                        "points and hit records must be 16-byte aligned, the poses, the motion tables and the count 4-byte aligned");
-    }
-    if (capacity < shard_rays(tr)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "capacity below the shard's ray count");
-    if (shard_rays(tr) > kMaxQueryRecords) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many rays in one call");
-    tr->rq.last_built = 0;
-    if (const int rc = uncommitted(tr)) return rc;   // (nothing is written, the count included)
-    // every geomID to its layout entry: the walk takes the tables in layout order
-    table.assign(tr->layout.size(), nullptr);
-    for (uint32_t k = 0; k < n_motions; ++k) {
-        size_t i = 0;
-        while (i < tr->slot_geom_ids.size() && (uint32_t)tr->slot_geom_ids[i] != motions[k].geom) ++i;
-        if (i >= table.size()) return fail(tr, LS_ERR_UNKNOWN_GEOMETRY, "a motion names a geometry that is not in the committed scene");
-        table[i] = motions[k].col_motion;
-    }
-    return LS_OK;
-}
-
-// d_col_pose nullptr: the sensor at rest -- the nominal rays from the origin (the centre sample of a beam: ls_trace_scene's rays),
-// nothing to deskew; moving false: no motions -- the walk of ls_trace_scene_sweep
-int moving_issue(ls_tracer *tr, hipStream_t s, const float *d_col_pose, const std::vector<const float *> &d_table, bool moving, uint32_t flags,
-                 void *d_points32, void *d_hits, uint32_t *d_n_points)
-{
-    ls_tracer::RayQuery &q = tr->rq;
-    const uint32_t nq = shard_rays(tr);
+    const float *d_col_pose = mv.col_pose;
     int rc;
     if ((rc = ensure(tr, q.sweep_rays, (size_t)nq * 32))) return rc;
     if ((rc = ensure(tr, q.sweep_hits, (size_t)nq * 16))) return rc;
     if ((rc = ensure(tr, q.sweep_counts, ls::sweep_block_count(nq)))) return rc;
     const ls::SensorTables tb = tables(tr);
     if (d_col_pose) {
-        ls::launch_sweep_rays(s, tb, d_col_pose, q.sweep_rays.p, nullptr);
+        ls::launch_sweep_rays(s, tb, d_col_pose, q.sweep_rays.p, d_rays_out);
     } else {
         ls::BeamPattern pat;
         std::memset(static_cast<void *>(&pat), 0, sizeof(pat));
         pat.k[0] = 1.0f;
         ls::launch_beam_rays(s, tb, pat, 1, q.sweep_rays.p);
     }
-    if ((rc = query_walk(tr, s, q.sweep_rays.p, nq, q.sweep_hits.p, closest_hits(), moving ? d_table.data() : nullptr))) return rc;
-    ls::launch_sweep_pack(s, tb, q.sweep_hits.p, q.sweep_counts.p, d_col_pose, d_col_pose && (flags & LS_SWEEP_DESKEW) != 0, d_points32, d_hits,
+    const std::vector<const float *> d_motion = mv.per_slot(tr->layout.size());
+    if ((rc = query_walk(tr, s, q.sweep_rays.p, nq, q.sweep_hits.p, closest_hits(), mv.n_motions ? d_motion.data() : nullptr))) return rc;
+    ls::launch_sweep_pack(s, tb, q.sweep_hits.p, q.sweep_counts.p, d_col_pose, d_col_pose && (mv.flags & LS_SWEEP_DESKEW) != 0, d_points32, d_hits,
                           d_n_points);
     LS_HIP(hipGetLastError());
     return LS_OK;
+}
+
+// the poses (or none), the motion tables and the outputs staged in q.io, on the handle's stream; the count comes back first, then as
+// many records; of rays_out (ls_trace_scene_sweep_host's) only the shard's columns are written: V rows of naz records, at their
+// place in the rows of H
+int sweep_host(ls_tracer *tr, const char *overflow, Moving &mv, void *points32, void *hits, uint32_t *n_points, void *rays_out)
+{
+    const hipStream_t s = tr->stream;
+    int rc;
+    if ((rc = query_enter(tr, s))) return rc;
+    const size_t nq = shard_rays(tr), row_bytes = (size_t)tr->H * 32;
+    Staging st;
+    const int p_points = st.out(points32, nq, 32), p_hits = st.out(hits, nq, 16), p_rays = st.scratch(rays_out ? tr->V * row_bytes : 0),
+              p_n = st.scratch(4);
+    mv.stage(tr, st);
+    Staged io;
+    if ((rc = st.commit(tr, s, io))) return rc;
+    mv.use_staged(io);
+    if ((rc = sweep_issue(tr, s, mv, io.dev(p_points), io.dev(p_hits), io.dev<uint32_t>(p_n), io.dev(p_rays)))) return rc;
+    const StridedRows rows = {rays_out, p_rays, (size_t)tr->az0 * 32, (size_t)tr->naz * 32, tr->V, row_bytes};
+    return io.fetch_counted(tr, p_n, nq, overflow, n_points, &rows);
+}
+
+// what ls_trace_scene_beams_sweep takes beyond ls_trace_scene_beams (nullptr where a function serves both: that call)
+struct BeamSweep {
+    const uint32_t *weights;
+    uint32_t min_weight;
+    const float *col_pose;
+    uint32_t n_cols, flags;
+};
+
+// what the entry points of both beam frames refuse, in this order, before anything touches the device; host memory may have any alignment
+int beams_check(ls_tracer *tr, const ls_beam_model *model, const BeamSweep *sw, const void *points32, const void *hits, const uint32_t *echo,
+                const uint32_t *n_points, uint32_t capacity, bool host)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (!n_points) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null count output");
+    int status = LS_OK;
+    if (const char *why = ls::beam_model_invalid(model, shard_rays(tr), capacity, &status)) return fail(tr, status, why);
+    if (sw) {
+        if (const char *why = ls::beam_weights_invalid(sw->weights, model->n_samples)) return fail(tr, LS_ERR_INVALID_ARGUMENT, why);
+        if (const int rc = pose_flags_check(tr, sw->col_pose, sw->n_cols, sw->flags)) return rc;
+    }
+    if (!host && (misaligned16(points32, hits) || misaligned(echo, 4) || misaligned(n_points, 4) || (sw && misaligned(sw->col_pose, 4))))
+        return fail(tr, LS_ERR_INVALID_ARGUMENT,
+                    sw ? "points and hit records must be 16-byte aligned, the echo words, the count and the poses 4-byte aligned"
+                       : "points and hit records must be 16-byte aligned, the echo words and the count 4-byte aligned");
+    tr->rq.last_built = 0;
+    return uncommitted(tr);   // (nothing is written, the count included)
+}
+
+// Both beam frames: the sub-rays, the closest-hit walk over them, the echoes of every beam and their ordered pack -- each frame with
+// its own two launches.  The caller's pattern and weights are read here and now: they travel in the kernel arguments.  The scratch:
+// sub-rays, their hit records, the returns of every beam; in one array the return count of every beam, of every 256 of them and,
+// under a sweep, a strength per record
+int beams_issue(ls_tracer *tr, hipStream_t s, const ls_beam_model *model, const BeamSweep *sw, void *d_points32, void *d_hits, uint32_t *d_echo,
+                uint32_t *d_n_points, uint32_t capacity)
+{
+    ls_tracer::RayQuery &q = tr->rq;
+    const uint32_t nq = shard_rays(tr), S = model->n_samples, n = nq * S;   // n <= 2^27
+    const size_t n_blocks = ls::beam_block_count(nq);
+    ls::BeamPattern pat;
+    std::memset(static_cast<void *>(&pat), 0, sizeof(pat));
+    for (uint32_t k = 0; k < S; ++k) {
+        pat.a[k] = model->pattern[3 * k];
+        pat.b[k] = model->pattern[3 * k + 1];
+        pat.k[k] = model->pattern[3 * k + 2];
+    }
+    int rc;
+    if ((rc = ensure(tr, q.beam_rays, (size_t)n * 32))) return rc;
+    if ((rc = ensure(tr, q.beam_hits, (size_t)n * 16))) return rc;
+    if ((rc = ensure(tr, q.beam_blocks, 3 * (size_t)nq))) return rc;
+    if ((rc = ensure(tr, q.beam_counts, (size_t)nq + n_blocks + (sw ? 3 * (size_t)nq : 0)))) return rc;
+    const ls::SensorTables tb = tables(tr);
+    if (sw) ls::launch_beam_sweep_rays(s, tb, pat, S, sw->col_pose, q.beam_rays.p);
+    else ls::launch_beam_rays(s, tb, pat, S, q.beam_rays.p);
+    if ((rc = query_walk(tr, s, q.beam_rays.p, n, q.beam_hits.p, closest_hits()))) return rc;
+    if (sw) {
+        uint32_t w_total = 0;
+        const ls::BeamWeights wts = ls::beam_weights_by_value(sw->weights, S, &w_total);
+        ls::launch_beam_sweep_pack(s, tb, pat, wts, w_total, S, model->echo_separation, model->min_count, sw->min_weight, model->returns, sw->col_pose,
+                                   (sw->flags & LS_SWEEP_DESKEW) != 0, q.beam_hits.p, q.beam_blocks.p, q.beam_counts.p + nq + n_blocks, q.beam_counts.p,
+                                   q.beam_counts.p + nq, d_points32, d_hits, d_echo, d_n_points, capacity);
+    } else {
+        ls::launch_beam_pack(s, tb, pat, S, model->echo_separation, model->min_count, model->returns, q.beam_hits.p, q.beam_blocks.p, q.beam_counts.p,
+                             q.beam_counts.p + nq, d_points32, d_hits, d_echo, d_n_points, capacity);
+    }
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+// the poses (if any) and the outputs staged in q.io, on the handle's stream; the count comes back first, then as many records
+int beams_host(ls_tracer *tr, const char *overflow, const ls_beam_model *model, const BeamSweep *sw, void *points32, void *hits, uint32_t *echo,
+               uint32_t *n_points)
+{
+    const hipStream_t s = tr->stream;
+    int rc;
+    if ((rc = query_enter(tr, s))) return rc;
+    const size_t cap = (size_t)__builtin_popcount(model->returns) * shard_rays(tr);   // what the beams can give: <= 3 * 2^27
+    Staging st;
+    const int p_pose = st.in(sw ? sw->col_pose : nullptr, sw ? (size_t)sw->n_cols * 48 : 0), p_points = st.out(points32, cap, 32),
+              p_hits = st.out(hits, cap, 16), p_echo = st.out(echo, cap, 4), p_n = st.scratch(4);
+    Staged io;
+    if ((rc = st.commit(tr, s, io))) return rc;
+    BeamSweep d_sw = sw ? *sw : BeamSweep();
+    d_sw.col_pose = io.dev<const float>(p_pose);
+    if ((rc = beams_issue(tr, s, model, sw ? &d_sw : nullptr, io.dev(p_points), io.dev(p_hits), io.dev<uint32_t>(p_echo), io.dev<uint32_t>(p_n),
+                          (uint32_t)cap)))
+        return rc;
+    return io.fetch_counted(tr, p_n, cap, overflow, n_points);
 }
 
 // tau_h = t0 + h dt; Q_h = Rodrigues' rotation by ang_vel * tau_h, c_h = (pivot - Q_h pivot) + lin_vel * tau_h (pivot nullptr: the
@@ -268,103 +317,51 @@ int ls_trace_scene_sweep(ls_tracer *tr, void *hip_stream, const float *d_col_pos
 {
     LS_ENTER(tr);
     const hipStream_t s = stream_of(tr, hip_stream);
-    int rc;
-    if ((rc = sweep_check(tr, d_col_pose, n_cols, flags, d_points32, d_hits, d_n_points, capacity, d_rays_out, false))) return rc;
-    if ((rc = query_enter(tr, s)) || (rc = sweep_issue(tr, s, d_col_pose, flags, d_points32, d_hits, d_n_points, d_rays_out))) return rc;
-    return query_leave(tr, s);
+    if (const int rc = sweep_check(tr, d_col_pose, n_cols, flags, d_points32, d_hits, d_n_points, capacity, d_rays_out, false)) return rc;
+    const Moving mv = {d_col_pose, n_cols, nullptr, 0, flags};
+    return query_run(tr, s, [&] { return sweep_issue(tr, s, mv, d_points32, d_hits, d_n_points, d_rays_out); });
 }
 
-// the poses, the outputs and the optional ray records staged in q.io, on the handle's stream; the count comes back first, then as
-// many records; of rays_out only the shard's columns are written: V rows of naz records, at their place in the rows of H
 int ls_trace_scene_sweep_host(ls_tracer *tr, const float *col_pose, uint32_t n_cols, uint32_t flags, void *points32, void *hits, uint32_t *n_points,
                               uint32_t capacity, void *rays_out)
 {
     LS_ENTER(tr);
-    DevBuf<uint8_t> &buf = tr->rq.io;
-    const hipStream_t s = tr->stream;
-    int rc;
-    if ((rc = sweep_check(tr, col_pose, n_cols, flags, points32, hits, n_points, capacity, rays_out, true))) return rc;
-    if ((rc = query_enter(tr, s))) return rc;
-    const size_t nq = shard_rays(tr), row_bytes = (size_t)tr->H * 32, first = (size_t)tr->az0 * 32;
-    IoPlan io;
-    const size_t at_points = io.add(points32 ? nq * 32 : 0), at_hits = io.add(hits ? nq * 16 : 0), at_rays = io.add(rays_out ? tr->V * row_bytes : 0),
-                 at_pose = io.add((size_t)n_cols * 48), at_n = io.add(4);
-    if ((rc = ensure(tr, buf, io.total()))) return rc;
-    LS_HIP(hipMemcpyAsync(buf.p + at_pose, col_pose, (size_t)n_cols * 48, hipMemcpyHostToDevice, s));
-    if ((rc = sweep_issue(tr, s, reinterpret_cast<const float *>(buf.p + at_pose), flags, points32 ? buf.p + at_points : nullptr,
-                          hits ? buf.p + at_hits : nullptr, reinterpret_cast<uint32_t *>(buf.p + at_n), rays_out ? buf.p + at_rays : nullptr)))
-        return rc;
-    return fetch_counted(tr, buf.p + at_n, nq, "ls_trace_scene_sweep: more points than rays",
-                         {{points32, buf.p + at_points, 32},
-                          {hits, buf.p + at_hits, 16},
-                          {rays_out ? static_cast<uint8_t *>(rays_out) + first : nullptr, buf.p + at_rays + first, (size_t)tr->naz * 32, tr->V, row_bytes}},
-                         n_points);
+    if (const int rc = sweep_check(tr, col_pose, n_cols, flags, points32, hits, n_points, capacity, rays_out, true)) return rc;
+    Moving mv = {col_pose, n_cols, nullptr, 0, flags};
+    return sweep_host(tr, "ls_trace_scene_sweep: more points than rays", mv, points32, hits, n_points, rays_out);
 }
 
 int ls_trace_scene_beams(ls_tracer *tr, void *hip_stream, const ls_beam_model *model, void *d_points32, void *d_hits, uint32_t *d_echo,
                          uint32_t *d_n_points, uint32_t capacity)
 {
-    LS_ENTER_CHECKED(tr, beams_check(tr, model, d_points32, d_hits, d_echo, d_n_points, capacity, false));
+    LS_ENTER_CHECKED(tr, beams_check(tr, model, nullptr, d_points32, d_hits, d_echo, d_n_points, capacity, false));
     const hipStream_t s = stream_of(tr, hip_stream);
-    int rc;
-    if ((rc = query_enter(tr, s)) || (rc = beams_issue(tr, s, model, d_points32, d_hits, d_echo, d_n_points, capacity))) return rc;
-    return query_leave(tr, s);
+    return query_run(tr, s, [&] { return beams_issue(tr, s, model, nullptr, d_points32, d_hits, d_echo, d_n_points, capacity); });
 }
 
-// the outputs staged in q.io, on the handle's stream; the count comes back first, then as many records
 int ls_trace_scene_beams_host(ls_tracer *tr, const ls_beam_model *model, void *points32, void *hits, uint32_t *echo, uint32_t *n_points,
                               uint32_t capacity)
 {
-    LS_ENTER_CHECKED(tr, beams_check(tr, model, points32, hits, echo, n_points, capacity, true));
-    DevBuf<uint8_t> &buf = tr->rq.io;
-    const hipStream_t s = tr->stream;
-    int rc;
-    if ((rc = query_enter(tr, s))) return rc;
-    const size_t cap = (size_t)__builtin_popcount(model->returns) * shard_rays(tr);   // what the beams can give: <= 3 * 2^27
-    IoPlan io;
-    const size_t at_points = io.add(points32 ? cap * 32 : 0), at_hits = io.add(hits ? cap * 16 : 0), at_echo = io.add(echo ? cap * 4 : 0), at_n = io.add(4);
-    if ((rc = ensure(tr, buf, io.total()))) return rc;
-    if ((rc = beams_issue(tr, s, model, points32 ? buf.p + at_points : nullptr, hits ? buf.p + at_hits : nullptr,
-                          echo ? reinterpret_cast<uint32_t *>(buf.p + at_echo) : nullptr, reinterpret_cast<uint32_t *>(buf.p + at_n), (uint32_t)cap)))
-        return rc;
-    return fetch_counted(tr, buf.p + at_n, cap, "ls_trace_scene_beams: more returns than the beams can give",
-                         {{points32, buf.p + at_points, 32}, {hits, buf.p + at_hits, 16}, {echo, buf.p + at_echo, 4}}, n_points);
+    LS_ENTER_CHECKED(tr, beams_check(tr, model, nullptr, points32, hits, echo, n_points, capacity, true));
+    return beams_host(tr, "ls_trace_scene_beams: more returns than the beams can give", model, nullptr, points32, hits, echo, n_points);
 }
 
 int ls_trace_scene_beams_sweep(ls_tracer *tr, void *hip_stream, const ls_beam_model *model, const uint32_t *weights, uint32_t min_weight,
                                const float *d_col_pose, uint32_t n_cols, uint32_t flags, void *d_points32, void *d_hits, uint32_t *d_echo,
                                uint32_t *d_n_points, uint32_t capacity)
 {
-    LS_ENTER_CHECKED(tr, beams_sweep_check(tr, model, weights, d_col_pose, n_cols, flags, d_points32, d_hits, d_echo, d_n_points, capacity, false));
+    const BeamSweep sw = {weights, min_weight, d_col_pose, n_cols, flags};
+    LS_ENTER_CHECKED(tr, beams_check(tr, model, &sw, d_points32, d_hits, d_echo, d_n_points, capacity, false));
     const hipStream_t s = stream_of(tr, hip_stream);
-    int rc;
-    if ((rc = query_enter(tr, s)) ||
-        (rc = beams_sweep_issue(tr, s, model, weights, min_weight, d_col_pose, flags, d_points32, d_hits, d_echo, d_n_points, capacity)))
-        return rc;
-    return query_leave(tr, s);
+    return query_run(tr, s, [&] { return beams_issue(tr, s, model, &sw, d_points32, d_hits, d_echo, d_n_points, capacity); });
 }
 
-// the poses and the outputs staged in q.io, on the handle's stream; the count comes back first, then as many records
 int ls_trace_scene_beams_sweep_host(ls_tracer *tr, const ls_beam_model *model, const uint32_t *weights, uint32_t min_weight, const float *col_pose,
                                     uint32_t n_cols, uint32_t flags, void *points32, void *hits, uint32_t *echo, uint32_t *n_points, uint32_t capacity)
 {
-    LS_ENTER_CHECKED(tr, beams_sweep_check(tr, model, weights, col_pose, n_cols, flags, points32, hits, echo, n_points, capacity, true));
-    DevBuf<uint8_t> &buf = tr->rq.io;
-    const hipStream_t s = tr->stream;
-    int rc;
-    if ((rc = query_enter(tr, s))) return rc;
-    const size_t cap = (size_t)__builtin_popcount(model->returns) * shard_rays(tr);   // what the beams can give: <= 3 * 2^27
-    IoPlan io;
-    const size_t at_points = io.add(points32 ? cap * 32 : 0), at_hits = io.add(hits ? cap * 16 : 0), at_pose = io.add((size_t)n_cols * 48),
-                 at_echo = io.add(echo ? cap * 4 : 0), at_n = io.add(4);
-    if ((rc = ensure(tr, buf, io.total()))) return rc;
-    if (col_pose) LS_HIP(hipMemcpyAsync(buf.p + at_pose, col_pose, (size_t)n_cols * 48, hipMemcpyHostToDevice, s));
-    if ((rc = beams_sweep_issue(tr, s, model, weights, min_weight, col_pose ? reinterpret_cast<const float *>(buf.p + at_pose) : nullptr, flags,
-                                points32 ? buf.p + at_points : nullptr, hits ? buf.p + at_hits : nullptr,
-                                echo ? reinterpret_cast<uint32_t *>(buf.p + at_echo) : nullptr, reinterpret_cast<uint32_t *>(buf.p + at_n), (uint32_t)cap)))
-        return rc;
-    return fetch_counted(tr, buf.p + at_n, cap, "ls_trace_scene_beams_sweep: more returns than the beams can give",
-                         {{points32, buf.p + at_points, 32}, {hits, buf.p + at_hits, 16}, {echo, buf.p + at_echo, 4}}, n_points);
+    const BeamSweep sw = {weights, min_weight, col_pose, n_cols, flags};
+    LS_ENTER_CHECKED(tr, beams_check(tr, model, &sw, points32, hits, echo, n_points, capacity, true));
+    return beams_host(tr, "ls_trace_scene_beams_sweep: more returns than the beams can give", model, &sw, points32, hits, echo, n_points);
 }
 
 // host only: w_s = max(1, round(65535 exp(-((a / sigma_az)^2 + (b / sigma_el)^2) / 2))); double throughout, one rounding
@@ -424,42 +421,18 @@ int ls_motion_constant_twist(const float lin_vel[3], const float ang_vel[3], con
 int ls_trace_scene_sweep_moving(ls_tracer *tr, void *hip_stream, const float *d_col_pose, uint32_t n_cols, const ls_geometry_motion *motions,
                                 uint32_t n_motions, uint32_t flags, void *d_points32, void *d_hits, uint32_t *d_n_points, uint32_t capacity)
 {
-    std::vector<const float *> table;
-    LS_ENTER_CHECKED(tr, moving_check(tr, d_col_pose, n_cols, motions, n_motions, flags, d_points32, d_hits, d_n_points, capacity, false, table));
+    Moving mv = {d_col_pose, n_cols, motions, n_motions, flags};
+    LS_ENTER_CHECKED(tr, sweep_moving_check(tr, mv, d_points32, d_hits, d_n_points, capacity, false));
     const hipStream_t s = stream_of(tr, hip_stream);
-    int rc;
-    if ((rc = query_enter(tr, s)) || (rc = moving_issue(tr, s, d_col_pose, table, n_motions != 0, flags, d_points32, d_hits, d_n_points))) return rc;
-    return query_leave(tr, s);
+    return query_run(tr, s, [&] { return sweep_issue(tr, s, mv, d_points32, d_hits, d_n_points, nullptr); });
 }
 
-// the poses, the motion tables and the outputs staged in q.io, on the handle's stream; the count comes back first, then as many records
 int ls_trace_scene_sweep_moving_host(ls_tracer *tr, const float *col_pose, uint32_t n_cols, const ls_geometry_motion *motions, uint32_t n_motions,
                                      uint32_t flags, void *points32, void *hits, uint32_t *n_points, uint32_t capacity)
 {
-    std::vector<const float *> table;
-    LS_ENTER_CHECKED(tr, moving_check(tr, col_pose, n_cols, motions, n_motions, flags, points32, hits, n_points, capacity, true, table));
-    DevBuf<uint8_t> &buf = tr->rq.io;
-    const hipStream_t s = tr->stream;
-    int rc;
-    if ((rc = query_enter(tr, s))) return rc;
-    const size_t nq = shard_rays(tr), table_bytes = (size_t)tr->H * 48;
-    IoPlan io;
-    const size_t at_points = io.add(points32 ? nq * 32 : 0), at_hits = io.add(hits ? nq * 16 : 0), at_pose = io.add((size_t)n_cols * 48),
-                 at_motion = io.add((size_t)n_motions * table_bytes), at_n = io.add(4);   // (48 H: every table starts 16-byte aligned)
-    if ((rc = ensure(tr, buf, io.total()))) return rc;
-    if (col_pose) LS_HIP(hipMemcpyAsync(buf.p + at_pose, col_pose, (size_t)n_cols * 48, hipMemcpyHostToDevice, s));
-    size_t staged = 0;
-    for (const float *&t : table) {
-        if (!t) continue;
-        uint8_t *dst = buf.p + at_motion + staged++ * table_bytes;
-        LS_HIP(hipMemcpyAsync(dst, t, table_bytes, hipMemcpyHostToDevice, s));
-        t = reinterpret_cast<const float *>(dst);
-    }
-    if ((rc = moving_issue(tr, s, col_pose ? reinterpret_cast<const float *>(buf.p + at_pose) : nullptr, table, n_motions != 0, flags,
-                           points32 ? buf.p + at_points : nullptr, hits ? buf.p + at_hits : nullptr, reinterpret_cast<uint32_t *>(buf.p + at_n))))
-        return rc;
-    return fetch_counted(tr, buf.p + at_n, nq, "ls_trace_scene_sweep_moving: more points than rays",
-                         {{points32, buf.p + at_points, 32}, {hits, buf.p + at_hits, 16}}, n_points);
+    Moving mv = {col_pose, n_cols, motions, n_motions, flags};
+    LS_ENTER_CHECKED(tr, sweep_moving_check(tr, mv, points32, hits, n_points, capacity, true));
+    return sweep_host(tr, "ls_trace_scene_sweep_moving: more points than rays", mv, points32, hits, n_points, nullptr);
 }
 
 }  // extern "C"
