@@ -9,10 +9,12 @@
 // (ls_hit_attr.h, the arithmetic ls_debug_hit_attributes_on_triangle runs on the host), and three 16-byte stores.
 // A record is valid when the exact test from the ray's origin passes on the named triangle with t bit-equal to hit.t; a quad
 // tries its two triangles in order.  Every index is checked against its bound before an address is formed from it: the
-// ray, the geometry id, the element, the three vertex indices.  Anything else: flags = 0, zeros, the ray index echoed.
+// ray, the geometry id and the element here, the three vertex indices in record_on_triangle (ls_hit_gather.h, the test all four
+// gathers run; the sensor ray's direction: sensor_ray_dir, there too).  Anything else: flags = 0, zeros, the ray index echoed.
 #include "ls_kernels.h"
 #include "ls_device.h"
 #include "ls_hit_attr.h"
+#include "ls_hit_gather.h"
 
 namespace ls {
 
@@ -38,32 +40,17 @@ __global__ __launch_bounds__(kBlock) void k_hit_attributes(const uint4 *__restri
                 o[0] = r0.x; o[1] = r0.y; o[2] = r0.z;
                 d[0] = r1.x; d[1] = r1.y; d[2] = r1.z;
             } else {
-                // LidarDevice.cpp:310-316: d = (sin(theta)cos(phi), sin(theta)sin(phi), cos(theta)), the products the trace kernels form
-                const uint32_t v = h.x / tb.H, hh = h.x - v * tb.H;
-                const float st = tb.sin_theta[v];
-                const float2 cs = tb.cs_phi[hh];
-                d[0] = st * cs.x; d[1] = st * cs.y; d[2] = tb.cos_theta[v];
+                uint32_t v, hh;
+                sensor_ray_dir(tb, h.x, d, &v, &hh);
             }
-            const uint32_t halves = g.quad ? 2u : 1u;
-            for (uint32_t c = 0; c < halves && !flags; ++c) {
-                const uint32_t k = g.quad ? 2u * h.z + c : h.z;
-                const uint32_t *ix = g.idx + 3 * (size_t)k;
-                const uint32_t i0 = ix[0], i1 = ix[1], i2 = ix[2];
-                if (i0 >= g.n_verts || i1 >= g.n_verts || i2 >= g.n_verts) continue;
-                const V3 a = xform_vertex(g.m, g.verts + (size_t)i0 * g.stride);
-                const V3 b = xform_vertex(g.m, g.verts + (size_t)i1 * g.stride);
-                const V3 cc = xform_vertex(g.m, g.verts + (size_t)i2 * g.stride);
-                const float v0[3] = {a.x, a.y, a.z}, v1[3] = {b.x, b.y, b.z}, v2[3] = {cc.x, cc.y, cc.z};
-                float t, r9[9];
-                if (hit_attributes_on_triangle(o, d, v0, v1, v2, &t, r9) && __float_as_uint(t) == h.w) {
+            float t, r9[9];
+            if (record_on_triangle(g, h, o, d, &tri, &t, r9)) {
 #pragma unroll
-                    for (int j = 0; j < 9; ++j) res[j] = r9[j];
-                    if (!rays) {   // a sensor ray: xyz = t * dir with no sum, the bits of k_pack (EmbreeTracer.cpp:341-345)
-                        res[6] = t * d[0]; res[7] = t * d[1]; res[8] = t * d[2];
-                    }
-                    tri = k;
-                    flags = 1u;
+                for (int j = 0; j < 9; ++j) res[j] = r9[j];
+                if (!rays) {   // a sensor ray: xyz = t * dir with no sum, the bits of k_pack (EmbreeTracer.cpp:341-345)
+                    res[6] = t * d[0]; res[7] = t * d[1]; res[8] = t * d[2];
                 }
+                flags = 1u;
             }
         }
     }

@@ -305,6 +305,13 @@ void launch_hit_attributes(hipStream_t s, const void *hits, const uint32_t *d_co
 // 16-byte records of scratch; block_counts: returns_block_count(n) words.  refl: per-geomID reflectivities (nullptr, or geom >=
 // n_refl: 1.0).  Rays, table and sensor tables as launch_hit_attributes.
 size_t returns_block_count(uint32_t n);
+// the two halves of `park` for n records: n 16-byte (x, y, z, I), then n 16-byte (ray, geom, prim, t' bits)
+struct ParkHalves { float4 *point; uint4 *hit; };
+inline ParkHalves park_halves(const void *park, uint32_t n)
+{
+    float4 *point = static_cast<float4 *>(const_cast<void *>(park));
+    return {point, reinterpret_cast<uint4 *>(point + n)};
+}
 void launch_returns(hipStream_t s, const void *hits, const uint32_t *d_count, uint32_t n, const void *rays, uint32_t n_rays, const SensorTables &tb,
                     const AttrGeom *table, uint32_t n_table, const ls_return_model &model, uint32_t frame_index, const float *refl,
                     uint32_t n_refl, void *park, uint32_t *block_counts, void *points32, void *hits_out, uint32_t *n_out);

@@ -52,6 +52,9 @@ LS_SWEEP_HD void sweep_point(const float *p, float dx, float dy, float dz, float
     out3[2] = p[11] + t * d[2];
 }
 
+// whether a table's address allows 16-byte loads of its records (checked once per launch, or per table pointer: wave-uniform)
+LS_SWEEP_HD bool table_aligned16(const float *table) { return ((uintptr_t)table & 15u) == 0u; }
+
 #if defined(__HIPCC__)
 // the 12 floats of column h's record (k_sweep_rays, k_sweep_pack; k_beam_sweep_rays, k_beam_sweep_pack); aligned16: the table's
 // address allows three 16-byte loads per record
