@@ -41,6 +41,15 @@ int ls_debug_download_scene(ls_tracer *tr, float *verts_xyz, uint32_t *tri_idx);
  *   triangle record: float v0[3]; uint32 gid; float e1[3]; float NgC; float e2[3]; uint32 pad */
 int ls_debug_download_bvh(ls_tracer *tr, void *nodes, void *tri_records);
 
+/* The hierarchy of geometry geom_id in the frame path's instanced set (the default of the BVH engine: one hierarchy per geometry
+ * in MESH space): *n_leaves, *leaf_size, n_leaves - 1 binary nodes (64 B each, as above; references and leaf ranges local to the
+ * geometry), their n_leaves - 1 four-wide twins (128 B each: float4 lo[4], hi[4]; lo[c].w = slot c's reference, 0xFFFFFFFF empty)
+ * and the geometry's triangle records (48 B each: float v0[3]; uint32 local id; float v1[3]; uint32 0; float v2[3]; uint32 0 --
+ * the corners as uploaded).  NULL pointers: sizes only.  LS_ERR_NOT_COMMITTED when the commit was not instanced, and for wide128
+ * while the four-wide twins of this hierarchy have not been made; LS_ERR_UNKNOWN_GEOMETRY for a geometry the commit left out. */
+int ls_debug_download_hierarchy(ls_tracer *tr, uint32_t geom_id, uint32_t *n_leaves, uint32_t *leaf_size, void *nodes64, void *wide128,
+                                void *records48);
+
 /* The build path's radix sort on its own (ls_sort.hip): sorts n (key, value) pairs by their 30-bit keys in place (host
  * arrays; stable: equal keys keep their input order). */
 int ls_debug_sort_pairs(ls_tracer *tr, uint32_t *keys, uint32_t *vals, uint32_t n);

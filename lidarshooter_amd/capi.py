@@ -63,7 +63,7 @@ SYMBOLS = (
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
 DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_scene_size", "ls_debug_download_scene",
-                 "ls_debug_download_bvh", "ls_debug_sort_pairs", "ls_debug_expand_hits", "ls_debug_closest_on_triangle",
+                 "ls_debug_download_bvh", "ls_debug_download_hierarchy", "ls_debug_sort_pairs", "ls_debug_expand_hits", "ls_debug_closest_on_triangle",
                  "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model", "ls_debug_sweep_ray",
                  "ls_debug_beam_ray", "ls_debug_beam_echoes", "ls_debug_beam_model_check",
                  "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check", "ls_debug_motion_ray",
@@ -187,6 +187,10 @@ NODE_DTYPE = np.dtype([("llo", "<f4", 3), ("left", "<u4"), ("lhi", "<f4", 3), ("
 LEAF_BIT = 0x80000000
 TRI_DTYPE = np.dtype([("v0", "<f4", 3), ("gid", "<u4"), ("e1", "<f4", 3), ("NgC", "<f4"), ("e2", "<f4", 3),
                       ("pad", "<u4")])
+# ls_debug_download_hierarchy: a four-wide node (lo[c] = slot c's box minimum and reference, hi[c] = its maximum and 0) and an
+# instanced hierarchy's triangle record (the corners as uploaded, the triangle's index in its geometry)
+WIDE_DTYPE = np.dtype([("lo", "<f4", (4, 4)), ("hi", "<f4", (4, 4))])
+MESH_TRI_DTYPE = np.dtype([("v0", "<f4", 3), ("gid", "<u4"), ("v1", "<f4", 3), ("pad0", "<u4"), ("v2", "<f4", 3), ("pad1", "<u4")])
 
 _lib = None
 
@@ -331,6 +335,7 @@ def load() -> C.CDLL:
     L.ls_debug_scene_size.argtypes = [vp, u32p, u32p, u32p, u32p]
     L.ls_debug_download_scene.argtypes = [vp, vp, vp]
     L.ls_debug_download_bvh.argtypes = [vp, vp, vp]
+    L.ls_debug_download_hierarchy.argtypes = [vp, u32, u32p, u32p, vp, vp, vp]
     L.ls_debug_sort_pairs.argtypes = [vp, vp, vp, u32]
     L.ls_debug_expand_hits.argtypes = [vp, vp, u32, vp, vp, vp, u32, u32]
     _lib = L
@@ -1038,6 +1043,19 @@ class Tracer:
         tri = np.zeros(s["n_tris"], TRI_DTYPE)
         self._check(self.L.ls_debug_download_bvh(self.h, nodes.ctypes.data, tri.ctypes.data), "ls_debug_download_bvh")
         return nodes, tri, s["leaf_size"]
+
+    def downloadHierarchy(self, name: str, wide: bool = True):
+        """ls_debug_download_hierarchy: the instanced hierarchy of geometry `name` (mesh space) -> (binary nodes NODE_DTYPE, their
+        four-wide twins WIDE_DTYPE or None, records MESH_TRI_DTYPE, leaf size)"""
+        gid, nt = self.getGeometryId(name), self.getElementCount(name)
+        L, g = C.c_uint32(), C.c_uint32()
+        self._check(self.L.ls_debug_download_hierarchy(self.h, gid, C.byref(L), C.byref(g), None, None, None), "ls_debug_download_hierarchy")
+        nodes = np.zeros(max(L.value, 1) - 1, NODE_DTYPE)
+        twins = np.zeros(nodes.shape[0], WIDE_DTYPE) if wide else None
+        rec = np.zeros(nt, MESH_TRI_DTYPE)
+        self._check(self.L.ls_debug_download_hierarchy(self.h, gid, None, None, nodes.ctypes.data, twins.ctypes.data if wide else None,
+                                                       rec.ctypes.data), "ls_debug_download_hierarchy")
+        return nodes, twins, rec, g.value
 
 
 def closest_on_triangle(p, v0, v1, v2):

@@ -94,6 +94,38 @@ int ls_debug_download_bvh(ls_tracer *tr, void *nodes, void *tri_records)
     return LS_OK;
 }
 
+int ls_debug_download_hierarchy(ls_tracer *tr, uint32_t geom_id, uint32_t *n_leaves, uint32_t *leaf_size, void *nodes64, void *wide128,
+                                void *records48)
+{
+    LS_ENTER(tr);
+    if (!tr->committed || !tr->bvh_built || !tr->bvh_inst || !tr->inst_valid)
+        return fail(tr, LS_ERR_NOT_COMMITTED, "no instanced hierarchies: commit with LS_OPT_ENGINE = 1 and LS_OPT_BVH_INSTANCED = 1");
+    size_t i = 0;
+    while (i < tr->slot_geom_ids.size() && (uint32_t)tr->slot_geom_ids[i] != geom_id) ++i;
+    if (i >= tr->slot_geom_ids.size() || i >= tr->inst_layout.size()) return fail(tr, LS_ERR_UNKNOWN_GEOMETRY, "no such geometry in the committed scene");
+    Geometry *ge = nullptr;
+    {
+        const int rc = committed_geometry(tr, i, &ge);
+        if (rc) return rc;
+    }
+    const ls_tracer::InstSlot &sl = tr->inst_layout[i];
+    if (n_leaves) *n_leaves = sl.n_leaves;
+    if (leaf_size) *leaf_size = tr->inst_leaf_size;
+    if (!nodes64 && !wide128 && !records48) return LS_OK;
+    if (wide128 && sl.n_leaves > 1u && (!tr->wide_valid || !sl.wide_made))
+        return fail(tr, LS_ERR_NOT_COMMITTED, "the four-wide twins of this hierarchy have not been made");
+    {
+        const int rc = flush_pipeline(tr);
+        if (rc) return rc;
+    }
+    LS_HIP(hipStreamSynchronize(tr->stream));
+    const size_t n_nodes = sl.n_leaves ? sl.n_leaves - 1u : 0u;
+    if (nodes64 && n_nodes) LS_HIP(hipMemcpy(nodes64, tr->nodes.p + sl.node_first, n_nodes * sizeof(ls::FatNode), hipMemcpyDeviceToHost));
+    if (wide128 && n_nodes) LS_HIP(hipMemcpy(wide128, tr->wide_nodes.p + sl.node_first, n_nodes * sizeof(ls::WideNode), hipMemcpyDeviceToHost));
+    if (records48) LS_HIP(hipMemcpy(records48, tr->records.p + sl.rec_first, (size_t)ge->n_tris * sizeof(ls::TriRecord), hipMemcpyDeviceToHost));
+    return LS_OK;
+}
+
 int ls_debug_sort_pairs(ls_tracer *tr, uint32_t *keys, uint32_t *vals, uint32_t n)
 {
     LS_ENTER(tr);

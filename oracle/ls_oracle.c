@@ -344,6 +344,35 @@ void lso_trace_bruteforce(const float *dirs, uint32_t nrays, const float *verts,
     for (int i = 0; i < nthreads; ++i) pthread_join(th[i], NULL);
 }
 
+/* Brute-force closest hit of caller rays (32-byte records: origin, tmin, direction, tmax) -- the loop the ray-query tests run
+ * around lso_tri_intersect, here for scenes in which every ray meets thousands of triangles: every triangle in ascending id from
+ * the ray's origin, a hit kept when tmin <= t <= tmax and t < the running best (+inf at first); a ray with a non-finite origin or
+ * direction, a zero direction or tmin > tmax misses. */
+void lso_rays_bruteforce(const float *rays8, uint32_t nrays, const float *verts, const uint32_t *tris, uint32_t ntris, float *t,
+                         uint32_t *gid)
+{
+    for (uint32_t r = 0; r < nrays; ++r) {
+        const float *ray = rays8 + 8 * (size_t)r;
+        const float tmin = ray[3], tmax = ray[7];
+        t[r] = -1.0f;
+        gid[r] = LSO_INVALID;
+        int ok = tmin <= tmax && (ray[4] != 0.0f || ray[5] != 0.0f || ray[6] != 0.0f);
+        for (int a = 0; a < 3; ++a) ok = ok && isfinite(ray[a]) && isfinite(ray[4 + a]);
+        if (!ok) continue;
+        float best = INFINITY;
+        for (uint32_t k = 0; k < ntris; ++k) {
+            float tt;
+            if (lso_tri_intersect(ray, ray + 4, verts + 3 * (size_t)tris[3 * k + 0], verts + 3 * (size_t)tris[3 * k + 1],
+                                  verts + 3 * (size_t)tris[3 * k + 2], &tt) &&
+                tmin <= tt && tt <= tmax && tt < best) {
+                best = tt;
+                t[r] = tt;
+                gid[r] = k;
+            }
+        }
+    }
+}
+
 /* ------------------------------------------------------------------------------------------
  * CPU BVH tracer used (a) as the cpu_baseline of bench.py and (b) to check full-size GPU
  * results.  Binned-SAH BVH2, leaves <= 4 triangles, single-ray stack traversal, near child

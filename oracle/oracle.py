@@ -59,6 +59,7 @@ def lib() -> C.CDLL:
         L.lso_set_edge_rule.argtypes = [C.c_int]
         L.lso_get_edge_rule.restype = C.c_int
         L.lso_trace_bruteforce.argtypes = [f32p, C.c_uint32, f32p, u32p, C.c_uint32, f32p, u32p, C.c_int]
+        L.lso_rays_bruteforce.argtypes = [f32p, C.c_uint32, f32p, u32p, C.c_uint32, f32p, u32p]
         L.lso_bvh_build.argtypes = [f32p, u32p, C.c_uint32, C.c_int]
         L.lso_bvh_build.restype = C.c_void_p
         L.lso_bvh_free.argtypes = [C.c_void_p]
@@ -385,6 +386,18 @@ def trace_bruteforce(dirs: np.ndarray, scene: Scene, nthreads: int = 8):
     tr = np.ascontiguousarray(scene.tris, np.uint32)
     lib().lso_trace_bruteforce(_p(dirs, C.c_float), n, _p(v, C.c_float), _p(tr, C.c_uint32), tr.shape[0],
                                _p(t, C.c_float), _p(gid, C.c_uint32), nthreads)
+    return t, gid
+
+
+def rays_bruteforce(rays: np.ndarray, scene: Scene):
+    """Closest hit of caller rays (float32 (n, 8): origin, tmin, direction, tmax) by brute force: lso_tri_intersect over every triangle
+    in ascending global id, a hit kept when tmin <= t <= tmax and t < the running best -> (t float32[n], -1 = miss; gid uint32[n])"""
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    n = rays.shape[0]
+    t, gid = np.zeros(n, np.float32), np.zeros(n, np.uint32)
+    verts, tris = np.ascontiguousarray(scene.verts, np.float32), np.ascontiguousarray(scene.tris, np.uint32)
+    lib().lso_rays_bruteforce(_p(rays, C.c_float), n, _p(verts, C.c_float), _p(tris, C.c_uint32), tris.shape[0], _p(t, C.c_float),
+                              _p(gid, C.c_uint32))
     return t, gid
 
 
