@@ -919,6 +919,83 @@ int ls_apply_return_model_moving_host(ls_tracer *tr, const ls_return_model *mode
                                       const float *reflectivity, uint32_t n_reflectivity,
                                       void *points32, void *hits_out, uint32_t *n_out);
 
+/* ---- surface and Doppler velocity at hit records.  An FMCW LiDAR reports the range rate next to every point, and scene-flow and
+ * moving-object labels are made of the surface's velocity.  The frame calls above say where a hit is; this gather says how fast the
+ * surface there moves, how fast the sensor's origin moves, and the rate at which the range between the two changes.  The rate is no
+ * difference of pose or motion tables (their float32 quantisation divided by a column spacing of tens of microseconds is more than
+ * 0.1 m/s of noise at 100 m): the caller supplies the instantaneous twist of every moving body per column, as they supply its
+ * displacement per column, and the call evaluates the rigid-body velocity field at the hit point. */
+typedef struct ls_geometry_twist {
+    uint32_t geom;            /* geomID */
+    uint32_t reserved;        /* must be 0 */
+    const float *col_twist;   /* H records of 6 floats [w | u]; DEVICE memory for the device call, host memory for _host */
+} ls_geometry_twist;
+
+/*   twist tables: a record is a spatial twist [w | u] in the handle's sensor frame as the scene was committed -- the frame the pose
+ *            and motion tables use --: a material point of the body that is at x at the instant column h fires moves with v(x) =
+ *            u_h + w_h x x.  LS_INFO_AZIMUTH_COUNT records indexed by the GLOBAL column whatever the shard, 4-byte aligned, in device
+ *            memory, never read on the host.
+ *   d_sensor_twist: NULL (the sensor at rest), or one such table for the sensor body.
+ *   twists:  HOST memory, n_twists entries, read during the call, like motions; each names a geometry of the committed scene once;
+ *            geometries not named have velocity 0.  Twists and motions are independent of each other: a frame of ls_trace_scene (no
+ *            pose table, no motions) with twists gives the Doppler field of a snapshot; a frame of ls_trace_scene_sweep_moving gets
+ *            both, and the caller makes both from the same motion (ls_motion_constant_twist and ls_twist_table_constant).
+ *   d_col_pose, n_cols, motions, n_motions: exactly the arguments of ls_hit_attributes_moving -- the tables the frame was traced with.
+ *   flags:   must be 0; LS_SWEEP_DESKEW has no meaning here and is refused like any other bit.
+ *   d_hits, d_count, n: as ls_hit_attributes; hit.ray is the global ray index.  The call does not depend on the shard.
+ * Per handled record, ONE float32 operation sequence with no fused multiply-add (csrc/ls_velocity.h; ls_debug_hit_velocity in
+ * lidarshooter_hip_debug.h runs it on the host):
+ *   1. column h = hit.ray % H and the nominal d; the ray the column cast, (o, c) = ls_debug_sweep_ray's record for pose[h], or (0, d)
+ *      without a pose table; the ray the record's geometry saw, as ls_hit_attributes_moving rebuilds it;
+ *   2. validity is exactly ls_hit_attributes_moving's for the same tables: the indices in range, a usable ray for the geometry, the
+ *      exact test with t bit-equal to hit.t.  The valid bit of record i equals the valid bit that call gives record i, always; every
+ *      index -- the ray, the geomID, the element, the vertices, the column -- is checked before an address is formed from it;
+ *   3. the hit point at its own instant, in the frame-start frame: P_i = o_i + t * c_i, one product and one sum (without a pose table o
+ *      is +0: t * d_i numerically);
+ *   4. the surface velocity, with (w, u) = twist[hit.geom][h]: v_s,0 = u_0 + (w_1 P_2 - w_2 P_1), v_s,1 = u_1 + (w_2 P_0 - w_0 P_2),
+ *      v_s,2 = u_2 + (w_0 P_1 - w_1 P_0), every product, difference and sum rounded once; without a twist for the geometry (+0, +0, +0);
+ *   5. the velocity of the sensor's origin v_o: the same sequence with the sensor's record h at o; without a sensor twist (+0, +0, +0);
+ *   6. rel_i = v_s,i - v_o,i; len = sqrtf((c_0 c_0 + c_1 c_1) + c_2 c_2), the return model's len; radial = ((rel_0 c_0 + rel_1 c_1) +
+ *      rel_2 c_2) / len.  Positive: the range grows.  The range rate of a material point is (v_p - v_o) . c^: a sensor that TURNS
+ *      about its own origin contributes nothing to it -- the sensor's w enters only through v_o, which it leaves alone at o = 0 --,
+ *      so do not expect the sensor's ang_vel to show up in `radial`.
+ *   d_out:   NULL, or one 32-byte record per handled hit, 16-byte aligned, in input order: v_s xyz f32@0, radial f32@12, v_o xyz
+ *            f32@16, flags u32@28 (bit 0 valid, the others 0).  An invalid record: zeros and flags 0.
+ *   d_radial: NULL, or n floats, 4-byte aligned: the radial of a valid record, 0x7FC00000 for an invalid one -- the dense field a
+ *            publisher puts next to the cloud.
+ *   At least one of the two must be given when n > 0; nothing is written past min(n, *d_count) records.  A non-finite twist entry
+ *   gives non-finite values in a record that stays valid: the sequence is what it is.
+ * LS_ERR_INVALID_ARGUMENT before any device call, in this order: a frame graph is open; NULL hit records with n > 0, or both outputs
+ * NULL with n > 0; ls_trace_scene_sweep_moving's checks of the pose table, the flags (none is known here) and the motions, in its
+ * order; twists NULL with n_twists > 0; a NULL twist table; a non-zero reserved; n_twists above ls_geometry_count() or the same geom
+ * twice; misaligned pointers for the device call (records 16 bytes; words, tables and d_radial 4).  Then LS_ERR_OUT_OF_RANGE for an n
+ * above the query-record limit, then the commit state as ls_hit_attributes (-1 writes nothing), then LS_ERR_UNKNOWN_GEOMETRY for a
+ * motion or a twist whose geom is not in the committed scene.  Stream order, scratch and the frame graph rule are those of
+ * ls_hit_attributes_moving; LS_INFO_RAY_QUERY_BUILT is left as it is: nothing is built.
+ * Not offered: beam echoes (their t is a reported range: the records are invalid, as for the attributes); deforming meshes; vectors
+ * in the instantaneous sensor frame; a velocity source for ls_format_cloud; a call of the ITracer adapter. */
+int ls_hit_velocities(ls_tracer *tr, void *hip_stream,
+                      const float *d_col_pose, uint32_t n_cols,
+                      const ls_geometry_motion *motions, uint32_t n_motions,
+                      const float *d_sensor_twist,
+                      const ls_geometry_twist *twists, uint32_t n_twists, uint32_t flags,
+                      const void *d_hits, const uint32_t *d_count, uint32_t n,
+                      void *d_out, float *d_radial);
+/* The same with host memory (pageable, any alignment) in and out and no count word, on the handle's stream: the tables are copied to
+ * the device; returns when the outputs are filled. */
+int ls_hit_velocities_host(ls_tracer *tr, const float *col_pose, uint32_t n_cols,
+                           const ls_geometry_motion *motions, uint32_t n_motions,
+                           const float *sensor_twist,
+                           const ls_geometry_twist *twists, uint32_t n_twists, uint32_t flags,
+                           const void *hits, uint32_t n, void *out, float *radial);
+/* Twist table of a body at a constant twist (host only, no handle, no device): tau_h = t0 + h * dt; w_h = ang_vel, u_h = lin_vel -
+ * ang_vel x (pivot + lin_vel * tau_h), evaluated in double and rounded once -- the twist of the body whose displacement table
+ * ls_motion_constant_twist writes for the same arguments; with pivot = 0 the twist of the sensor of ls_sweep_poses_constant_twist.
+ * With ang_vel = 0 every record is (0, 0, 0, lin_vel) bit for bit.  col_twist: n_cols records of 6 floats.
+ * LS_ERR_INVALID_ARGUMENT for NULL pointers or non-finite inputs. */
+int ls_twist_table_constant(const float lin_vel[3], const float ang_vel[3], const float pivot[3],
+                            double t0, double dt, uint32_t n_cols, float *col_twist);
+
 /* ---- clouds in a driver's own PointCloud2 layout.  Every frame call above leaves the same fixed cloud: 32-byte XYZIR records
  * (XYZIRBytes.cpp:24-40), compacted, and next to it the ls_hit records (and, for beams, the echo words).  What a driver publishes
  * differs: Velodyne's 22-byte XYZIRT with a per-point `time` (what LIO-SAM, FAST-LIO and KISS-ICP deskew by), Ouster's organized

@@ -118,6 +118,11 @@ int ls_debug_motion_ray(const float ray8_in[8], const float motion12[12], float 
  * was committed, carried forward by one motion record, on the host (no device, no handle): the float32 operation sequence
  * k_hit_attributes_moving runs (csrc/ls_motion.h) -> out_i = (Q[i][0] n_0 + Q[i][1] n_1) + Q[i][2] n_2 */
 int ls_debug_motion_normal(const float n3[3], const float motion12[12], float out3[3]);
+/* one valid record of ls_hit_velocities on the host (no device, no handle): the float32 operation sequence k_hit_velocities runs
+ * (csrc/ls_velocity.h) for a hit at t along the ray its column cast (cast8: ls_debug_sweep_ray's record, or origin 0 and the nominal
+ * direction without a pose table), with the column's twist records [w | u] of the sensor and of the geometry that was hit; either
+ * may be NULL: at rest, that velocity is (+0, +0, +0) -> the 32-byte record: v_s xyz, radial, v_o xyz, flags = 1 */
+int ls_debug_hit_velocity(const float cast8[8], float t, const float sensor_twist6[6], const float geom_twist6[6], float out8[8]);
 
 /* one record of ls_format_cloud on the host (no device, no handle): the operation sequence k_format_cloud runs per record
  * (csrc/ls_cloud_format.h).  point32: the 32-byte point, or NULL (zeros: the format names none of its fields); hit: the ls_hit, or

@@ -59,6 +59,7 @@ SYMBOLS = (
     "ls_trace_scene_beams_sweep", "ls_trace_scene_beams_sweep_host", "ls_beam_weights_gaussian",
     "ls_trace_scene_sweep_moving", "ls_trace_scene_sweep_moving_host", "ls_motion_constant_twist",
     "ls_hit_attributes_moving", "ls_hit_attributes_moving_host", "ls_apply_return_model_moving", "ls_apply_return_model_moving_host",
+    "ls_hit_velocities", "ls_hit_velocities_host", "ls_twist_table_constant",
     "ls_format_cloud", "ls_format_cloud_host", "ls_cloud_format_check", "ls_cloud_format_from_point_fields", "ls_column_times",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
@@ -67,7 +68,7 @@ DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_s
                  "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model", "ls_debug_sweep_ray",
                  "ls_debug_beam_ray", "ls_debug_beam_echoes", "ls_debug_beam_model_check",
                  "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check", "ls_debug_motion_ray",
-                 "ls_debug_motion_normal", "ls_debug_format_record")
+                 "ls_debug_motion_normal", "ls_debug_hit_velocity", "ls_debug_format_record")
 
 
 class SensorDesc(C.Structure):
@@ -111,6 +112,12 @@ class GeometryMotion(C.Structure):
     """ls_geometry_motion: the geomID of a geometry that moves during the turn and its table of H records [Q | c] (an address:
     device memory for the device call, host memory for the host variant)"""
     _fields_ = [("geom", C.c_uint32), ("reserved", C.c_uint32), ("col_motion", C.c_void_p)]
+
+
+class GeometryTwist(C.Structure):
+    """ls_geometry_twist: the geomID of a moving geometry and its table of H twist records [w | u] (an address: device memory for
+    the device call, host memory for the host variant)"""
+    _fields_ = [("geom", C.c_uint32), ("reserved", C.c_uint32), ("col_twist", C.c_void_p)]
 
 
 # ls_format_cloud: the sources of a cloud field, the sensor_msgs::PointField datatypes, the limits and the flag
@@ -182,6 +189,9 @@ CLOSEST_DTYPE = np.dtype([("q", "<f4", 3), ("dist", "<f4"), ("geom", "<u4"), ("p
 # ls_hit_attributes: surface attributes of one ls_hit (flags bit 0: valid; an invalid record is zeros but for `ray`)
 HIT_ATTR_DTYPE = np.dtype([("n", "<f4", 3), ("cos_inc", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4"), ("flags", "<u4"),
                            ("p", "<f4", 3), ("ray", "<u4")])
+# ls_hit_velocities: the surface's velocity, the range rate and the velocity of the sensor's origin at one ls_hit (flags bit 0: valid;
+# an invalid record is zeros)
+HIT_VELOCITY_DTYPE = np.dtype([("v_s", "<f4", 3), ("radial", "<f4"), ("v_o", "<f4", 3), ("flags", "<u4")])
 NODE_DTYPE = np.dtype([("llo", "<f4", 3), ("left", "<u4"), ("lhi", "<f4", 3), ("right", "<u4"),
                        ("rlo", "<f4", 3), ("pad0", "<u4"), ("rhi", "<f4", 3), ("pad1", "<u4")])
 LEAF_BIT = 0x80000000
@@ -323,6 +333,10 @@ def load() -> C.CDLL:
     L.ls_apply_return_model_moving_host.argtypes = [vp, C.POINTER(ReturnModel), u32, vp, u32, C.POINTER(GeometryMotion), u32, u32, vp, u32, vp, u32,
                                                     vp, vp, u32p]
     L.ls_debug_motion_normal.argtypes = [f32p, f32p, f32p]
+    L.ls_hit_velocities.argtypes = [vp, vp, vp, u32, C.POINTER(GeometryMotion), u32, vp, C.POINTER(GeometryTwist), u32, u32, vp, vp, u32, vp, vp]
+    L.ls_hit_velocities_host.argtypes = [vp, vp, u32, C.POINTER(GeometryMotion), u32, vp, C.POINTER(GeometryTwist), u32, u32, vp, u32, vp, vp]
+    L.ls_twist_table_constant.argtypes = [f32p, f32p, f32p, C.c_double, C.c_double, u32, f32p]
+    L.ls_debug_hit_velocity.argtypes = [f32p, C.c_float, f32p, f32p, f32p]
     L.ls_format_cloud.argtypes = [vp, vp, C.POINTER(CloudFormat), vp, vp, vp, vp, u32, vp, vp, vp]
     L.ls_format_cloud_host.argtypes = [vp, C.POINTER(CloudFormat), vp, vp, vp, u32, vp, vp, vp]
     L.ls_cloud_format_check.argtypes = [C.POINTER(CloudFormat)]
@@ -917,6 +931,49 @@ class Tracer:
                                                  d_hits_out or None, d_n_out or None)
         return -1 if rc == -1 else int(self._check(rc, "ls_apply_return_model_moving"))
 
+    @staticmethod
+    def _device_twists(twists):
+        items = list(dict(twists).items())
+        arr = (GeometryTwist * max(1, len(items)))()
+        for m, (g, addr) in zip(arr, items):
+            m.geom, m.reserved, m.col_twist = int(g), 0, int(addr)
+        return (arr if items else None), len(items)
+
+    def hitVelocities(self, hits, col_pose=None, motions=(), sensor_twist=None, twists=(), flags: int = 0, records: bool = True,
+                      radial: bool = True):
+        """Velocities at hit records (ls_hit_velocities_host): `hits`, `col_pose` and `motions` as hitAttributesMoving takes them --
+        the tables the frame was traced with --; `sensor_twist` None (the sensor at rest) or float32 (H, 6) records [w | u];
+        `twists` a dict geomID -> float32 (H, 6) (geometries not named are at rest).  -> (rc, HIT_VELOCITY_DTYPE[n] or None, the
+        radial velocities float32[n] or None -- NaN for an invalid record); rc = -1 (no commit, empty scene): every record invalid."""
+        h = self._hit_array(hits)
+        n = h.shape[0]
+        *tables, keep = self._host_tables(col_pose, motions)
+        H = self.info(LS_INFO_AZIMUTH_COUNT)
+        st = None if sensor_twist is None else np.ascontiguousarray(sensor_twist, np.float32)
+        tabs = {int(g): np.ascontiguousarray(t, np.float32) for g, t in dict(twists).items()}
+        if any(t.shape != (H, 6) for t in list(tabs.values()) + ([] if st is None else [st])):
+            raise ValueError("twists: float32 (H, 6) per body")
+        arr, n_twists = self._device_twists({g: t.ctypes.data for g, t in tabs.items()})
+        out = np.zeros(n, HIT_VELOCITY_DTYPE) if records else None
+        rad = np.full(n, np.nan, np.float32) if radial else None
+        rc = self.L.ls_hit_velocities_host(self.h, *tables, None if st is None else st.ctypes.data, arr, n_twists, flags, h.ctypes.data if n else None,
+                                           n, out.ctypes.data if records and n else None, rad.ctypes.data if radial and n else None)
+        if rc != -1:
+            self._check(rc, "ls_hit_velocities_host")
+        return int(rc), out, rad
+
+    def hitVelocitiesDevice(self, d_hits: int, n: int, d_out: int = 0, d_radial: int = 0, d_col_pose: int = 0, n_cols: int = 0, motions=(),
+                            d_sensor_twist: int = 0, twists=(), flags: int = 0, d_count: int = 0, stream=None) -> int:
+        """ls_hit_velocities on device pointers: hitAttributesMovingDevice's records and tables, d_sensor_twist 0 (the sensor at rest)
+        or the device address of H 24-byte twist records, `twists` a dict geomID -> such an address; 32-byte records to d_out and
+        floats to d_radial, either may be 0; enqueued on `stream` (a hipStream_t as an int, None: the handle's), no wait.  -> 0, or
+        -1 on an empty / uncommitted scene (nothing written)."""
+        arr, n_motions = self._device_motions(motions)
+        tws, n_twists = self._device_twists(twists)
+        rc = self.L.ls_hit_velocities(self.h, stream, d_col_pose or None, n_cols, arr, n_motions, d_sensor_twist or None, tws, n_twists, flags,
+                                      d_hits or None, d_count or None, n, d_out or None, d_radial or None)
+        return -1 if rc == -1 else int(self._check(rc, "ls_hit_velocities"))
+
     def traceBeamsHost(self, model: BeamModel, points: bool = True, hits: bool = True, echo: bool = True):
         """A frame of diverging beams with multi-echo returns (ls_trace_scene_beams_host): model.n_samples sub-rays per ray of the
         shard, the returns of every beam in ascending ray index and range.  An output asked for with False comes back None.
@@ -1164,6 +1221,33 @@ def motion_normal(n3, motion12):
     if rc != 0:
         raise LidarShooterHipError(f"ls_debug_motion_normal: status {rc}")
     return out
+
+
+def twist_table_constant(lin_vel, ang_vel, pivot, t0: float, dt: float, n_cols: int):
+    """ls_twist_table_constant: the twist table of the body whose motion table motion_constant_twist writes for the same arguments
+    -> float32 (n_cols, 6), [w | u], tau_h = t0 + h dt"""
+    L = load()
+    lin, ang, piv = (np.ascontiguousarray(x, np.float32).reshape(3) for x in (lin_vel, ang_vel, pivot))
+    out = np.zeros((int(n_cols), 6), np.float32)
+    rc = L.ls_twist_table_constant(_f32p(lin), _f32p(ang), _f32p(piv), float(t0), float(dt), int(n_cols), _f32p(out))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_twist_table_constant: status {rc}")
+    return out
+
+
+def hit_velocity(cast8, t, sensor_twist6=None, geom_twist6=None):
+    """ls_debug_hit_velocity: one valid record of ls_hit_velocities on the host, for a hit at t along the cast ray record cast8 with
+    the column's twist records of the sensor and of the geometry (None: at rest) -> uint32[8]: the bits of v_s xyz, radial, v_o xyz,
+    and flags = 1"""
+    L = load()
+    c = np.ascontiguousarray(cast8, np.float32).reshape(8)
+    st, gt = (None if x is None else np.ascontiguousarray(x, np.float32).reshape(6) for x in (sensor_twist6, geom_twist6))
+    out = np.zeros(8, np.float32)
+    rc = L.ls_debug_hit_velocity(_f32p(c), C.c_float(float(np.float32(t))), None if st is None else _f32p(st), None if gt is None else _f32p(gt),
+                                 _f32p(out))
+    if rc != 0:
+        raise LidarShooterHipError(f"ls_debug_hit_velocity: status {rc}")
+    return out.view(np.uint32)
 
 
 def beam_pattern_rings(half_angle_az: float, half_angle_el: float, n_rings: int, per_ring: int):

@@ -7,6 +7,7 @@
 #include "ls_return_model.h"
 #include "ls_sweep.h"
 #include "ls_motion.h"
+#include "ls_velocity.h"
 #include "ls_beam.h"
 #include "ls_cloud_format.h"
 
@@ -196,6 +197,18 @@ int ls_debug_motion_normal(const float n3[3], const float motion12[12], float ou
 {
     if (!n3 || !motion12 || !out3) return LS_ERR_INVALID_ARGUMENT;
     ls::motion_normal(motion12, n3, out3);
+    return LS_OK;
+}
+
+// hit_velocity: what a lane of k_hit_velocities does for a valid record
+int ls_debug_hit_velocity(const float cast8[8], float t, const float sensor_twist6[6], const float geom_twist6[6], float out8[8])
+{
+    if (!cast8 || !out8) return LS_ERR_INVALID_ARGUMENT;
+    float res[7];
+    ls::hit_velocity(cast8, t, sensor_twist6 != nullptr, sensor_twist6, geom_twist6 != nullptr, geom_twist6, res);
+    const uint32_t valid = 1u;
+    std::memcpy(out8, res, sizeof(res));
+    std::memcpy(out8 + 7, &valid, 4);
     return LS_OK;
 }
 

@@ -2,7 +2,8 @@
 // ls_attr.hip) and ls_apply_return_model (sensor returns from them: the same gather, a model on top of it and an ordered compaction,
 // ls_returns.hip), each with its host-memory variant; and the two again for the records of ls_trace_scene_sweep_moving, whose
 // geometries each saw a ray of their own (ls_hit_attributes_moving, ls_apply_return_model_moving: ls_attr_moving.hip, with a
-// motion-table pointer per geomID next to the gather's table).  Their place among what the handle issues is that of the queries on the
+// motion-table pointer per geomID next to the gather's table); and ls_hit_velocities, the velocities at those records
+// (ls_velocity.hip, with a twist-table pointer per geomID as a third array).  Their place among what the handle issues is that of the queries on the
 // hierarchies (query_enter / query_leave, ls_query.cpp); LS_INFO_RAY_QUERY_BUILT is left as it is.
 //
 // A static call and its _moving pair share their check, their issue function and their host-memory variant: `mv` is nullptr for the
@@ -182,6 +183,122 @@ int returns_host(ls_tracer *tr, const char *overflow, const ls_return_model *mod
     return io.fetch_counted(tr, p_n, n, overflow, n_out);
 }
 
+// ---- ls_hit_velocities ----------------------------------------------------------------------------------------------------------
+
+// the sensor's twist table and the twists of the geometries as the caller gave them (host or device addresses; no table: at rest),
+// resolved and staged the way Moving resolves and stages motions: the kernel takes the tables per geomID
+struct Twists {
+    const float *sensor;
+    const ls_geometry_twist *twists;
+    uint32_t n_twists;
+    struct Entry { uint32_t geom; const float *table; int piece; };
+    std::vector<Entry> e;
+    int sensor_piece = -1;
+
+    // what every call refuses of them, in this order (nothing of it needs a commit or the device)
+    int args_check(ls_tracer *tr) const
+    {
+        if (n_twists && !twists) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null twists with n_twists > 0");
+        for (uint32_t k = 0; k < n_twists; ++k)
+            if (!twists[k].col_twist) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a twist without a table");
+        for (uint32_t k = 0; k < n_twists; ++k)
+            if (twists[k].reserved) return fail(tr, LS_ERR_INVALID_ARGUMENT, "ls_geometry_twist.reserved must be 0");
+        if (n_twists > tr->geoms.size()) return fail(tr, LS_ERR_INVALID_ARGUMENT, "more twists than geometries");
+        std::vector<uint32_t> ids(n_twists);
+        for (uint32_t k = 0; k < n_twists; ++k) ids[k] = twists[k].geom;
+        std::sort(ids.begin(), ids.end());
+        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a geometry named by two twists");
+        return LS_OK;
+    }
+    bool misaligned4() const
+    {
+        bool bad = misaligned(sensor, 4);
+        for (uint32_t k = 0; k < n_twists; ++k) bad = bad || misaligned(twists[k].col_twist, 4);
+        return bad;
+    }
+    // the last refusal, after the motions': LS_ERR_UNKNOWN_GEOMETRY for a twist of a geometry that is not in the committed scene
+    int resolve(ls_tracer *tr)
+    {
+        const std::vector<int> &ids = tr->slot_geom_ids;
+        for (uint32_t k = 0; k < n_twists; ++k) {
+            const size_t slot = (size_t)(std::find(ids.begin(), ids.end(), (int)twists[k].geom) - ids.begin());
+            if (slot >= tr->layout.size()) return fail(tr, LS_ERR_UNKNOWN_GEOMETRY, "a twist names a geometry that is not in the committed scene");
+            e.push_back({twists[k].geom, twists[k].col_twist, -1});
+        }
+        return LS_OK;
+    }
+    std::vector<const float *> per_geom(size_t n) const   // (a geomID beyond n is left out: the kernel checks against one bound)
+    {
+        std::vector<const float *> t(n, nullptr);
+        for (const Entry &x : e)
+            if (x.geom < n) t[x.geom] = x.table;
+        return t;
+    }
+    // the sensor's table (H records of 24 bytes, or none) and the named geometries'
+    void stage(const ls_tracer *tr, Staging &st)
+    {
+        sensor_piece = st.in(sensor, (size_t)tr->H * 24);
+        for (Entry &x : e) x.piece = st.in(x.table, (size_t)tr->H * 24);
+    }
+    void use_staged(const Staged &io)
+    {
+        sensor = io.dev<const float>(sensor_piece);
+        for (Entry &x : e) x.table = io.dev<const float>(x.piece);
+    }
+};
+
+// what the device entry point and the host-memory variant (any alignment) refuse, in this order
+int vel_check(ls_tracer *tr, Moving &mv, uint32_t flags, Twists &tw, const void *hits, const uint32_t *count, uint32_t n, const void *out,
+              const float *radial, bool host)
+{
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open");
+    if (n && (!hits || (!out && !radial))) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null hit records, or neither output");
+    // the pose table, then the flags -- this call has none, LS_SWEEP_DESKEW included --, then the motions
+    if (const int rc = pose_flags_check(tr, mv.col_pose, mv.n_cols, 0)) return rc;
+    if (flags) return fail(tr, LS_ERR_INVALID_ARGUMENT, "unknown flags: ls_hit_velocities takes none");
+    if (const int rc = moving_args_check(tr, mv)) return rc;
+    if (const int rc = tw.args_check(tr)) return rc;
+    if (!host && (moving_misaligned({hits, out}, {count, radial}, mv) || tw.misaligned4()))
+        return fail(tr, LS_ERR_INVALID_ARGUMENT,
+                    "hit records and velocity records must be 16-byte aligned, the count, the radial array, the poses, the motion tables and the "
+                    "twist tables 4-byte aligned");
+    if (n > kMaxQueryRecords) return fail(tr, LS_ERR_OUT_OF_RANGE, "too many hit records in one call");
+    if (const int rc = uncommitted(tr)) return rc;   // (before n = 0: the same answer whatever n)
+    if (const int rc = moving_resolve(tr, mv)) return rc;
+    return tw.resolve(tr);
+}
+
+int vel_issue(ls_tracer *tr, hipStream_t s, const Moving &mv, const Twists &tw, const void *d_hits, const uint32_t *d_count, uint32_t n, void *d_out,
+              float *d_radial)
+{
+    ls_tracer::HitAttr &a = tr->ha;
+    if (const int rc = tables_prepare(tr, s, &mv)) return rc;
+    std::vector<const float *> by_id = tw.per_geom(a.table.current.size());
+    if (const int rc = a.twist.upload_if_changed(tr, s, by_id)) return rc;
+    ls::launch_hit_velocities(s, d_hits, d_count, n, tables(tr), a.table.dev.p, a.motion.dev.p, a.twist.dev.p, (uint32_t)a.table.current.size(),
+                              mv.col_pose, tw.sensor, d_out, d_radial);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+// records, tables and results staged in q.io, on the handle's stream; returns when the outputs are filled
+int vel_host(ls_tracer *tr, Moving &mv, Twists &tw, const void *hits, uint32_t n, void *out, float *radial)
+{
+    const hipStream_t s = tr->stream;
+    int rc;
+    if ((rc = query_enter(tr, s))) return rc;
+    Staging st;
+    const int p_hits = st.in(hits, (size_t)n * 16), p_out = st.out(out, n, 32), p_radial = st.out(radial, n, 4);
+    mv.stage(tr, st);
+    tw.stage(tr, st);
+    Staged io;
+    if ((rc = st.commit(tr, s, io))) return rc;
+    mv.use_staged(io);
+    tw.use_staged(io);
+    if ((rc = vel_issue(tr, s, mv, tw, io.dev(p_hits), nullptr, n, io.dev(p_out), io.dev<float>(p_radial)))) return rc;
+    return io.fetch(tr);
+}
+
 }  // namespace
 
 void hit_attr_release(ls_tracer *tr)
@@ -189,6 +306,7 @@ void hit_attr_release(ls_tracer *tr)
     ls_tracer::HitAttr &a = tr->ha;
     a.table.release();
     a.motion.release();
+    a.twist.release();
     release(a.park); release(a.block_counts);
 }
 
@@ -281,6 +399,29 @@ int ls_apply_return_model_moving_host(ls_tracer *tr, const ls_return_model *mode
     LS_ENTER_CHECKED(tr, returns_check(tr, model, nullptr, 0, &mv, hits, nullptr, n, reflectivity, n_reflectivity, points32, hits_out, n_out, true));
     return returns_host(tr, "ls_apply_return_model_moving: more returns than records", model, frame_index, nullptr, 0, &mv, hits, n, reflectivity,
                         n_reflectivity, points32, hits_out, n_out);
+}
+
+int ls_hit_velocities(ls_tracer *tr, void *hip_stream, const float *d_col_pose, uint32_t n_cols, const ls_geometry_motion *motions, uint32_t n_motions,
+                      const float *d_sensor_twist, const ls_geometry_twist *twists, uint32_t n_twists, uint32_t flags, const void *d_hits,
+                      const uint32_t *d_count, uint32_t n, void *d_out, float *d_radial)
+{
+    Moving mv = {d_col_pose, n_cols, motions, n_motions, 0u};
+    Twists tw = {d_sensor_twist, twists, n_twists};
+    LS_ENTER_CHECKED(tr, vel_check(tr, mv, flags, tw, d_hits, d_count, n, d_out, d_radial, false));
+    if (!n) return LS_OK;
+    const hipStream_t s = stream_of(tr, hip_stream);
+    return query_run(tr, s, [&] { return vel_issue(tr, s, mv, tw, d_hits, d_count, n, d_out, d_radial); });
+}
+
+int ls_hit_velocities_host(ls_tracer *tr, const float *col_pose, uint32_t n_cols, const ls_geometry_motion *motions, uint32_t n_motions,
+                           const float *sensor_twist, const ls_geometry_twist *twists, uint32_t n_twists, uint32_t flags, const void *hits, uint32_t n,
+                           void *out, float *radial)
+{
+    Moving mv = {col_pose, n_cols, motions, n_motions, 0u};
+    Twists tw = {sensor_twist, twists, n_twists};
+    LS_ENTER_CHECKED(tr, vel_check(tr, mv, flags, tw, hits, nullptr, n, out, radial, true));
+    if (!n) return LS_OK;
+    return vel_host(tr, mv, tw, hits, n, out, radial);
 }
 
 }  // extern "C"

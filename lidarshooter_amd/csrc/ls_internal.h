@@ -330,6 +330,8 @@ struct ls_tracer {
         // ls_hit_attributes_moving / ls_apply_return_model_moving: a motion-table pointer per geomID next to `table` (nullptr: at
         // rest), as long as it is
         lsi::StagedTable<const float *> motion;
+        // ls_hit_velocities: a twist-table pointer per geomID next to them (nullptr: at rest), as long as they are
+        lsi::StagedTable<const float *> twist;
     } ha;
     uint64_t upload_seq = 0;
 

@@ -329,6 +329,13 @@ void launch_returns_eval_moving(hipStream_t s, const void *hits, const uint32_t 
                                 uint32_t frame_index, const float *refl, uint32_t n_refl, void *park, uint32_t *block_counts);
 void launch_returns_pack(hipStream_t s, const void *park, const uint32_t *block_counts, const uint32_t *d_count, uint32_t n, uint32_t ring_div,
                          void *points32, void *hits_out, uint32_t *n_out);
+// ls_hit_velocities (ls_velocity.hip): one more gather over the same records with the same tables -- pose and motion as above --
+// and a third per-geomID array, `twist`: that geometry's twist table (H records of 6 floats [w | u], 4-byte aligned), nullptr: at
+// rest; sensor_twist: the sensor's (nullptr: at rest).  out: 32-byte records (v_s xyz, radial, v_o xyz, flags), radial: n floats --
+// either may be nullptr.
+void launch_hit_velocities(hipStream_t s, const void *hits, const uint32_t *d_count, uint32_t n, const SensorTables &tb, const AttrGeom *table,
+                           const float *const *motion, const float *const *twist, uint32_t n_table, const float *pose, const float *sensor_twist,
+                           void *out, float *radial);
 // ls_trace_scene_sweep (ls_sweep.hip): the shard's rays through the per-column pose table (H records of 12 floats, [R | o] row-major,
 // indexed by the global column) as 32-byte records -- shard-local order in `rays` (what launch_trace_rays reads), and at their
 // global index in rays_out (nullable); then, over the walk's dense ls_hit records of those rays, the ordered pack: 32-byte

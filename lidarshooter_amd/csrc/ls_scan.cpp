@@ -8,7 +8,7 @@
 //                         the weighted echoes and their pack (ls_beam.hip); ls_beam_weights_gaussian: a weight per sample;
 //   ls_trace_scene_sweep_moving  the sweep with geometries that move during the turn: the sweep's rays and pack around the walk that
 //                         carries each ray through the inverse of a geometry's motion (ls_moving.hip); ls_motion_constant_twist: a
-//                         motion table.
+//                         motion table; ls_twist_table_constant: that body's twist table (ls_hit_velocities, ls_gather.cpp).
 #include "ls_internal.h"
 #include "ls_beam.h"
 
@@ -415,6 +415,28 @@ int ls_motion_constant_twist(const float lin_vel[3], const float ang_vel[3], con
     if (!lin_vel || !ang_vel || !pivot || (n_cols && !col_motion)) return LS_ERR_INVALID_ARGUMENT;
     if (!twist_finite(lin_vel, ang_vel, pivot, t0, dt)) return LS_ERR_INVALID_ARGUMENT;
     twist_table(lin_vel, ang_vel, pivot, t0, dt, n_cols, col_motion);
+    return LS_OK;
+}
+
+// host only: the twist of the body whose displacement table ls_motion_constant_twist writes for the same arguments -- w_h = ang_vel,
+// u_h = lin_vel - ang_vel x (pivot + lin_vel tau_h); double throughout, one rounding; a cross product that is zero leaves lin_vel's bits
+int ls_twist_table_constant(const float lin_vel[3], const float ang_vel[3], const float pivot[3], double t0, double dt, uint32_t n_cols,
+                            float *col_twist)
+{
+    if (!lin_vel || !ang_vel || !pivot || (n_cols && !col_twist)) return LS_ERR_INVALID_ARGUMENT;
+    if (!twist_finite(lin_vel, ang_vel, pivot, t0, dt)) return LS_ERR_INVALID_ARGUMENT;
+    const double w[3] = {ang_vel[0], ang_vel[1], ang_vel[2]};
+    for (uint32_t h = 0; h < n_cols; ++h) {
+        const double tau = t0 + (double)h * dt;
+        double a[3];
+        for (int i = 0; i < 3; ++i) a[i] = (double)pivot[i] + (double)lin_vel[i] * tau;
+        const double cross[3] = {w[1] * a[2] - w[2] * a[1], w[2] * a[0] - w[0] * a[2], w[0] * a[1] - w[1] * a[0]};
+        float *p = col_twist + 6 * (size_t)h;
+        for (int i = 0; i < 3; ++i) {
+            p[i] = ang_vel[i];
+            p[3 + i] = cross[i] != 0.0 ? (float)((double)lin_vel[i] - cross[i]) : lin_vel[i];
+        }
+    }
     return LS_OK;
 }
 
