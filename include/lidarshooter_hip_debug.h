@@ -132,6 +132,15 @@ int ls_debug_hit_velocity(const float cast8[8], float t, const float sensor_twis
 int ls_debug_format_record(const ls_cloud_format *fmt, const void *point32, const ls_hit *hit, uint32_t echo_word,
                            float col_time_value, float chan_time_value, uint32_t V, uint32_t H, uint32_t cell_ray, void *out_bytes);
 
+/* k_project's start of a footprint's channel band by guess and verify (csrc/ls_band_map.h), on the host (no device, no handle).
+ * ls_debug_band_map_fit: the map the library fits to an ascending table tan_up[V] -> map8 = a0 a1 a2 a3 t0 t1 (floats), then back
+ * and walk (int32 words); walk < 0: the handle would keep the bisection.  ls_debug_band_guess: the kernel's start position
+ * (0 .. V) for the query t under such a map, the float32 operation sequence the kernel runs.  ls_debug_tracer_band_map: the
+ * map a handle's frames use, same layout. */
+int ls_debug_band_map_fit(const float *tan_up, uint32_t V, float map8[8]);
+int ls_debug_band_guess(const float map8[8], uint32_t V, float t, uint32_t *start);
+int ls_debug_tracer_band_map(const ls_tracer *tr, float map8[8]);
+
 #ifdef __cplusplus
 }
 #endif

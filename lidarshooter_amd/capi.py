@@ -68,7 +68,8 @@ DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_s
                  "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model", "ls_debug_sweep_ray",
                  "ls_debug_beam_ray", "ls_debug_beam_echoes", "ls_debug_beam_model_check",
                  "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check", "ls_debug_motion_ray",
-                 "ls_debug_motion_normal", "ls_debug_hit_velocity", "ls_debug_format_record")
+                 "ls_debug_motion_normal", "ls_debug_hit_velocity", "ls_debug_format_record",
+                 "ls_debug_band_map_fit", "ls_debug_band_guess", "ls_debug_tracer_band_map")
 
 
 class SensorDesc(C.Structure):
@@ -342,6 +343,9 @@ def load() -> C.CDLL:
     L.ls_cloud_format_check.argtypes = [C.POINTER(CloudFormat)]
     L.ls_cloud_format_from_point_fields.argtypes = [C.POINTER(C.c_char_p), u32p, C.POINTER(C.c_uint8), u32p, u32, u32, C.POINTER(CloudFormat)]
     L.ls_column_times.argtypes = [C.c_double, C.c_double, u32, f32p]
+    L.ls_debug_band_map_fit.argtypes = [f32p, u32, f32p]
+    L.ls_debug_band_guess.argtypes = [f32p, u32, C.c_float, u32p]
+    L.ls_debug_tracer_band_map.argtypes = [vp, f32p]
     L.ls_debug_format_record.argtypes = [C.POINTER(CloudFormat), vp, vp, u32, C.c_float, C.c_float, u32, u32, u32, vp]
     L.ls_geometry_type.argtypes = [vp, C.c_char_p]
     L.ls_debug_dense_hits.argtypes = [vp, f32p, u32p]

@@ -326,6 +326,34 @@ int ls_debug_format_record(const ls_cloud_format *fmt, const void *point32, cons
     return LS_OK;
 }
 
+static_assert(sizeof(ls::BandMap) == 32, "map8 is the BandMap, word for word");
+
+int ls_debug_band_map_fit(const float *tan_up, uint32_t V, float map8[8])
+{
+    if (!tan_up || !V || !map8) return LS_ERR_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < V; ++i)
+        if (std::isnan(tan_up[i]) || (i && tan_up[i] < tan_up[i - 1])) return LS_ERR_INVALID_ARGUMENT;
+    const ls::BandMap bm = ls::band_map_fit(tan_up, V);
+    std::memcpy(map8, &bm, sizeof(bm));
+    return LS_OK;
+}
+
+int ls_debug_band_guess(const float map8[8], uint32_t V, float t, uint32_t *start)
+{
+    if (!map8 || !start) return LS_ERR_INVALID_ARGUMENT;
+    ls::BandMap bm;
+    std::memcpy(&bm, map8, sizeof(bm));
+    *start = ls::band_guess(bm, V, t);
+    return LS_OK;
+}
+
+int ls_debug_tracer_band_map(const ls_tracer *tr, float map8[8])
+{
+    if (!tr || !map8) return LS_ERR_INVALID_ARGUMENT;
+    std::memcpy(map8, &tr->band, sizeof(tr->band));
+    return LS_OK;
+}
+
 }  // extern "C"
 
 int ls_debug_expand_hits(void *dst_points32, const void *hits8, uint32_t n, const float *sin_theta, const float *cos_theta,

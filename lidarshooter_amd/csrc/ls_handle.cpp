@@ -50,6 +50,10 @@ void fill_tables(ls_tracer *tr, std::vector<float> &tab)
         dn[i] = std::nextafter(td, -INFINITY);
         std::memcpy(&dn[V + i], &perm[i], 4);
     }
+    // k_project's start of the channel band: position as a cubic in the tangent, judged against this very table
+    static const int band_map = tune_int("LS_PROJECT_BAND_MAP", 1);
+    tr->band = ls::band_map_fit(up, V);
+    if (!band_map) tr->band.walk = -1;
     // (cos_phi, sin_phi) interleaved
     float *cs = tab.data() + 2 * (size_t)V + 2 * (size_t)H + 3 * (size_t)V;
     for (uint32_t h = 0; h < H; ++h) {

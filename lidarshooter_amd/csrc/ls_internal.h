@@ -127,6 +127,7 @@ struct ls_tracer {
     std::vector<float> host_tables;   // the same words on the host (ls_trace_scene_expand rebuilds points from (ray, t) records)
     float lut_t0 = 0.0f, lut_scale = 0.0f;   // k_cull's channel look-up table (ProjectParams::chan_lut)
     bool lut_ok = false;
+    ls::BandMap band = {{0.0f, 0.0f, 0.0f, 0.0f}, 0.0f, 0.0f, 0, -1};   // k_project's channel band by guess and verify (ls_band_map.h; fill_tables)
     uint32_t az0 = 0, naz = 0;
 
     // geometry registry

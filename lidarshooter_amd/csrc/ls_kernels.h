@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ls_band_map.h"
+
 struct ls_return_model;   // include/lidarshooter_hip.h
 struct ls_cloud_format;
 
@@ -107,6 +109,7 @@ struct ProjectParams {
     const uint16_t *chan_lut;
     float lut_t0, lut_scale;
     int lut_ok;
+    BandMap band;                  // k_project's start of the channel band by guess and verify (ls_band_map.h); walk < 0: bisection
     float begin_deg, step_deg;     // azimuth of column h = begin + step*h (LidarDevice.cpp:306)
     float inv_step_deg, inv_period; // 1/step and |step|/360 (0 when step is 0)
     float margin_deg;              // angular slack of the footprint bounds

@@ -91,7 +91,22 @@ __device__ __forceinline__ void band_from_ranges(const ProjectParams &pp, const 
     }
     // channels whose elevation (widened by the angular margin) meets the band: chan_tan_up[i] =
     // tan(chi_i + margin), chan_tan_dn[i] = tan(chi_i - margin), both ascending
+    // The first of them, lo = first position with tan_up >= tan_lo, by guess and verify (ls_band_map.h): a start from the handle's
+    // fitted map, CHECKED here -- the entry below it must be below tan_lo -- and a short forward walk; a start that fails the
+    // check (or a handle without a map: walk < 0, uniform) is bisected.  Either way lo is the exact lower bound: a superset is
+    // kept for any table and whatever the map's arithmetic rounds to.  (A NaN tan_lo fails every comparison: lo = 0 both ways.)
     uint32_t lo = 0, hi = pp.tb.V;
+    if (pp.band.walk >= 0) {
+        uint32_t s = band_guess(pp.band, pp.tb.V, tan_lo);   // 0 .. V
+        const float below = ct.tan_up[s ? s - 1u : 0u];
+        float cur = ct.tan_up[min(s, pp.tb.V - 1u)];          // goes out with `below`: one LDS round trip
+        if (s == 0u || below < tan_lo) {
+            while (s < pp.tb.V && cur < tan_lo) { ++s; cur = ct.tan_up[min(s, pp.tb.V - 1u)]; }
+            lo = hi = s;
+        } else {
+            hi = s - 1u;   // tan_up[s - 1] >= tan_lo: the bound is at or below s - 1
+        }
+    }
     while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (ct.tan_up[m] < tan_lo) lo = m + 1; else hi = m; }
     const uint32_t i0 = lo;
     uint32_t i1 = i0;  // bands are narrow: walk forward instead of a second search

@@ -64,6 +64,7 @@ ls::ProjectParams project_params(const ls_tracer *tr)
     pp.lut_t0 = tr->lut_t0;
     pp.lut_scale = tr->lut_scale;
     pp.lut_ok = tr->lut_ok ? 1 : 0;
+    pp.band = tr->band;
     pp.begin_deg = tr->h_begin;
     pp.step_deg = tr->h_step;  // LidarDevice.cpp:611
     pp.inv_step_deg = pp.step_deg != 0.0f ? 1.0f / pp.step_deg : 0.0f;
