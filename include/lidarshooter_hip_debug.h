@@ -141,6 +141,37 @@ int ls_debug_band_map_fit(const float *tan_up, uint32_t V, float map8[8]);
 int ls_debug_band_guess(const float map8[8], uint32_t V, float t, uint32_t *start);
 int ls_debug_tracer_band_map(const ls_tracer *tr, float map8[8]);
 
+/* ---- group culling of the projection engine (k_group_bounds, k_cull: csrc/ls_project.hip) ----------------------------
+ * ls_debug_force_group_cull: while on, LS_OPT_BLOCK_CULL = 1 applies to a geometry of ANY size from one triangle (as shipped
+ * it applies to meshes large enough for waves of 64 triangles: 524 225 or more); the culling data is made by the next commit.
+ * Off (the default): nothing changes. */
+int ls_debug_force_group_cull(ls_tracer *tr, int on);
+/* The culling data of committed geometry geom_id: *n_tris; perm[n_tris]: sorted position -> the caller's triangle;
+ * group_boxes: 8 floats per group of 4 sorted triangles (the last group may be partial) = (cx, cy, cz, hx), (hy, hz, sx, sy):
+ * the mesh-space box { c + a e1 + b e2 + g e3 : |a|, |b|, |g| <= 1 }, e1 = (hx, 0, sx hx), e2 = (0, hy, sy hy), e3 = (0, 0, hz);
+ * hx = +inf: unbounded (never rejected); block_boxes: the same per 64 groups.  NULL pointers are skipped.
+ * LS_ERR_NOT_COMMITTED when the geometry has no current culling data. */
+int ls_debug_download_cull(ls_tracer *tr, uint32_t geom_id, uint32_t *n_tris, uint32_t *perm, float *group_boxes, float *block_boxes);
+/* The groups of geometry geom_id that the NEXT frame's cull pass keeps: the pass is run as launch_project would run it --
+ * committed scene, current poses and shard, the same batch of geometries, the same k_cull instantiation -- into scratch of this
+ * call (the frames' counters, survivor lists, statistics and hint word are not touched), synchronously.  out[0 .. *n): group
+ * numbers ascending (LS_ERR_OUT_OF_RANGE when *n > cap; *n is set); *variant: LS_DEBUG_CULL_* bits of the instantiation, or
+ * LS_DEBUG_CULL_UNCULLED alone when the frame projects every triangle of the geometry (no culling data, or more culled
+ * geometries than one launch takes: 17): then every group is reported. */
+#define LS_DEBUG_CULL_LUT 1u        /* channel query by look-up table (else binary search) */
+#define LS_DEBUG_CULL_LDS 2u        /* channel tables staged in LDS (else read from global memory: V > 2048) */
+#define LS_DEBUG_CULL_SECTOR 4u     /* azimuth-sector test of a shard narrower than half a turn */
+#define LS_DEBUG_CULL_COUNT 8u      /* LS_OPT_COUNT_VISITS: the counting instantiation */
+#define LS_DEBUG_CULL_UNCULLED 16u
+int ls_debug_cull_survivors(ls_tracer *tr, uint32_t geom_id, uint32_t *out, uint32_t cap, uint32_t *n, uint32_t *variant);
+/* The channel tables k_cull queries, V entries each in ascending elevation: tan_up, tan_dn, the channel of each position, and
+ * whether the look-up table passed the host's check (NULL pointers are skipped). */
+int ls_debug_cull_tables(ls_tracer *tr, float *tan_up, float *tan_dn, uint32_t *chan_perm, int *lut_ok);
+/* k_cull's channel query on the device -- is there a channel i with tan_up[i] >= tan_lo and tan_dn[i] <= tan_hi -- for n
+ * (tan_lo, tan_hi) pairs against the handle's tables, staged as k_cull stages them: lut_search[2 i] = the look-up table's
+ * answer (0 / 1; 2 when this handle's k_cull does not use the table), lut_search[2 i + 1] = the binary search's. */
+int ls_debug_chan_query(ls_tracer *tr, const float *tan_lo_hi, uint32_t n, uint8_t *lut_search);
+
 #ifdef __cplusplus
 }
 #endif

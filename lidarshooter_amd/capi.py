@@ -69,7 +69,10 @@ DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_s
                  "ls_debug_beam_ray", "ls_debug_beam_echoes", "ls_debug_beam_model_check",
                  "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check", "ls_debug_motion_ray",
                  "ls_debug_motion_normal", "ls_debug_hit_velocity", "ls_debug_format_record",
-                 "ls_debug_band_map_fit", "ls_debug_band_guess", "ls_debug_tracer_band_map")
+                 "ls_debug_band_map_fit", "ls_debug_band_guess", "ls_debug_tracer_band_map",
+                 "ls_debug_force_group_cull", "ls_debug_download_cull", "ls_debug_cull_survivors", "ls_debug_cull_tables", "ls_debug_chan_query")
+# ls_debug_cull_survivors: which k_cull instantiation ran
+LS_DEBUG_CULL_LUT, LS_DEBUG_CULL_LDS, LS_DEBUG_CULL_SECTOR, LS_DEBUG_CULL_COUNT, LS_DEBUG_CULL_UNCULLED = 1, 2, 4, 8, 16
 
 
 class SensorDesc(C.Structure):
@@ -346,6 +349,11 @@ def load() -> C.CDLL:
     L.ls_debug_band_map_fit.argtypes = [f32p, u32, f32p]
     L.ls_debug_band_guess.argtypes = [f32p, u32, C.c_float, u32p]
     L.ls_debug_tracer_band_map.argtypes = [vp, f32p]
+    L.ls_debug_force_group_cull.argtypes = [vp, i32]
+    L.ls_debug_download_cull.argtypes = [vp, u32, u32p, vp, vp, vp]
+    L.ls_debug_cull_survivors.argtypes = [vp, u32, vp, u32, u32p, u32p]
+    L.ls_debug_cull_tables.argtypes = [vp, vp, vp, vp, C.POINTER(i32)]
+    L.ls_debug_chan_query.argtypes = [vp, vp, u32, vp]
     L.ls_debug_format_record.argtypes = [C.POINTER(CloudFormat), vp, vp, u32, C.c_float, C.c_float, u32, u32, u32, vp]
     L.ls_geometry_type.argtypes = [vp, C.c_char_p]
     L.ls_debug_dense_hits.argtypes = [vp, f32p, u32p]
@@ -1117,6 +1125,43 @@ class Tracer:
         self._check(self.L.ls_debug_download_hierarchy(self.h, gid, None, None, nodes.ctypes.data, twins.ctypes.data if wide else None,
                                                        rec.ctypes.data), "ls_debug_download_hierarchy")
         return nodes, twins, rec, g.value
+
+    def forceGroupCull(self, on: bool = True):
+        """ls_debug_force_group_cull: LS_OPT_BLOCK_CULL = 1 then applies to geometries of any size (from the next commit)"""
+        self._check(self.L.ls_debug_force_group_cull(self.h, 1 if on else 0), "ls_debug_force_group_cull")
+
+    def downloadCull(self, name: str):
+        """ls_debug_download_cull: -> (perm uint32[n_tris]: sorted position -> caller's triangle, group boxes float32[n_groups, 8],
+        block boxes float32[n_blocks, 8]; a box = cx cy cz hx hy hz sx sy)"""
+        gid, nt = self.getGeometryId(name), C.c_uint32()
+        self._check(self.L.ls_debug_download_cull(self.h, gid, C.byref(nt), None, None, None), "ls_debug_download_cull")
+        groups = (nt.value + 3) // 4
+        perm, gb, bb = np.zeros(nt.value, np.uint32), np.zeros((groups, 8), np.float32), np.zeros(((groups + 63) // 64, 8), np.float32)
+        self._check(self.L.ls_debug_download_cull(self.h, gid, None, perm.ctypes.data, gb.ctypes.data, bb.ctypes.data), "ls_debug_download_cull")
+        return perm, gb, bb
+
+    def cullSurvivors(self, name: str):
+        """ls_debug_cull_survivors: the groups of geometry `name` the next frame's cull pass keeps -> (uint32[n] ascending,
+        LS_DEBUG_CULL_* bits of the k_cull instantiation that ran)"""
+        gid = self.getGeometryId(name)
+        out = np.zeros((self.getElementCount(name) * (2 if self.getGeometryType(name) else 1) + 3) // 4, np.uint32)
+        n, variant = C.c_uint32(), C.c_uint32()
+        self._check(self.L.ls_debug_cull_survivors(self.h, gid, out.ctypes.data, out.shape[0], C.byref(n), C.byref(variant)), "ls_debug_cull_survivors")
+        return out[:n.value].copy(), variant.value
+
+    def cullTables(self):
+        """ls_debug_cull_tables: -> (tan_up float32[V], tan_dn float32[V], channel of each position uint32[V], lut_ok bool)"""
+        up, dn, perm, ok = np.zeros(self.V, np.float32), np.zeros(self.V, np.float32), np.zeros(self.V, np.uint32), C.c_int()
+        self._check(self.L.ls_debug_cull_tables(self.h, up.ctypes.data, dn.ctypes.data, perm.ctypes.data, C.byref(ok)), "ls_debug_cull_tables")
+        return up, dn, perm, bool(ok.value)
+
+    def chanQuery(self, tan_lo, tan_hi):
+        """ls_debug_chan_query: k_cull's channel query on the device -> (look-up table's answers uint8[n], 2 = not in use;
+        binary search's uint8[n])"""
+        q = np.ascontiguousarray(np.stack([np.asarray(tan_lo, np.float32), np.asarray(tan_hi, np.float32)], axis=1))
+        out = np.zeros((q.shape[0], 2), np.uint8)
+        self._check(self.L.ls_debug_chan_query(self.h, q.ctypes.data, q.shape[0], out.ctypes.data), "ls_debug_chan_query")
+        return out[:, 0].copy(), out[:, 1].copy()
 
 
 def closest_on_triangle(p, v0, v1, v2):

@@ -54,10 +54,18 @@ bool cull_enabled(const ls_tracer *tr, const Geometry &g)
     return g.n_tris >= 524288u && shard_sector(tr, lo, hi);
 }
 
+// Group culling takes whole waves of 64 sorted triangles: meshes that the unculled launch would cut into smaller waves stay
+// unculled -- unless a test asked for them with ls_debug_force_group_cull (and LS_OPT_BLOCK_CULL = 1): from one triangle
+bool cull_size_ok(const ls_tracer *tr, uint32_t n_tris)
+{
+    if (tr->debug_force_cull && tr->opt_block_cull == 1) return n_tris > 0u;
+    return ls::project_tris_per_wave(n_tris) == 64u;
+}
+
 // Group-culling data of one geometry, brought up to date (stream-ordered on the handle's stream).
 int prepare_blocks(ls_tracer *tr, Geometry &g)
 {
-    const bool want = cull_enabled(tr, g) && g.has_verts && g.has_idx && ls::project_tris_per_wave(g.n_tris) == 64u;
+    const bool want = cull_enabled(tr, g) && g.has_verts && g.has_idx && cull_size_ok(tr, g.n_tris);
     if (!want) return LS_OK;
     if (!g.order_stale && !g.bounds_stale) return LS_OK;
     // frames in flight on the slot streams read d_idx_sorted / d_perm / d_boxes / d_corners

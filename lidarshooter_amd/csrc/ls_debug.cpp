@@ -12,8 +12,29 @@
 #include "ls_cloud_format.h"
 
 #include <algorithm>
+#include <vector>
 
 using namespace lsi;
+
+namespace {
+// layout entry and registry entry of a committed geometry
+int find_committed(ls_tracer *tr, uint32_t geom_id, size_t *slot, Geometry **ge)
+{
+    if (!tr->committed) return fail(tr, LS_ERR_NOT_COMMITTED, "scene not committed");
+    size_t i = 0;
+    while (i < tr->slot_geom_ids.size() && (uint32_t)tr->slot_geom_ids[i] != geom_id) ++i;
+    if (i >= tr->slot_geom_ids.size() || i >= tr->layout.size()) return fail(tr, LS_ERR_UNKNOWN_GEOMETRY, "no such geometry in the committed scene");
+    *slot = i;
+    return committed_geometry(tr, i, ge);
+}
+
+template <typename T>
+struct Scratch {   // device memory of one call
+    T *p = nullptr;
+    ~Scratch() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(n, 1) * sizeof(T)); }
+};
+}  // namespace
 
 extern "C" {
 
@@ -351,6 +372,129 @@ int ls_debug_tracer_band_map(const ls_tracer *tr, float map8[8])
 {
     if (!tr || !map8) return LS_ERR_INVALID_ARGUMENT;
     std::memcpy(map8, &tr->band, sizeof(tr->band));
+    return LS_OK;
+}
+
+// ---- group culling ---------------------------------------------------------------------------------------------------
+static_assert(LS_DEBUG_CULL_LUT == ls::kCullVariantLut && LS_DEBUG_CULL_LDS == ls::kCullVariantLds && LS_DEBUG_CULL_SECTOR == ls::kCullVariantSector &&
+              LS_DEBUG_CULL_COUNT == ls::kCullVariantCount, "the header's bits are launch_cull's");
+int ls_debug_force_group_cull(ls_tracer *tr, int on)
+{
+    LS_ENTER(tr);
+    const int rc = flush_pipeline(tr);
+    if (rc) return rc;
+    tr->debug_force_cull = on ? 1 : 0;   // (the culling data is made by the next commit: prepare_blocks)
+    return LS_OK;
+}
+
+int ls_debug_download_cull(ls_tracer *tr, uint32_t geom_id, uint32_t *n_tris, uint32_t *perm, float *group_boxes, float *block_boxes)
+{
+    LS_ENTER(tr);
+    size_t slot = 0;
+    Geometry *ge = nullptr;
+    int rc = find_committed(tr, geom_id, &slot, &ge);
+    if (rc) return rc;
+    if (!use_projection(tr) || !cull_enabled(tr, *ge) || !cull_size_ok(tr, ge->n_tris) || !ge->d_perm || !ge->d_boxes || ge->order_stale || ge->bounds_stale)
+        return fail(tr, LS_ERR_NOT_COMMITTED, "this geometry has no current culling data (projection engine, LS_OPT_BLOCK_CULL, commit after the last upload)");
+    if (n_tris) *n_tris = ge->n_tris;
+    if (!perm && !group_boxes && !block_boxes) return LS_OK;
+    if ((rc = flush_pipeline(tr))) return rc;
+    LS_HIP(hipStreamSynchronize(tr->stream));
+    const size_t groups = (ge->n_tris + ls::kCullGroup - 1) / ls::kCullGroup, blocks = ls::project_box_entries(ge->n_tris) - groups;
+    if (perm) LS_HIP(hipMemcpy(perm, ge->d_perm, (size_t)ge->n_tris * 4, hipMemcpyDeviceToHost));
+    if (group_boxes) LS_HIP(hipMemcpy(group_boxes, ge->d_boxes, groups * 32, hipMemcpyDeviceToHost));
+    if (block_boxes) LS_HIP(hipMemcpy(block_boxes, ge->d_boxes + 2 * groups, blocks * 32, hipMemcpyDeviceToHost));
+    return LS_OK;
+}
+
+int ls_debug_cull_survivors(ls_tracer *tr, uint32_t geom_id, uint32_t *out, uint32_t cap, uint32_t *n, uint32_t *variant)
+{
+    LS_ENTER(tr);
+    if (!n || (!out && cap)) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null output");
+    size_t slot = 0;
+    Geometry *ge = nullptr;
+    int rc = find_committed(tr, geom_id, &slot, &ge);
+    if (rc) return rc;
+    if (!use_projection(tr)) return fail(tr, LS_ERR_NOT_COMMITTED, "group culling belongs to the projection engine (LS_OPT_ENGINE = 2)");
+    if (tr->fg_open) return fail(tr, LS_ERR_INVALID_ARGUMENT, "a frame graph is open: its launches are recorded, not run");
+    if ((rc = flush_pipeline(tr))) return rc;
+    std::vector<ls::GeomSource> srcs;
+    bool any_culled = false;
+    if ((rc = project_sources(tr, srcs, any_culled))) return rc;
+    const ls::ProjectParams pp = project_params(tr);
+    const uint32_t groups = (ge->n_tris + ls::kCullGroup - 1) / ls::kCullGroup;
+    ls::CullProbe probe;
+    std::memset(&probe, 0, sizeof(probe));
+    uint32_t at = ls::kGeomsPerLaunch;
+    if (any_culled && shard_rays(tr) && ls::launch_cull_probe(tr->stream, pp, srcs.data(), (uint32_t)srcs.size(), nullptr, nullptr, nullptr, probe))
+        for (uint32_t i = 0; i < probe.n; ++i)
+            if (probe.src_index[i] == (uint32_t)slot) at = i;
+    if (at == (uint32_t)ls::kGeomsPerLaunch) {
+        // the frame projects every triangle of this geometry: no bounds, or more culled geometries than one launch takes
+        *n = groups;
+        if (variant) *variant = LS_DEBUG_CULL_UNCULLED;
+        if (cap < groups) return fail(tr, LS_ERR_OUT_OF_RANGE, "more surviving groups than the output holds");
+        for (uint32_t g = 0; g < groups; ++g) out[g] = g;
+        return LS_OK;
+    }
+    Scratch<uint32_t> list, counts;
+    Scratch<unsigned long long> stats;
+    constexpr size_t kCountWords = (size_t)ls::kCullCounters * 16;
+    LS_HIP(list.alloc(probe.entries));
+    LS_HIP(counts.alloc(kCountWords));
+    LS_HIP(stats.alloc(4));
+    LS_HIP(hipMemsetAsync(counts.p, 0, kCountWords * 4, tr->stream));
+    LS_HIP(hipMemsetAsync(stats.p, 0, 32, tr->stream));
+    // (the frame's own counters, survivor lists, statistics and hint word are not touched: everything lands in this call's scratch)
+    if (!ls::launch_cull_probe(tr->stream, pp, srcs.data(), (uint32_t)srcs.size(), list.p, counts.p, tr->opt_count ? stats.p : nullptr, probe))
+        return fail(tr, LS_ERR_HIP, "the cull pass could not be laid out twice the same way");
+    LS_HIP(hipGetLastError());
+    LS_HIP(hipStreamSynchronize(tr->stream));
+    std::vector<uint32_t> h_counts(kCountWords), found;
+    LS_HIP(hipMemcpy(h_counts.data(), counts.p, kCountWords * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> seg(probe.seg_cap[at]);
+    for (uint32_t s = 0; s < ls::kCullSegs; ++s) {
+        const uint32_t c = h_counts[((size_t)at * ls::kCullSegs + s) * 16];
+        if (c > probe.seg_cap[at]) return fail(tr, LS_ERR_OUT_OF_RANGE, "a survivor segment holds more than its capacity");
+        if (!c) continue;
+        LS_HIP(hipMemcpy(seg.data(), list.p + probe.list_first[at] + (size_t)s * probe.seg_cap[at], (size_t)c * 4, hipMemcpyDeviceToHost));
+        found.insert(found.end(), seg.begin(), seg.begin() + c);
+    }
+    std::sort(found.begin(), found.end());
+    *n = (uint32_t)found.size();
+    if (variant) *variant = probe.variant;
+    if (found.size() > cap) return fail(tr, LS_ERR_OUT_OF_RANGE, "more surviving groups than the output holds");
+    std::copy(found.begin(), found.end(), out);
+    return LS_OK;
+}
+
+int ls_debug_cull_tables(ls_tracer *tr, float *tan_up, float *tan_dn, uint32_t *chan_perm, int *lut_ok)
+{
+    LS_ENTER(tr);
+    const size_t V = tr->V, at = 2 * V + 2 * (size_t)tr->H;
+    if (tr->host_tables.size() < at + 3 * V) return fail(tr, LS_ERR_NOT_COMMITTED, "the handle has no sensor tables");
+    if (tan_up) std::memcpy(tan_up, tr->host_tables.data() + at, V * 4);
+    if (tan_dn) std::memcpy(tan_dn, tr->host_tables.data() + at + V, V * 4);
+    if (chan_perm) std::memcpy(chan_perm, tr->host_tables.data() + at + 2 * V, V * 4);
+    if (lut_ok) *lut_ok = tr->lut_ok ? 1 : 0;
+    return LS_OK;
+}
+
+int ls_debug_chan_query(ls_tracer *tr, const float *tan_lo_hi, uint32_t n, uint8_t *lut_search)
+{
+    LS_ENTER(tr);
+    if (!n) return LS_OK;
+    if (!tan_lo_hi || !lut_search) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null argument");
+    if (!use_projection(tr)) return fail(tr, LS_ERR_NOT_COMMITTED, "group culling belongs to the projection engine (LS_OPT_ENGINE = 2)");
+    Scratch<float> q;
+    Scratch<uint8_t> a;
+    LS_HIP(q.alloc(2 * (size_t)n));
+    LS_HIP(a.alloc(2 * (size_t)n));
+    LS_HIP(hipMemcpy(q.p, tan_lo_hi, (size_t)n * 8, hipMemcpyHostToDevice));
+    ls::launch_chan_query(tr->stream, project_params(tr), q.p, n, a.p);
+    LS_HIP(hipGetLastError());
+    LS_HIP(hipStreamSynchronize(tr->stream));
+    LS_HIP(hipMemcpy(lut_search, a.p, (size_t)n * 2, hipMemcpyDeviceToHost));
     return LS_OK;
 }
 

@@ -251,6 +251,7 @@ struct ls_tracer {
     int opt_upload_mode = 1;     // LS_OPT_UPLOAD_MODE
     int opt_emit_points = 1;     // LS_OPT_EMIT_POINTS
     int opt_debug_fault = 0;     // LS_OPT_DEBUG_FAULT (one frame)
+    int debug_force_cull = 0;    // ls_debug_force_group_cull: LS_OPT_BLOCK_CULL = 1 applies to a geometry of any size (cull_size_ok)
     uint32_t *h_status = nullptr;   // sticky device status word in pinned host memory (bit 0: chained prefix gave up)
     uint32_t cull_hint_in_use = 0;  // the survivor hint the culled grid is sized from (h_status[1] with hysteresis: trace_once)
     // ls_trace_scene_begin / ls_trace_scene_expand: the device tells the host how far the frame is (ls::HostProgress)
@@ -460,6 +461,9 @@ void free_geometry(Geometry &g);
 // ls_commit.cpp
 int materialize_scene(ls_tracer *tr, bool with_maxabs, bool keep_indices = false);
 bool cull_enabled(const ls_tracer *tr, const Geometry &g);
+bool cull_size_ok(const ls_tracer *tr, uint32_t n_tris);   // large enough for 64 triangles per wave (or ls_debug_force_group_cull)
+// the committed geometries as the projection engine's next frame reads them (ls_trace.cpp): culling data attached where it is current
+int project_sources(ls_tracer *tr, std::vector<ls::GeomSource> &srcs, bool &any_culled);
 bool shard_sector(const ls_tracer *tr, double &lo_deg, double &hi_deg);   // ls_trace.cpp
 bool inst_inverse(const ls_tracer *tr, const Geometry &ge, double *minv9, double *o3, double *cond);
 int commit_locked(ls_tracer *tr);

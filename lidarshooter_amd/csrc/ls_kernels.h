@@ -457,6 +457,19 @@ void launch_project(hipStream_t s, const ProjectParams &pp, const GeomSource *sr
                     uint32_t survivors_hint = 0);    // 1 + the fullest survivor segment of a recent frame (0: unknown): sizes the culled grid
 uint32_t project_tris_per_wave(uint32_t ntris);   // 64 for big meshes, fewer for small ones (more waves than ntris / 64)
 uint32_t project_cull_entries(const GeomSource *srcs, uint32_t n_srcs, bool sector);   // survivor-list words for the geometries with bounds (0: none, or too many for one launch)
+// test hooks (include/lidarshooter_hip_debug.h).  launch_cull_probe: the cull pass of launch_project alone -- same batch, same k_cull
+// instantiation -- into a list and counters of the caller (list: out.entries words, found with list = nullptr, which launches
+// nothing; counts: kCullCounters * 16 zeroed words, segment (i, seg)'s at (i * kCullSegs + seg) * 16); false: the frame would not
+// launch k_cull (no geometry with bounds, or more than a launch takes).  launch_chan_query: k_cull's channel query for n
+// (tan_lo, tan_hi) pairs -> two bytes each: the look-up table's answer (2: this sensor's k_cull searches) and the search's
+constexpr uint32_t kCullVariantLut = 1u, kCullVariantLds = 2u, kCullVariantSector = 4u, kCullVariantCount = 8u;
+struct CullProbe {
+    uint32_t n, entries, variant;
+    uint32_t src_index[kGeomsPerLaunch], list_first[kGeomsPerLaunch], seg_cap[kGeomsPerLaunch];
+};
+bool launch_cull_probe(hipStream_t s, const ProjectParams &pp, const GeomSource *srcs, uint32_t n_srcs, uint32_t *list, uint32_t *counts,
+                       unsigned long long *stats, CullProbe &out);
+void launch_chan_query(hipStream_t s, const ProjectParams &pp, const float *d_lo_hi, uint32_t n, uint8_t *d_out);
 // one-off per topology: Morton order of the triangles (centroids in mesh space) -> perm (sorted position -> triangle),
 // idx_sorted; scratch: keys_a/keys_b/vals_a (ntris words each), aabb (6 words), sort temp
 bool launch_mesh_order(hipStream_t s, const uint8_t *verts, uint32_t stride, uint32_t nverts, const uint32_t *idx, uint32_t ntris,

@@ -748,12 +748,13 @@ __global__ __launch_bounds__(kBlock) void k_group_bounds(const uint8_t *__restri
     const uint32_t n = live ? min(kCullGroup, ntris - first) * 3u : 0u;
     auto vertex = [&](uint32_t j) { return reinterpret_cast<const float *>(verts + (size_t)idx_sorted[3 * (size_t)first + j] * stride); };
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    float nan_if_any = 0.f;   // fminf / fmaxf pass a NaN coordinate by: 0 * x is NaN for a NaN or infinite x
     for (uint32_t j = 0; j < n; ++j) {
         const float *p = vertex(j);
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], p[a]); hi[a] = fmaxf(hi[a], p[a]); }
+        for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], p[a]); hi[a] = fmaxf(hi[a], p[a]); nan_if_any = fmaf(0.f, p[a], nan_if_any); }
     }
-    const bool bad = live && box_extent_bad(lo, hi);
+    const bool bad = live && (box_extent_bad(lo, hi) || nan_if_any != nan_if_any);
     if (live && bad) {
         // NaN / infinite coordinates: a bound that k_cull never rejects
         bounds[2 * (size_t)g] = make_float4(0.f, 0.f, 0.f, INFINITY);
@@ -825,7 +826,8 @@ __global__ __launch_bounds__(kBlock) void k_group_bounds(const uint8_t *__restri
 // linear part L = Rinv * A and offset o = Rinv * (A.t - t) of the vertex transform p' = Rinv ((A v) - t), per geometry;
 // nrm >= the largest factor by which L stretches a vector (its Frobenius norm, rounded up: sqrt(3) for a rotation).
 // Uniform per geometry and only ever used in bounds: formed on the host (launch_project), once per launch.
-struct LinearMap { float l[9], o[3], nrm; };
+// e0, e1: how far the vertex path (xform_vertex, ls_device.h) can put a vertex v from L v + o -- at most e0 + e1 |v|_1 (linear_map).
+struct LinearMap { float l[9], o[3], nrm, e0, e1; };
 
 // what k_cull needs of the geometries of a launch (kernel argument)
 struct CullGeom {
@@ -869,6 +871,31 @@ __device__ __forceinline__ bool chan_query(const ChanQuery &cq, float tan_lo, fl
     return lo_i < cq.V && cq.tan_dn[lo_i] <= tan_hi;
 }
 
+// the query's tables where k_cull reads them: global memory as they are, or staged by the workgroup (kBlock threads; a barrier
+// must follow) into s_tan = tan_up[V + 2], tan_dn[V + 2] (two +inf sentinels each), LUT: then chan_lut
+template <bool LDS_TABLES, bool LUT /* needs LDS_TABLES */>
+__device__ __forceinline__ ChanQuery stage_chan_query(const ProjectParams &pp, float *s_tan)
+{
+    const uint32_t V = pp.tb.V;
+    ChanQuery cq = {pp.chan_tan_up, pp.chan_tan_dn, pp.chan_lut, pp.lut_t0, pp.lut_scale, V};
+    if (LDS_TABLES) {
+        float *s_up = s_tan, *s_dn = s_tan + V + 2u;
+        for (uint32_t i = threadIdx.x; i < V + 2u; i += kBlock) {
+            s_up[i] = i < V ? pp.chan_tan_up[i] : INFINITY;
+            s_dn[i] = i < V ? pp.chan_tan_dn[i] : INFINITY;
+        }
+        cq.tan_up = s_up;
+        cq.tan_dn = s_dn;
+        if (LUT) {
+            uint32_t *s_lut = reinterpret_cast<uint32_t *>(s_dn + V + 2u);
+            const uint32_t *g_lut = reinterpret_cast<const uint32_t *>(pp.chan_lut);
+            for (uint32_t i = threadIdx.x; i < kCullLutBuckets / 2u; i += kBlock) s_lut[i] = g_lut[i];
+            cq.lut = reinterpret_cast<const uint16_t *>(s_lut);
+        }
+    }
+    return cq;
+}
+
 // Can any ray of this handle's raster meet the sheared box  { c + a e1 + b e2 + g e3 : |a|, |b|, |g| <= 1 },  e1 = (hx, 0, sx hx),
 // e2 = (0, hy, sy hy), e3 = (0, 0, hz)  (mesh space; b0 = (c, hx), b1 = (hy, hz, sx, sy))?  With p' = L p + o the sensor-
 // frame point and f = z' / rho' the tangent of its elevation:
@@ -884,6 +911,15 @@ __device__ __forceinline__ bool chan_query(const ChanQuery &cq, float tan_lo, fl
 // the azimuth-sector half of the test below, alone (k_cull's workgroup-level early out): seen from above the box lies inside
 // the disc of radius rad around its centre; it is outside a boundary plane of the shard's sector if the centre is further
 // out than that.  Needs no channel table.
+// The triangles k_project tests are the vertex path's, and that path rounds A v + A.t in float BEFORE it subtracts t: under a pose
+// with a georeferenced offset (A.t = 4.2e6 m: half an ulp is 0.25 m) they are not where the box, carried over exactly, says.  The
+// box is widened by the bound of that displacement -- a sphere of this radius around every point of it: ext = the sum of the box's
+// half extents along the mesh axes, so |v|_1 <= |c|_1 + ext for every vertex v inside.
+__device__ __forceinline__ float vertex_path_error(const LinearMap &m, float4 b0, float ext)
+{
+    return fmaf(m.e1, (fabsf(b0.x) + fabsf(b0.y)) + (fabsf(b0.z) + ext), m.e0);
+}
+
 __device__ __forceinline__ bool box_out_of_sector(const ProjectParams &pp, const LinearMap &m, float4 b0, float4 b1)
 {
     const float hx = b0.w, hy = b1.x, hz = b1.y, sx = b1.z, sy = b1.w;
@@ -892,7 +928,8 @@ __device__ __forceinline__ bool box_out_of_sector(const ProjectParams &pp, const
     const float cy = fmaf(m.l[3], b0.x, fmaf(m.l[4], b0.y, fmaf(m.l[5], b0.z, m.o[1])));
     const float rho2 = fmaf(cx, cx, cy * cy);
     if (!(rho2 > 1e-12f) || !(rho2 < INFINITY)) return false;   // on the axis
-    const float rad = m.nrm * fmaf(hx, 1.0f + fabsf(sx), fmaf(hy, 1.0f + fabsf(sy), hz)) * 1.00001f;
+    const float ext = fmaf(hx, 1.0f + fabsf(sx), fmaf(hy, 1.0f + fabsf(sy), hz));
+    const float rad = fmaf(m.nrm * 1.00001f, ext, vertex_path_error(m, b0, ext));
     const float reach = fmaf(rad, 1.0001f, 1e-6f * rho2 * __builtin_amdgcn_rsqf(rho2));
     return (pp.sec_a[0] * cy - pp.sec_a[1] * cx < -reach) | (cx * pp.sec_b[1] - cy * pp.sec_b[0] < -reach);
 }
@@ -915,11 +952,15 @@ __device__ __forceinline__ bool group_meets_raster(const ProjectParams &pp, cons
     const float gx = fmaf(m.l[0], ax, fmaf(m.l[3], ay, m.l[6] * inv_rho));
     const float gy = fmaf(m.l[1], ax, fmaf(m.l[4], ay, m.l[7] * inv_rho));
     const float gz = fmaf(m.l[2], ax, fmaf(m.l[5], ay, m.l[8] * inv_rho));
-    const float w = fmaf(hx, fabsf(fmaf(sx, gz, gx)), fmaf(hy, fabsf(fmaf(sy, gz, gy)), hz * fabsf(gz)));
+    // (the vertex path's displacement, perr: a step of that length changes f by at most |grad f| perr <= (1 + |fc|) perr / rho to
+    // first order, and the box's vertical extent and radius grow by it)
+    const float ext = fmaf(hx, 1.0f + fabsf(sx), fmaf(hy, 1.0f + fabsf(sy), hz));
+    const float perr = vertex_path_error(m, b0, ext);
+    const float w = fmaf(hx, fabsf(fmaf(sx, gz, gx)), fmaf(hy, fabsf(fmaf(sy, gz, gy)), fmaf(hz, fabsf(gz), perr * (1.0f + fabsf(fc)) * inv_rho)));
     // vertical half extent of the box in the sensor frame (exact to rounding: a flat patch of ground has next to none,
     // and it multiplies the larger of the two second-order terms), and its radius
-    const float ez = fmaf(hx, fabsf(fmaf(sx, m.l[8], m.l[6])), fmaf(hy, fabsf(fmaf(sy, m.l[8], m.l[7])), hz * fabsf(m.l[8]))) * 1.00001f;
-    const float rad = m.nrm * fmaf(hx, 1.0f + fabsf(sx), fmaf(hy, 1.0f + fabsf(sy), hz)) * 1.00001f;
+    const float ez = fmaf(fmaf(hx, fabsf(fmaf(sx, m.l[8], m.l[6])), fmaf(hy, fabsf(fmaf(sy, m.l[8], m.l[7])), hz * fabsf(m.l[8]))), 1.00001f, perr);
+    const float rad = fmaf(m.nrm * 1.00001f, ext, perr);
     bool out_of_sector = false;
     if (pp.sector_on) {   // uniform
         // seen from above the box lies inside the disc of radius rad around its centre: outside a boundary plane of the
@@ -978,24 +1019,8 @@ __global__ __launch_bounds__(kBlock) void k_cull(ProjectParams pp, CullBatch bat
     if (has_block) { c0 = block_boxes[2 * (size_t)my_block]; c1 = block_boxes[2 * (size_t)my_block + 1]; }
     const LinearMap &m = src.m;
     if (SECTOR && !__any(has_block && !box_out_of_sector(pp, m, c0, c1))) return;   // (the same in all four waves: no barrier is left waiting)
-    const uint32_t V = pp.tb.V;
-    ChanQuery cq = {pp.chan_tan_up, pp.chan_tan_dn, pp.chan_lut, pp.lut_t0, pp.lut_scale, V};
     if (threadIdx.x == 0) s_n = 0;
-    if (LDS_TABLES) {
-        float *s_up = s_tan, *s_dn = s_tan + V + 2u;
-        for (uint32_t i = threadIdx.x; i < V + 2u; i += kBlock) {
-            s_up[i] = i < V ? pp.chan_tan_up[i] : INFINITY;
-            s_dn[i] = i < V ? pp.chan_tan_dn[i] : INFINITY;
-        }
-        cq.tan_up = s_up;
-        cq.tan_dn = s_dn;
-        if (LUT) {
-            uint32_t *s_lut = reinterpret_cast<uint32_t *>(s_dn + V + 2u);
-            const uint32_t *g_lut = reinterpret_cast<const uint32_t *>(pp.chan_lut);
-            for (uint32_t i = threadIdx.x; i < kCullLutBuckets / 2u; i += kBlock) s_lut[i] = g_lut[i];
-            cq.lut = reinterpret_cast<const uint16_t *>(s_lut);
-        }
-    }
+    const ChanQuery cq = stage_chan_query<LDS_TABLES, LUT>(pp, s_tan);
     __syncthreads();
     const bool block_alive = group_meets_raster<LUT>(pp, cq, m, c0, c1);
     const uint32_t alive_all = (uint32_t)__ballot(has_block && block_alive);
@@ -1038,6 +1063,22 @@ __global__ __launch_bounds__(kBlock) void k_cull(ProjectParams pp, CullBatch bat
     __syncthreads();
     uint32_t *out = list + batch.list_first[gi] + seg * batch.seg_cap[gi] + s_base;
     for (uint32_t i = threadIdx.x; i < n; i += kBlock) out[i] = s_keep[i];
+}
+
+// test hook (launch_chan_query): k_cull's channel query on its own, the tables staged as k_cull stages them -- query i of n:
+// out[2 i] = the look-up table's answer (2: this handle's k_cull does not use it), out[2 i + 1] = the binary search's
+template <bool LDS_TABLES>
+__global__ __launch_bounds__(kBlock) void k_chan_query(ProjectParams pp, const float2 *__restrict__ q, uint32_t n, uint8_t *__restrict__ out)
+{
+    extern __shared__ float s_tan[];
+    const bool lut = LDS_TABLES && pp.lut_ok;   // uniform
+    const ChanQuery cq = lut ? stage_chan_query<LDS_TABLES, LDS_TABLES>(pp, s_tan) : stage_chan_query<LDS_TABLES, false>(pp, s_tan);
+    __syncthreads();
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+        const float2 t = q[i];
+        out[2 * (size_t)i] = lut ? (chan_query<LDS_TABLES>(cq, t.x, t.y) ? 1 : 0) : 2;
+        out[2 * (size_t)i + 1] = chan_query<false>(cq, t.x, t.y) ? 1 : 0;
+    }
 }
 
 // Finish pass, one thread per ray: (1) triangles whose footprint was too large for one wave were
@@ -1496,6 +1537,7 @@ uint32_t cull_resident_workgroups()
 LinearMap linear_map(const GeomSource &src)
 {
     LinearMap m;
+    m.e0 = m.e1 = 0.f;
     if (src.xform == 0) {
         for (int i = 0; i < 9; ++i) m.l[i] = (i % 4 == 0) ? 1.f : 0.f;
         m.o[0] = m.o[1] = m.o[2] = 0.f;
@@ -1522,6 +1564,34 @@ LinearMap linear_map(const GeomSource &src)
         top = std::max(top, row);
     }
     m.nrm = (float)(std::sqrt(top) * 1.00001);
+    // How far xform_vertex can put a vertex from L v + o.  With u = 2^-24, row i of the path is
+    //     q_i = fl(fl(fl(a_i0 x + a_i1 y) + a_i2 z) + a_i3),   d_i = fl(q_i - t_i),   p' = fl(Rinv d):
+    // the three products and two partial sums err by at most 3.1 u S_i, S_i = |a_i0 x| + |a_i1 y| + |a_i2 z| <= amax |v|_1; the
+    // last sum by u |q_i| <= u (|a_i3| + 1.1 S_i) -- the term that does not shrink with the mesh: half an ulp of the pose's offset.
+    // So |q - (A v + A.t)|_2 <= u |A.t|_2 + 4.2 sqrt(3) u amax |v|_1, and Rinv stretches that by at most its largest singular
+    // value (the row-sum bound above).  t itself costs nothing: the subtraction and the product with Rinv round RELATIVE to
+    // their results -- a few u of the vertex's distance from the sensor, an angle of under 6e-7 rad, which the elevation margin
+    // of the channel tables (3.5e-6 rad, of which the rays' own rounding needs 3e-7: ls_internal.h) and the sector's column and a
+    // half of padding hold.  With A the identity (xform 2) A v is exact and both terms are zero.  2 % on top for the second order.
+    if (src.xform == 1) {
+        double rtop = 0.0, amax = 0.0;
+        for (int i = 0; i < 3; ++i) {
+            double row = 0.0;
+            for (int j = 0; j < 3; ++j) {
+                double sij = 0.0;
+                for (int k = 0; k < 3; ++k) sij += (double)a.rinv[3 * k + i] * (double)a.rinv[3 * k + j];
+                row += std::fabs(sij);
+                amax = std::max(amax, std::fabs((double)a.a[4 * i + j]));
+            }
+            rtop = std::max(rtop, row);
+        }
+        const double u = 1.0 / 16777216.0, rn = std::sqrt(rtop) * 1.02;
+        const double at = std::sqrt((double)a.a[3] * a.a[3] + (double)a.a[7] * a.a[7] + (double)a.a[11] * a.a[11]);
+        m.e0 = (float)(rn * u * at);
+        m.e1 = (float)(rn * u * 4.2 * std::sqrt(3.0) * amax);
+        if (!(m.e0 < INFINITY)) m.e0 = INFINITY;   // (a non-finite pose: nothing is rejected)
+        if (!(m.e1 < INFINITY)) m.e1 = INFINITY;
+    }
     return m;
 }
 
@@ -1587,6 +1657,39 @@ bool fill_culled_batch(const GeomSource *srcs, uint32_t n_srcs, GeomBatch &batch
     batch.list_first[batch.n] = entries;
     batch.cull_first[batch.n] = cull_blocks;
     return batch.n > 0;
+}
+// k_cull over the geometries of a culled batch (fill_culled_batch): survivors to `list`, their numbers per list segment to
+// counts[(i * kCullSegs + seg) * 16].  -> the instantiation that ran, as kCullVariant* bits
+uint32_t launch_cull(hipStream_t s, const ProjectParams &pp, const GeomBatch &batch, uint32_t *cull_list, uint32_t *counts, unsigned long long *stats,
+                     hipEvent_t ev_start)
+{
+    const bool lt = pp.tb.V <= 2048u;   // channel tables fit in LDS
+    const dim3 cgrid(batch.cull_first[batch.n]);
+    CullBatch cb;
+    std::memset(static_cast<void *>(&cb), 0, sizeof(cb));   // (argument bytes are compared frame to frame by the frame graph)
+    cb.n = batch.n;
+    cb.rounds = batch.cull_rounds;
+    for (uint32_t i = 0; i < batch.n; ++i) {
+        cb.cull_first[i] = batch.cull_first[i];
+        cb.list_first[i] = batch.list_first[i];
+        cb.seg_cap[i] = batch.seg_cap[i];
+        cb.g[i].boxes = batch.g[i].boxes;
+        cb.g[i].ntris = batch.g[i].ntris;
+        cb.g[i].m = linear_map(batch.g[i]);
+    }
+    cb.cull_first[batch.n] = batch.cull_first[batch.n];
+    const bool lut = lt && pp.lut_ok;
+    const uint32_t clds = lt ? (uint32_t)(2 * ((size_t)pp.tb.V + 2) * sizeof(float) + (lut ? kCullLutBuckets * sizeof(uint16_t) : 0)) : 0u;
+#define LS_CULL_S(L, C, U, S) do { \
+        if (ev_start) hipExtLaunchKernelGGL((k_cull<L, C, U, S>), cgrid, dim3(kBlock), clds, s, ev_start, nullptr, 0u, pp, cb, cull_list, counts, stats); \
+        else launch_k(k_cull<L, C, U, S>, cgrid, dim3(kBlock), clds, s, pp, cb, cull_list, counts, stats); } while (0)
+#define LS_CULL(L, C, U) do { if (pp.sector_on) LS_CULL_S(L, C, U, true); else LS_CULL_S(L, C, U, false); } while (0)
+    if (lut) { if (stats) LS_CULL(true, true, true); else LS_CULL(true, false, true); }
+    else if (lt) { if (stats) LS_CULL(true, true, false); else LS_CULL(true, false, false); }
+    else { if (stats) LS_CULL(false, true, false); else LS_CULL(false, false, false); }
+#undef LS_CULL
+#undef LS_CULL_S
+    return (lut ? kCullVariantLut : 0u) | (lt ? kCullVariantLds : 0u) | (pp.sector_on ? kCullVariantSector : 0u) | (stats ? kCullVariantCount : 0u);
 }
 }  // namespace
 
@@ -1660,33 +1763,7 @@ void launch_project(hipStream_t s, const ProjectParams &pp, const GeomSource *sr
         { static const int shard_pct = lsi::tune_int("LS_PROJECT_SHARD_GRID_PCT", 0); if (shard_pct > 0 && pp.sector_on) grid_pct = (uint32_t)shard_pct; }
         { static const int use_hint = lsi::tune_int("LS_PROJECT_GRID_HINT", 1); if (!use_hint) survivors_hint = 0; }
         if (fill_culled_batch(srcs, n_srcs, batch, blocks, entries, pp.sector_on != 0, grid_pct, survivors_hint)) {
-            const dim3 cgrid(batch.cull_first[batch.n]);
-            CullBatch cb;
-            std::memset(static_cast<void *>(&cb), 0, sizeof(cb));   // (argument bytes are compared frame to frame by the frame graph)
-            cb.n = batch.n;
-            cb.rounds = batch.cull_rounds;
-            for (uint32_t i = 0; i < batch.n; ++i) {
-                cb.cull_first[i] = batch.cull_first[i];
-                cb.list_first[i] = batch.list_first[i];
-                cb.seg_cap[i] = batch.seg_cap[i];
-                cb.g[i].boxes = batch.g[i].boxes;
-                cb.g[i].ntris = batch.g[i].ntris;
-                cb.g[i].m = linear_map(batch.g[i]);
-            }
-            cb.cull_first[batch.n] = batch.cull_first[batch.n];
-            const bool lut = lt && pp.lut_ok;
-            const uint32_t clds = lt ? (uint32_t)(2 * ((size_t)pp.tb.V + 2) * sizeof(float) + (lut ? kCullLutBuckets * sizeof(uint16_t) : 0)) : 0u;
-            uint32_t *counts = big_count + kCullCountAt;
-            // (ev_start: the cull pass belongs to the timed stage, the clock starts with it)
-#define LS_CULL_S(L, C, U, S) do { \
-                if (ev_start) hipExtLaunchKernelGGL((k_cull<L, C, U, S>), cgrid, dim3(kBlock), clds, s, ev_start, nullptr, 0u, pp, cb, cull_list, counts, stats); \
-                else launch_k(k_cull<L, C, U, S>, cgrid, dim3(kBlock), clds, s, pp, cb, cull_list, counts, stats); } while (0)
-#define LS_CULL(L, C, U) do { if (pp.sector_on) LS_CULL_S(L, C, U, true); else LS_CULL_S(L, C, U, false); } while (0)
-            if (lut) { if (stats) LS_CULL(true, true, true); else LS_CULL(true, false, true); }
-            else if (lt) { if (stats) LS_CULL(true, true, false); else LS_CULL(true, false, false); }
-            else { if (stats) LS_CULL(false, true, false); else LS_CULL(false, false, false); }
-#undef LS_CULL
-#undef LS_CULL_S
+            launch_cull(s, pp, batch, cull_list, big_count + kCullCountAt, stats, ev_start);   // (ev_start: the cull pass belongs to the timed stage, the clock starts with it)
             ev_start = nullptr;
             launch(batch, blocks, cull_list);
             culled_done = true;
@@ -1716,6 +1793,39 @@ void launch_project(hipStream_t s, const ProjectParams &pp, const GeomSource *sr
         launch(batch, blocks, nullptr);
     }
     if (rider) launch_finish_pack(s, pp, *rider, stats);   // nothing was launched for it to ride with
+}
+
+bool launch_cull_probe(hipStream_t s, const ProjectParams &pp, const GeomSource *srcs, uint32_t n_srcs, uint32_t *list, uint32_t *counts,
+                       unsigned long long *stats, CullProbe &out)
+{
+    GeomBatch batch;
+    std::memset(static_cast<void *>(&batch), 0, sizeof(batch));
+    std::memset(&out, 0, sizeof(out));
+    uint32_t blocks, entries;
+    if (!fill_culled_batch(srcs, n_srcs, batch, blocks, entries, pp.sector_on != 0)) return false;
+    out.n = batch.n;
+    out.entries = entries;
+    uint32_t at = 0;
+    for (uint32_t i = 0; i < n_srcs && at < batch.n; ++i) {   // fill_culled_batch's order
+        if (!srcs[i].boxes || !srcs[i].ntris) continue;
+        out.src_index[at] = i;
+        out.list_first[at] = batch.list_first[at];
+        out.seg_cap[at] = batch.seg_cap[at];
+        ++at;
+    }
+    if (list) out.variant = launch_cull(s, pp, batch, list, counts, stats, nullptr);
+    return true;
+}
+
+void launch_chan_query(hipStream_t s, const ProjectParams &pp, const float *d_lo_hi, uint32_t n, uint8_t *d_out)
+{
+    if (!n) return;
+    const bool lt = pp.tb.V <= 2048u, lut = lt && pp.lut_ok;   // as launch_cull
+    const uint32_t lds = lt ? (uint32_t)(2 * ((size_t)pp.tb.V + 2) * sizeof(float) + (lut ? kCullLutBuckets * sizeof(uint16_t) : 0)) : 0u;
+    const dim3 grid(std::min<uint32_t>((n + kBlock - 1) / kBlock, 64u));
+    const float2 *q = reinterpret_cast<const float2 *>(d_lo_hi);
+    if (lt) hipLaunchKernelGGL(k_chan_query<true>, grid, dim3(kBlock), lds, s, pp, q, n, d_out);
+    else hipLaunchKernelGGL(k_chan_query<false>, grid, dim3(kBlock), lds, s, pp, q, n, d_out);
 }
 
 bool launch_mesh_order(hipStream_t s, const uint8_t *verts, uint32_t stride, uint32_t nverts, const uint32_t *idx, uint32_t ntris,

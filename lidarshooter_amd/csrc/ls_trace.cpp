@@ -97,6 +97,39 @@ ls::ProjectParams project_params(const ls_tracer *tr)
     return pp;
 }
 
+int project_sources(ls_tracer *tr, std::vector<ls::GeomSource> &srcs, bool &any_culled)
+{
+    srcs.clear();
+    any_culled = false;
+    for (const auto &le : tr->layout) {
+        auto it = tr->geoms.find(le.name);
+        if (it == tr->geoms.end()) return fail(tr, LS_ERR_NOT_COMMITTED, "geometry removed since the last commit");
+        const Geometry &ge = it->second;
+        ls::GeomSource src;
+        std::memset(static_cast<void *>(&src), 0, sizeof(src));   // (padding too: the frame graph compares argument bytes)
+        src.verts = static_cast<const uint8_t *>(ge.raw());
+        src.stride = ge.stride;
+        src.idx = ge.idx();
+        src.ntris = ge.n_tris;
+        src.gid_first = le.tfirst;
+        static const float kIdentity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        src.xform = std::memcmp(ge.affine, kIdentity, sizeof(kIdentity)) == 0 ? 2 : 1;
+        std::memcpy(src.m.a, ge.affine, sizeof(src.m.a));
+        std::memcpy(src.m.rinv, tr->rinv, sizeof(src.m.rinv));
+        std::memcpy(src.m.t, tr->t, sizeof(src.m.t));
+        // block culling data is current (prepare_blocks ran at the commit) unless an update came in since
+        const bool culled = cull_enabled(tr, ge) && ge.d_boxes && ge.d_corners && !ge.order_stale && !ge.bounds_stale &&
+                            cull_size_ok(tr, ge.n_tris);
+        src.perm = culled ? ge.d_perm : nullptr;
+        src.boxes = culled ? ge.d_boxes : nullptr;
+        src.corners = culled ? ge.d_corners : nullptr;
+        if (culled) src.idx = ge.d_idx_sorted;
+        any_culled = any_culled || culled;
+        srcs.push_back(src);
+    }
+    return LS_OK;
+}
+
 namespace {
 
 // LS_OPT_PIPELINE = 2 needs three streams whose kernels really run side by side.  The runtime multiplexes
@@ -683,34 +716,8 @@ int trace_once(ls_tracer *tr, uint32_t frame, ls_frame *out, bool readback)
         const bool ride = tr->opt_timing == 2;
         mark(tr, 7, ride ? &ev_k0 : nullptr);
         std::vector<ls::GeomSource> &srcs = tr->project_srcs;
-        srcs.clear();
         bool any_culled = false;
-        for (const auto &le : tr->layout) {
-            auto it = tr->geoms.find(le.name);
-            if (it == tr->geoms.end()) return fail(tr, LS_ERR_NOT_COMMITTED, "geometry removed since the last commit");
-            const Geometry &ge = it->second;
-            ls::GeomSource src;
-            std::memset(static_cast<void *>(&src), 0, sizeof(src));   // (padding too: the frame graph compares argument bytes)
-            src.verts = static_cast<const uint8_t *>(ge.raw());
-            src.stride = ge.stride;
-            src.idx = ge.idx();
-            src.ntris = ge.n_tris;
-            src.gid_first = le.tfirst;
-            static const float kIdentity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-            src.xform = std::memcmp(ge.affine, kIdentity, sizeof(kIdentity)) == 0 ? 2 : 1;
-            std::memcpy(src.m.a, ge.affine, sizeof(src.m.a));
-            std::memcpy(src.m.rinv, tr->rinv, sizeof(src.m.rinv));
-            std::memcpy(src.m.t, tr->t, sizeof(src.m.t));
-            // block culling data is current (prepare_blocks ran at the commit) unless an update came in since
-            const bool culled = cull_enabled(tr, ge) && ge.d_boxes && ge.d_corners && !ge.order_stale && !ge.bounds_stale &&
-                                ls::project_tris_per_wave(ge.n_tris) == 64u;
-            src.perm = culled ? ge.d_perm : nullptr;
-            src.boxes = culled ? ge.d_boxes : nullptr;
-            src.corners = culled ? ge.d_corners : nullptr;
-            if (culled) src.idx = ge.d_idx_sorted;
-            any_culled = any_culled || culled;
-            srcs.push_back(src);
-        }
+        if ((rc = project_sources(tr, srcs, any_culled))) return rc;
         // survivor list of this frame's k_cull: one of three (as many frames as can be in flight)
         uint32_t *cull_list = nullptr;
         if (any_culled) {
