@@ -996,6 +996,66 @@ int ls_hit_velocities_host(ls_tracer *tr, const float *col_pose, uint32_t n_cols
 int ls_twist_table_constant(const float lin_vel[3], const float ang_vel[3], const float pivot[3],
                             double t0, double dt, uint32_t n_cols, float *col_twist);
 
+/* ---- object labels: what detection and tracking ground truth asks per GEOMETRY of a frame -- how many points it got, where they
+ * are (a box in the sensor frame), how near it is, and how much of it other geometries hide (KITTI's occlusion level) -- from hit
+ * records that are already in device memory, without reading the cloud back.  The first three are a reduction over the records; the
+ * last needs the rays that would hit the geometry if it stood alone, which no other call answers: a walk over the query hierarchies
+ * of ls_trace_rays, one geometry after the other, that does not stop at a ray's first hit.
+ *   d_labels: n_labels ls_object_label records indexed by geomID (the convention of d_reflectivity), 16-byte aligned; every one of
+ *            them is written.  A geomID below n_labels that names no geometry of the committed scene gets the empty record with
+ *            flags = 0; a committed geometry whose id is >= n_labels is counted nowhere, neither in hits nor in the footprint.
+ *   d_rays, n_rays, d_hits, d_count, n: exactly as ls_hit_attributes takes them.  d_rays = NULL: the handle's own sensor rays,
+ *            hit.ray the global ray index, the bound V * H, n_rays ignored.  d_count NULL or a device word: min(n, *d_count)
+ *            records are handled.  n = 0 with d_hits = NULL is allowed: the footprint alone.
+ *   flags:   0 or LS_LABEL_FOOTPRINT; any other bit is refused.
+ * A record COUNTS when hit.geom < n_labels and names a geometry of the committed scene, hit.prim < its element count, hit.ray < the
+ * ray bound, hit.t is finite and >= 0 (a -0 counts as +0) and, with caller rays, the ray is one ls_trace_rays walks: finite origin
+ * and direction, a non-zero direction, tmin <= tmax.  The triangle is NOT tested again: this is a reduction, not the validity gather
+ * of ls_hit_attributes -- a stale t of a geometry moved since counts where it says.  Every index is checked before an address is
+ * formed from it.  A record's point is ls_hit_attributes' px, py, pz: o + t d per axis (one product, one sum) for a caller ray, t d
+ * with no sum for a sensor ray -- the bits of the frame's points32.
+ * Every value is an integer count, a minimum or a maximum (of floats, -0 below +0; of (t, ray) pairs): none depends on the order of
+ * the records or of the device's work, so the records are the same bytes from call to call and for shuffled input.
+ * LS_LABEL_FOOTPRINT: over the n_rays caller rays -- or, with d_rays = NULL, over all V * H rays of the handle's full raster whatever
+ * the shard, generated into a scratch buffer of the handle as ls_generate_rays_aos generates them, with tmin = 0 and tmax = +inf --
+ * ray r adds one to n_alone[g] for every committed geometry g with id < n_labels on which the exact test of ls_occluded_rays passes
+ * for some triangle with tmin <= t <= tmax.  A ray through three geometries counts in all three; a degenerate ray, as ls_trace_rays
+ * defines it, counts nowhere.  When the records are the closest hits of those same rays, n_hits[g] <= n_alone[g], and the visible
+ * fraction of g is n_hits / n_alone.  The flag uses the query hierarchies ls_trace_rays and its siblings share and builds what they
+ * lack: LS_INFO_RAY_QUERY_BUILT reports for it.  Without the flag no hierarchy is touched and that word is left as it is.
+ * LS_ERR_INVALID_ARGUMENT before any device call, in this order: a frame graph is open; NULL d_labels with n_labels > 0; NULL hits
+ * with n > 0; unknown flag bits; misaligned pointers for the device call (rays, records and labels 16 bytes, the count 4).  Then
+ * LS_ERR_OUT_OF_RANGE for n or n_rays above the query-record limit or n_labels above 65536, then the commit state as
+ * ls_hit_attributes (-1 with no commit or an empty scene: nothing is written).  Stream order and the frame graph rule are those of
+ * ls_trace_rays.  Calls on one handle use scratch buffers of the handle (64 bytes per label; 32 bytes per ray of the raster for the
+ * footprint of the sensor's own rays) and are ordered through its stream: one at a time.
+ * Not offered: labels for sweep, moving or beam frames (their points are not o + t d of one ray); centroids (float sums depend on
+ * the order). */
+#define LS_LABEL_FOOTPRINT 1u   /* also count, per geometry, the rays that hit it taken alone (n_alone) */
+
+typedef struct ls_object_label {   /* 64 bytes, no pointers */
+    uint32_t n_hits;     /* records that name this geometry and count (above) */
+    uint32_t n_alone;    /* LS_LABEL_FOOTPRINT: rays that pass the exact test on some triangle of THIS geometry within [tmin, tmax],
+                            whatever else is in the scene; 0 without the flag */
+    float    t_min;      /* smallest t of the counted records; +inf when n_hits = 0 */
+    uint32_t ray_min;    /* the lowest hit.ray among the records with that t; 0xFFFFFFFF when n_hits = 0 */
+    float    t_max;      /* largest t; -inf when n_hits = 0 */
+    uint32_t ray_max;    /* the lowest hit.ray among the records with that t; 0xFFFFFFFF when n_hits = 0 */
+    float    lo[3];      /* per-axis minimum of the counted records' points; +inf when n_hits = 0 */
+    float    hi[3];      /* per-axis maximum; -inf when n_hits = 0 */
+    uint32_t flags;      /* bit 0: this geomID names a geometry of the committed scene */
+    uint32_t reserved[3];/* 0 */
+} ls_object_label;
+
+int ls_object_labels(ls_tracer *tr, void *hip_stream, uint32_t flags,
+                     const void *d_rays, uint32_t n_rays,
+                     const void *d_hits, const uint32_t *d_count, uint32_t n,
+                     void *d_labels, uint32_t n_labels);
+/* The same with host memory (pageable, any alignment) in and out and no count word, on the handle's stream; returns when labels is
+ * filled. */
+int ls_object_labels_host(ls_tracer *tr, uint32_t flags, const void *rays, uint32_t n_rays,
+                          const void *hits, uint32_t n, void *labels, uint32_t n_labels);
+
 /* ---- clouds in a driver's own PointCloud2 layout.  Every frame call above leaves the same fixed cloud: 32-byte XYZIR records
  * (XYZIRBytes.cpp:24-40), compacted, and next to it the ls_hit records (and, for beams, the echo words).  What a driver publishes
  * differs: Velodyne's 22-byte XYZIRT with a per-point `time` (what LIO-SAM, FAST-LIO and KISS-ICP deskew by), Ouster's organized

@@ -60,6 +60,7 @@ SYMBOLS = (
     "ls_trace_scene_sweep_moving", "ls_trace_scene_sweep_moving_host", "ls_motion_constant_twist",
     "ls_hit_attributes_moving", "ls_hit_attributes_moving_host", "ls_apply_return_model_moving", "ls_apply_return_model_moving_host",
     "ls_hit_velocities", "ls_hit_velocities_host", "ls_twist_table_constant",
+    "ls_object_labels", "ls_object_labels_host",
     "ls_format_cloud", "ls_format_cloud_host", "ls_cloud_format_check", "ls_cloud_format_from_point_fields", "ls_column_times",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
@@ -196,6 +197,11 @@ HIT_ATTR_DTYPE = np.dtype([("n", "<f4", 3), ("cos_inc", "<f4"), ("u", "<f4"), ("
 # ls_hit_velocities: the surface's velocity, the range rate and the velocity of the sensor's origin at one ls_hit (flags bit 0: valid;
 # an invalid record is zeros)
 HIT_VELOCITY_DTYPE = np.dtype([("v_s", "<f4", 3), ("radial", "<f4"), ("v_o", "<f4", 3), ("flags", "<u4")])
+# ls_object_labels: what one geometry got of a frame's hit records (flags bit 0: the geomID names a committed geometry; n_hits = 0:
+# t_min / lo = +inf, t_max / hi = -inf, the rays 0xFFFFFFFF)
+LS_LABEL_FOOTPRINT = 1
+OBJECT_LABEL_DTYPE = np.dtype([("n_hits", "<u4"), ("n_alone", "<u4"), ("t_min", "<f4"), ("ray_min", "<u4"), ("t_max", "<f4"), ("ray_max", "<u4"),
+                               ("lo", "<f4", 3), ("hi", "<f4", 3), ("flags", "<u4"), ("reserved", "<u4", 3)])
 NODE_DTYPE = np.dtype([("llo", "<f4", 3), ("left", "<u4"), ("lhi", "<f4", 3), ("right", "<u4"),
                        ("rlo", "<f4", 3), ("pad0", "<u4"), ("rhi", "<f4", 3), ("pad1", "<u4")])
 LEAF_BIT = 0x80000000
@@ -340,6 +346,8 @@ def load() -> C.CDLL:
     L.ls_hit_velocities.argtypes = [vp, vp, vp, u32, C.POINTER(GeometryMotion), u32, vp, C.POINTER(GeometryTwist), u32, u32, vp, vp, u32, vp, vp]
     L.ls_hit_velocities_host.argtypes = [vp, vp, u32, C.POINTER(GeometryMotion), u32, vp, C.POINTER(GeometryTwist), u32, u32, vp, u32, vp, vp]
     L.ls_twist_table_constant.argtypes = [f32p, f32p, f32p, C.c_double, C.c_double, u32, f32p]
+    L.ls_object_labels.argtypes = [vp, vp, u32, vp, u32, vp, vp, u32, vp, u32]
+    L.ls_object_labels_host.argtypes = [vp, u32, vp, u32, vp, u32, vp, u32]
     L.ls_debug_hit_velocity.argtypes = [f32p, C.c_float, f32p, f32p, f32p]
     L.ls_format_cloud.argtypes = [vp, vp, C.POINTER(CloudFormat), vp, vp, vp, vp, u32, vp, vp, vp]
     L.ls_format_cloud_host.argtypes = [vp, C.POINTER(CloudFormat), vp, vp, vp, u32, vp, vp, vp]
@@ -488,10 +496,16 @@ class Tracer:
 
     # ---- ITracer surface
     def addGeometry(self, name: str, n_vertices: int, n_elements: int, geometry_type: int = 0) -> int:
-        return self.L.ls_add_geometry(self.h, name.encode(), geometry_type, int(n_vertices), int(n_elements))
+        gid = self.L.ls_add_geometry(self.h, name.encode(), geometry_type, int(n_vertices), int(n_elements))
+        if gid >= 0:
+            self.__dict__.setdefault("_geom_ids", {})[name] = int(gid)   # (objectLabels' default n_labels)
+        return gid
 
     def removeGeometry(self, name: str) -> int:
-        return self.L.ls_remove_geometry(self.h, name.encode())
+        rc = self.L.ls_remove_geometry(self.h, name.encode())
+        if rc >= 0:
+            self.__dict__.setdefault("_geom_ids", {}).pop(name, None)
+        return rc
 
     def updateGeometry(self, name: str, affine, verts: np.ndarray, tris: np.ndarray | None, stride: int | None = None):
         A = np.ascontiguousarray(affine, np.float32).reshape(12)
@@ -823,6 +837,42 @@ class Tracer:
         None: the handle's), no wait.  -> 0, or -1 on an empty / uncommitted scene (d_out not written)."""
         rc = self.L.ls_hit_attributes(self.h, stream, d_rays or None, n_rays, d_hits or None, d_count or None, n, d_out or None)
         return -1 if rc == -1 else int(self._check(rc, "ls_hit_attributes"))
+
+    @staticmethod
+    def emptyObjectLabels(n_labels: int):
+        """n_labels records of a geomID that got nothing and names nothing: what objectLabels returns for rc = -1"""
+        out = np.zeros(n_labels, OBJECT_LABEL_DTYPE)
+        out["t_min"], out["lo"] = np.inf, np.inf
+        out["t_max"], out["hi"] = -np.inf, -np.inf
+        out["ray_min"], out["ray_max"] = INVALID, INVALID
+        return out
+
+    def objectLabels(self, hits, rays=None, footprint: bool = True, n_labels: int | None = None):
+        """Per-geometry labels of hit records (ls_object_labels_host): `hits` and `rays` as hitAttributes takes them (`hits` may be
+        None or empty: the footprint alone), `footprint`: also n_alone, the rays that hit each geometry taken alone
+        (LS_LABEL_FOOTPRINT); `n_labels` records indexed by geomID, by default the highest id added through this object + 1.
+        -> (rc, OBJECT_LABEL_DTYPE[n_labels]); rc = -1 (no commit, empty scene): every record empty with flags = 0."""
+        h = self._hit_array(np.zeros(0, HIT_DTYPE) if hits is None else hits)
+        n = h.shape[0]
+        r = None if rays is None else self._ray_array(rays)
+        if n_labels is None:
+            n_labels = max(self.__dict__.get("_geom_ids", {}).values(), default=-1) + 1
+        out = np.zeros(n_labels, OBJECT_LABEL_DTYPE)
+        rc = self.L.ls_object_labels_host(self.h, LS_LABEL_FOOTPRINT if footprint else 0, None if r is None else (r.ctypes.data if r.shape[0] else out.ctypes.data),
+                                          0 if r is None else r.shape[0], h.ctypes.data if n else None, n, out.ctypes.data if n_labels else None, n_labels)
+        if rc == -1:
+            return -1, self.emptyObjectLabels(n_labels)
+        self._check(rc, "ls_object_labels_host")
+        return int(rc), out
+
+    def objectLabelsDevice(self, d_labels: int, n_labels: int, d_hits: int = 0, n: int = 0, d_rays: int = 0, n_rays: int = 0, d_count: int = 0,
+                           footprint: bool = True, stream=None) -> int:
+        """ls_object_labels on device pointers (n 16-byte ls_hit records in, n_labels 64-byte records out; d_rays = 0: the handle's
+        sensor rays; d_count != 0: a device word, min(n, *d_count) records are handled); enqueued on `stream` (a hipStream_t as an
+        int, None: the handle's), no wait.  -> 0, or -1 on an empty / uncommitted scene (d_labels not written)."""
+        rc = self.L.ls_object_labels(self.h, stream, LS_LABEL_FOOTPRINT if footprint else 0, d_rays or None, n_rays, d_hits or None, d_count or None,
+                                     n, d_labels or None, n_labels)
+        return -1 if rc == -1 else int(self._check(rc, "ls_object_labels"))
 
     def applyReturnModel(self, model: ReturnModel, hits, rays=None, reflectivity=None, frame_index: int = 0):
         """Sensor returns from hit records (ls_apply_return_model_host): `hits` and `rays` as hitAttributes takes them, `reflectivity`

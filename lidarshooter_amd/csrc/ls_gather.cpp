@@ -15,8 +15,6 @@
 
 namespace lsi {
 
-namespace {
-
 // the table k_hit_attributes reads, one entry per geomID up to the highest committed one (free ids stay zero), from the committed
 // layout and the geometries' current buffers and poses (committed_geometry's checks), and for a moving call the motion-table pointer
 // per geomID next to it, as long as it is; each uploaded on s when it differs from what the device holds
@@ -48,6 +46,8 @@ int tables_prepare(ls_tracer *tr, hipStream_t s, const Moving *mv)
     std::vector<const float *> by_id = mv->per_geom(tr->ha.table.current.size());
     return tr->ha.motion.upload_if_changed(tr, s, by_id);
 }
+
+namespace {
 
 // what the moving calls refuse after their own NULL checks, in this order: ls_trace_scene_sweep_moving's pose table, flags and
 // motions; misaligned device pointers (p16: records and points, p4: words and reflectivities; the tables 4 bytes); too many records;

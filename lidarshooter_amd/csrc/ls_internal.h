@@ -314,6 +314,9 @@ struct ls_tracer {
         lsi::DevBuf<uint32_t> beam_counts;
         // ls_format_cloud, organized: which record fills each of the V * H cells (one call at a time, as the sweep)
         lsi::DevBuf<uint32_t> cloud_map;
+        // ls_object_labels: one 64-byte accumulator per geomID below n_labels (ls::LabelAcc), and the V * H records of the handle's own
+        // rays for its footprint (32 bytes each) -- one call at a time, as the sweep
+        lsi::DevBuf<uint8_t> label_acc, label_rays;
         std::vector<RayQuerySlot> built;       // per layout entry
         std::vector<int> layout_ids;           // geometry ids of the layout the slots were made for ...
         std::vector<uint32_t> layout_firsts;   // ... and their first vertex, first triangle in it
@@ -512,11 +515,17 @@ template <typename... P>
 inline bool misaligned16(const P *...p) { return (misaligned(p, 16) || ...); }
 // a query's place among what the handle issues (query_enter: the call's one flush_pipeline) and its walk over the hierarchies
 struct RayQueryKind;
+struct Moving;
 const RayQueryKind &closest_hits();   // ls_trace_rays' kind: the walk of the frames in ls_scan.cpp
 int query_enter(ls_tracer *tr, hipStream_t s);
 int query_walk(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, void *d_out, const RayQueryKind &kind,
                const float *const *motion = nullptr);   // motion: ls_trace_scene_sweep_moving's tables, one per layout entry
 int query_leave(ls_tracer *tr, hipStream_t s);
+// ls_object_labels' footprint (ls_labels_host.cpp): the query set brought up to date as query_walk does, then k_label_footprint over the n
+// rays, one launch per batch of kGeomsPerLaunch geometries, each on its own -- a geometry whose id is >= n_labels is not walked
+int query_footprint(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, bool own_rays, uint32_t n_labels, void *d_acc);
+// ls_gather.cpp: the per-geomID table of the gathers (tr->ha.table) brought up to date on s; mv: a moving call's motion tables too
+int tables_prepare(ls_tracer *tr, hipStream_t s, const Moving *mv);
 // the tail of every device entry point: the query's place on s around what it issues
 template <typename Issue>
 inline int query_run(ls_tracer *tr, hipStream_t s, Issue &&issue)

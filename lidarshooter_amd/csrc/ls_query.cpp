@@ -14,6 +14,7 @@
 // What a slot was built from (vertex / index upload, mode, pose) is kept per slot: a query after a commit that changed only
 // poses builds nothing; new vertices refit that geometry (its sorted order is kept in the set's own keys), new indices rebuild it.
 #include "ls_internal.h"
+#include "ls_labels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -221,7 +222,7 @@ void ray_query_release(ls_tracer *tr)
     release(q.keys_a); release(q.keys_b); release(q.vals_b); release(q.sort_temp); release(q.spill); release(q.io);
     release(q.sweep_rays); release(q.sweep_hits); release(q.sweep_counts);
     release(q.beam_rays); release(q.beam_hits); release(q.beam_blocks); release(q.beam_counts);
-    release(q.cloud_map);
+    release(q.cloud_map); release(q.label_acc); release(q.label_rays);
     if (q.d_maxabs) (void)hipFree(q.d_maxabs);
     if (q.d_counters) (void)hipFree(q.d_counters);
     if (q.ev_ready) (void)hipEventDestroy(q.ev_ready);
@@ -320,6 +321,37 @@ int query_walk(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, voi
             continue;
         }
         kind.launch(s, tr->trace_blocks, d_rays, n, batch, pm, q.wide_nodes.p, q.records.p, q.leaf, d_out, q.d_counters + b, q.spill.p);
+    }
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+// ls_object_labels' footprint: query_walk's preparation and batches around k_label_footprint (ls_labels.hip).  The counts go to the
+// call's accumulators, nothing to a per-ray output, and no launch starts from what another one left.
+int query_footprint(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, bool own_rays, uint32_t n_labels, void *d_acc)
+{
+    ls_tracer::RayQuery &q = tr->rq;
+    int rc;
+    std::vector<Geometry *> order;
+    std::vector<bool> sensor_frame;
+    if ((rc = ray_query_prepare(tr, s, order, sensor_frame))) return rc;
+    if ((rc = ensure(tr, q.spill, ls::trace_spill_bytes(tr->trace_blocks) / 4))) return rc;
+    if (!q.d_counters) LS_HIP(hipMalloc(reinterpret_cast<void **>(&q.d_counters), kMaxRayLaunches * 4));
+    const uint32_t launches = (uint32_t)((order.size() + ls::kGeomsPerLaunch - 1) / ls::kGeomsPerLaunch);
+    LS_HIP(hipMemsetAsync(q.d_counters, 0, (size_t)launches * 4, s));
+    for (uint32_t b = 0; b < launches; ++b) {
+        ls::RayBatch batch;
+        std::memset(static_cast<void *>(&batch), 0, sizeof(batch));
+        const size_t first = (size_t)b * ls::kGeomsPerLaunch, last = std::min(order.size(), first + ls::kGeomsPerLaunch);
+        batch.n = (uint32_t)(last - first);
+        batch.first = 1u;
+        for (size_t i = first; i < last; ++i) {
+            ls::RayGeom &rg = batch.g[i - first];
+            ray_geom(tr, i, *order[i], sensor_frame[i], rg);
+            if (rg.geom_id >= n_labels) rg.n_leaves = 0;   // no record for it: counted nowhere, and no accumulator to add to
+        }
+        ls::launch_label_footprint(s, tr->trace_blocks, d_rays, n, own_rays, batch, q.wide_nodes.p, q.records.p, q.leaf,
+                                   static_cast<ls::LabelAcc *>(d_acc), q.d_counters + b, q.spill.p);
     }
     LS_HIP(hipGetLastError());
     return LS_OK;
