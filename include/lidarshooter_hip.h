@@ -1056,6 +1056,74 @@ int ls_object_labels(ls_tracer *tr, void *hip_stream, uint32_t flags,
 int ls_object_labels_host(ls_tracer *tr, uint32_t flags, const void *rays, uint32_t n_rays,
                           const void *hits, uint32_t n, void *labels, uint32_t n_labels);
 
+/* ---- occupancy grid: what mapping and occupancy-prediction ground truth asks per CELL of a voxel grid -- did a return fall in it,
+ * did a ray cross it before its return or before it ran out of range (observed free space), or did no ray touch it (unknown) -- from
+ * hit records that are already in device memory.  Every call above describes what the rays hit; this one describes what they passed
+ * through: each ray is walked through the grid, cell by cell, up to its return.
+ *   grid:     the descriptor below, a host pointer, copied during the call.
+ *   sensor_to_grid3x4: a host pointer to 12 floats (row-major 3 x 4, copied during the call), or NULL.  NULL applies no arithmetic
+ *             at all to the ray: the grid is given in the sensor frame, and for the handle's own rays the occupied cell is the cell
+ *             of the frame's points32 xyz, bit for bit.  Non-NULL: origin and direction go through the affine in the order
+ *             ls_cloud_to_world applies its affine to a point -- o'_i = ((m[i][0] o_0 + m[i][1] o_1) + m[i][2] o_2) + m[i][3], the
+ *             direction the same without the translation --; t is unchanged: the matrix is taken as rigid, only finiteness is checked.
+ *   d_rays, n_rays, d_hits, d_count, n: exactly as ls_object_labels takes them.  d_rays = NULL: the handle's own sensor rays, the full
+ *             V x H raster whatever the shard, hit.ray the global ray index, tmin = 0 and tmax = +inf.  n = 0 with d_hits = NULL is
+ *             allowed: every ray is a miss.
+ *   d_counts: nx ny nz records of two uint32_t {n_free, n_occ}, 16-byte aligned; every one of them is written.
+ *   d_geom:   NULL, or nx ny nz uint32_t: the lowest geomID among the counted records whose point fell in the cell, 0xFFFFFFFF
+ *             where there is none.
+ * A record COUNTS by ls_object_labels' rule: hit.geom names a committed geometry, hit.prim < its element count, hit.ray < the ray
+ * bound, t is finite and >= 0 (a -0 counts as +0) and the ray is walkable (finite origin and direction, a non-zero direction, tmin <=
+ * tmax).  Every index is checked before an address is formed from it.  Where several counted records name one ray, the one with the
+ * smallest t decides, then the lowest geomID (a 64-bit minimum per ray in a scratch buffer of the handle, 8 bytes per ray).
+ * Per ray, with t_start = max(tmin, min_range) and t_far = min(tmax, max_range):
+ *   no deciding record, without LS_OCC_CARVE_MISSES, or a ray that is not walkable:   nothing;
+ *   no deciding record, with the flag:        free cells on [t_start, t_far];
+ *   t < min_range:                            nothing (blocked in the blind zone);
+ *   min_range <= t <= max_range:              free cells on [t_start, t], and the cell of p = o + t d is occupied if p is inside;
+ *   t > max_range:                            free cells on [t_start, t_far], with or without the flag.
+ * p is one product and one sum per axis (t d with no sum for an own ray without a transform); its cell is floorf((p - origin) /
+ * cell) per axis, compared as floats against [0, n) before any cast, and does not depend on the walk.  The occupied cell gets n_occ
+ * += 1 and geom = min(geom, hit.geom).  The walk adds n_free += 1 to every cell it visits except this ray's own occupied cell; it
+ * visits a cell at most once, so n_free counts rays.  A cell with n_free = n_occ = 0 is unknown.
+ * The walk (csrc/ls_voxel.h, float32, every operation rounded once, no reciprocal and no accumulated boundary): the span is clipped
+ * against the grid's box per axis by two divisions; the first cell is floorf of the entry point, clamped into the grid; from cell
+ * c the ray leaves along axis a at ((c_a + (d_a > 0)) cell - q_a) / d_a, q = o - origin; the smallest of the three decides, ties
+ * going to x, then y, then z; the walk ends when that parameter is beyond the span or the next cell is outside, after at most nx +
+ * ny + nz cells.  ls_debug_voxel_walk runs the same sequence on the host for one ray.
+ * Every value is an integer count or a minimum: the grid is the same bytes whatever the order of the records and of the device's
+ * work, from call to call.
+ * LS_ERR_INVALID_ARGUMENT before any device call, in this order: a frame graph is open; NULL grid; NULL d_counts; NULL hits with n >
+ * 0; unknown flag bits or non-zero reserved; a non-finite origin or transform; cell not finite or not > 0; min_range not finite or
+ * < 0; max_range not finite or < min_range; misaligned pointers for the device call (rays, records and counts 16 bytes; geom and the
+ * count word 4).  Then LS_ERR_OUT_OF_RANGE for a dimension of 0 or above 2048, nx ny nz above 2^27, a non-finite origin + n cell, n
+ * or n_rays above the query-record limit; then the commit state as ls_object_labels (-1 with no commit or an empty scene: nothing
+ * is written).  ls_occupancy_grid_check returns the descriptor's part of this (host only, no device call).  Stream order, the
+ * one-call-at-a-time rule and the frame graph rule are those of ls_trace_rays.
+ * Not offered: grids of sweep, moving or beam frames (their points are not o + t d of one ray); a majority label per cell; log-odds
+ * (float sums depend on the order); non-cubic cells; a call of the ITracer adapter. */
+#define LS_OCC_CARVE_MISSES 1u   /* a ray with no counted record carves free space up to min(tmax, max_range) */
+#define LS_OCC_ACCUMULATE   2u   /* add to what d_counts / d_geom hold instead of clearing them first */
+
+typedef struct ls_occupancy_grid_desc {   /* 48 bytes, no pointers */
+    float    origin[3];   /* minimum corner of cell (0,0,0), in the grid's frame */
+    float    cell;        /* edge of a cubic cell */
+    uint32_t dims[3];     /* nx, ny, nz; cell (x,y,z) is word pair (z*ny + y)*nx + x */
+    uint32_t flags;
+    float    min_range;   /* the walk starts at max(tmin, min_range): the sensor's blind zone */
+    float    max_range;   /* range gate, finite */
+    uint32_t reserved[2]; /* 0 */
+} ls_occupancy_grid_desc;
+
+int ls_occupancy_grid(ls_tracer *tr, void *hip_stream, const ls_occupancy_grid_desc *grid, const float *sensor_to_grid3x4,
+                      const void *d_rays, uint32_t n_rays, const void *d_hits, const uint32_t *d_count, uint32_t n,
+                      void *d_counts, void *d_geom);
+/* The same with host memory (pageable, any alignment) in and out and no count word, on the handle's stream; returns when counts and
+ * geom are filled.  With LS_OCC_ACCUMULATE the two arrays travel to the device first. */
+int ls_occupancy_grid_host(ls_tracer *tr, const ls_occupancy_grid_desc *grid, const float *sensor_to_grid3x4,
+                           const void *rays, uint32_t n_rays, const void *hits, uint32_t n, void *counts, void *geom);
+int ls_occupancy_grid_check(const ls_occupancy_grid_desc *grid);   /* host only, no device call: LS_OK or the refusal */
+
 /* ---- clouds in a driver's own PointCloud2 layout.  Every frame call above leaves the same fixed cloud: 32-byte XYZIR records
  * (XYZIRBytes.cpp:24-40), compacted, and next to it the ls_hit records (and, for beams, the echo words).  What a driver publishes
  * differs: Velodyne's 22-byte XYZIRT with a per-point `time` (what LIO-SAM, FAST-LIO and KISS-ICP deskew by), Ouster's organized

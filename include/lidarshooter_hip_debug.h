@@ -124,6 +124,17 @@ int ls_debug_motion_normal(const float n3[3], const float motion12[12], float ou
  * may be NULL: at rest, that velocity is (+0, +0, +0) -> the 32-byte record: v_s xyz, radial, v_o xyz, flags = 1 */
 int ls_debug_hit_velocity(const float cast8[8], float t, const float sensor_twist6[6], const float geom_twist6[6], float out8[8]);
 
+/* one ray of ls_occupancy_grid on the host (no device, no handle): the float32 operation sequence k_voxel_carve runs per ray
+ * (csrc/ls_voxel.h) -- the affine (sensor_to_grid3x4, or NULL), the span of the header's table, the occupied cell and the walk.
+ * ray32: a 32-byte ray record (origin xyz, tmin, direction xyz, tmax); t_end: the t of the ray's deciding record, or NaN: the ray has
+ * none (it carves only with LS_OCC_CARVE_MISSES in grid->flags).  -> cells_out[0 .. min(*n_cells, capacity)): the cells the walk
+ * visits, in order, as word-pair indices (z ny + y) nx + x -- the ray's own occupied cell among them where the walk reaches it --;
+ * *n_cells: how many it visits; *occupied_cell_out: the cell the record's point marks, or 0xFFFFFFFF.  A ray that is not walkable
+ * visits and marks nothing.  LS_ERR_INVALID_ARGUMENT for NULL grid, ray32, n_cells or occupied_cell_out, NULL cells_out with capacity
+ * > 0, a non-finite transform or a descriptor ls_occupancy_grid_check refuses; LS_ERR_OUT_OF_RANGE when *n_cells > capacity. */
+int ls_debug_voxel_walk(const ls_occupancy_grid_desc *grid, const float *sensor_to_grid3x4, const float ray32[8], float t_end,
+                        uint32_t *cells_out, uint32_t capacity, uint32_t *n_cells, uint32_t *occupied_cell_out);
+
 /* one record of ls_format_cloud on the host (no device, no handle): the operation sequence k_format_cloud runs per record
  * (csrc/ls_cloud_format.h).  point32: the 32-byte point, or NULL (zeros: the format names none of its fields); hit: the ls_hit, or
  * NULL -- the miss cell of cell_ray (an organized cloud's cell nobody fills); echo_word; col_time_value / chan_time_value: the

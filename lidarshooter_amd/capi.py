@@ -61,6 +61,7 @@ SYMBOLS = (
     "ls_hit_attributes_moving", "ls_hit_attributes_moving_host", "ls_apply_return_model_moving", "ls_apply_return_model_moving_host",
     "ls_hit_velocities", "ls_hit_velocities_host", "ls_twist_table_constant",
     "ls_object_labels", "ls_object_labels_host",
+    "ls_occupancy_grid", "ls_occupancy_grid_host", "ls_occupancy_grid_check",
     "ls_format_cloud", "ls_format_cloud_host", "ls_cloud_format_check", "ls_cloud_format_from_point_fields", "ls_column_times",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
@@ -69,7 +70,7 @@ DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_s
                  "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model", "ls_debug_sweep_ray",
                  "ls_debug_beam_ray", "ls_debug_beam_echoes", "ls_debug_beam_model_check",
                  "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check", "ls_debug_motion_ray",
-                 "ls_debug_motion_normal", "ls_debug_hit_velocity", "ls_debug_format_record",
+                 "ls_debug_motion_normal", "ls_debug_hit_velocity", "ls_debug_format_record", "ls_debug_voxel_walk",
                  "ls_debug_band_map_fit", "ls_debug_band_guess", "ls_debug_tracer_band_map",
                  "ls_debug_force_group_cull", "ls_debug_download_cull", "ls_debug_cull_survivors", "ls_debug_cull_tables", "ls_debug_chan_query")
 # ls_debug_cull_survivors: which k_cull instantiation ran
@@ -202,6 +203,26 @@ HIT_VELOCITY_DTYPE = np.dtype([("v_s", "<f4", 3), ("radial", "<f4"), ("v_o", "<f
 LS_LABEL_FOOTPRINT = 1
 OBJECT_LABEL_DTYPE = np.dtype([("n_hits", "<u4"), ("n_alone", "<u4"), ("t_min", "<f4"), ("ray_min", "<u4"), ("t_max", "<f4"), ("ray_max", "<u4"),
                                ("lo", "<f4", 3), ("hi", "<f4", 3), ("flags", "<u4"), ("reserved", "<u4", 3)])
+# ls_occupancy_grid: per cell of a voxel grid the rays that crossed it (n_free) and the returns that fell in it (n_occ)
+LS_OCC_CARVE_MISSES, LS_OCC_ACCUMULATE = 1, 2
+OCCUPANCY_MAX_DIM, OCCUPANCY_MAX_CELLS = 2048, 1 << 27
+
+
+class OccupancyGridDesc(C.Structure):
+    """ls_occupancy_grid_desc (48 bytes): cell (x, y, z) of the grid is word pair (z * ny + y) * nx + x"""
+    _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float), ("dims", C.c_uint32 * 3), ("flags", C.c_uint32),
+                ("min_range", C.c_float), ("max_range", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+    @classmethod
+    def make(cls, origin, cell, dims, flags=0, min_range=0.0, max_range=1e4):
+        d = cls()
+        d.origin = (C.c_float * 3)(*[float(x) for x in origin])
+        d.cell = float(cell)
+        d.dims = (C.c_uint32 * 3)(*[int(x) for x in dims])
+        d.flags, d.min_range, d.max_range = int(flags), float(min_range), float(max_range)
+        return d
+
+
 NODE_DTYPE = np.dtype([("llo", "<f4", 3), ("left", "<u4"), ("lhi", "<f4", 3), ("right", "<u4"),
                        ("rlo", "<f4", 3), ("pad0", "<u4"), ("rhi", "<f4", 3), ("pad1", "<u4")])
 LEAF_BIT = 0x80000000
@@ -348,6 +369,10 @@ def load() -> C.CDLL:
     L.ls_twist_table_constant.argtypes = [f32p, f32p, f32p, C.c_double, C.c_double, u32, f32p]
     L.ls_object_labels.argtypes = [vp, vp, u32, vp, u32, vp, vp, u32, vp, u32]
     L.ls_object_labels_host.argtypes = [vp, u32, vp, u32, vp, u32, vp, u32]
+    L.ls_occupancy_grid.argtypes = [vp, vp, C.POINTER(OccupancyGridDesc), vp, vp, u32, vp, vp, u32, vp, vp]
+    L.ls_occupancy_grid_host.argtypes = [vp, C.POINTER(OccupancyGridDesc), vp, vp, u32, vp, u32, vp, vp]
+    L.ls_occupancy_grid_check.argtypes = [C.POINTER(OccupancyGridDesc)]
+    L.ls_debug_voxel_walk.argtypes = [C.POINTER(OccupancyGridDesc), vp, vp, C.c_float, vp, u32, u32p, u32p]
     L.ls_debug_hit_velocity.argtypes = [f32p, C.c_float, f32p, f32p, f32p]
     L.ls_format_cloud.argtypes = [vp, vp, C.POINTER(CloudFormat), vp, vp, vp, vp, u32, vp, vp, vp]
     L.ls_format_cloud_host.argtypes = [vp, C.POINTER(CloudFormat), vp, vp, vp, u32, vp, vp, vp]
@@ -873,6 +898,52 @@ class Tracer:
         rc = self.L.ls_object_labels(self.h, stream, LS_LABEL_FOOTPRINT if footprint else 0, d_rays or None, n_rays, d_hits or None, d_count or None,
                                      n, d_labels or None, n_labels)
         return -1 if rc == -1 else int(self._check(rc, "ls_object_labels"))
+
+    @staticmethod
+    def _grid_shape(desc: OccupancyGridDesc):
+        """(nz, ny, nx) of a descriptor the library would not refuse for its size (the arrays are made before the call)"""
+        nx, ny, nz = (int(x) for x in desc.dims)
+        if not (0 < nx <= OCCUPANCY_MAX_DIM and 0 < ny <= OCCUPANCY_MAX_DIM and 0 < nz <= OCCUPANCY_MAX_DIM and nx * ny * nz <= OCCUPANCY_MAX_CELLS):
+            raise LidarShooterHipError("ls_occupancy_grid: a grid dimension of 0 or above 2048, or more than 2^27 cells")
+        return nz, ny, nx
+
+    def occupancyGrid(self, desc: OccupancyGridDesc, hits, rays=None, sensor_to_grid=None, into=None):
+        """The voxel grid a frame carves (ls_occupancy_grid_host): `hits` and `rays` as objectLabels takes them (`hits` may be None or
+        empty: every ray is a miss), `sensor_to_grid` None or 12 floats (row-major 3 x 4), `into` None or a pair (counts, geom) to
+        accumulate on -- the call then runs with LS_OCC_ACCUMULATE and returns new arrays.
+        -> (rc, counts uint32[nz, ny, nx, 2] = {n_free, n_occ}, geom uint32[nz, ny, nx]); rc = -1 (no commit, empty scene): cleared
+        arrays (zeros and 0xFFFFFFFF)."""
+        h = self._hit_array(np.zeros(0, HIT_DTYPE) if hits is None else hits)
+        n = h.shape[0]
+        r = None if rays is None else self._ray_array(rays)
+        nz, ny, nx = self._grid_shape(desc)
+        d = OccupancyGridDesc.from_buffer_copy(desc)
+        if into is None:
+            counts, geom = np.zeros((nz, ny, nx, 2), np.uint32), np.full((nz, ny, nx), INVALID, np.uint32)
+            d.flags &= ~LS_OCC_ACCUMULATE
+        else:
+            counts = np.array(into[0], np.uint32, order="C").reshape(nz, ny, nx, 2)
+            geom = np.array(into[1], np.uint32, order="C").reshape(nz, ny, nx)
+            d.flags |= LS_OCC_ACCUMULATE
+        m = None if sensor_to_grid is None else np.ascontiguousarray(sensor_to_grid, np.float32).reshape(12)
+        rc = self.L.ls_occupancy_grid_host(self.h, C.byref(d), None if m is None else m.ctypes.data,
+                                           None if r is None else (r.ctypes.data if r.shape[0] else counts.ctypes.data), 0 if r is None else r.shape[0],
+                                           h.ctypes.data if n else None, n, counts.ctypes.data, geom.ctypes.data)
+        if rc == -1:
+            return -1, np.zeros((nz, ny, nx, 2), np.uint32), np.full((nz, ny, nx), INVALID, np.uint32)
+        self._check(rc, "ls_occupancy_grid_host")
+        return int(rc), counts, geom
+
+    def occupancyGridDevice(self, desc: OccupancyGridDesc, d_counts: int, d_geom: int = 0, d_hits: int = 0, n: int = 0, d_rays: int = 0,
+                            n_rays: int = 0, d_count: int = 0, sensor_to_grid=None, stream=None) -> int:
+        """ls_occupancy_grid on device pointers (n 16-byte ls_hit records in; nx ny nz {n_free, n_occ} pairs and, with d_geom != 0, as
+        many geom words out; d_rays = 0: the handle's sensor rays; d_count != 0: a device word, min(n, *d_count) records are
+        handled); enqueued on `stream` (a hipStream_t as an int, None: the handle's), no wait.  -> 0, or -1 on an empty /
+        uncommitted scene (nothing written)."""
+        m = None if sensor_to_grid is None else np.ascontiguousarray(sensor_to_grid, np.float32).reshape(12)
+        rc = self.L.ls_occupancy_grid(self.h, stream, C.byref(desc), None if m is None else m.ctypes.data, d_rays or None, n_rays,
+                                      d_hits or None, d_count or None, n, d_counts or None, d_geom or None)
+        return -1 if rc == -1 else int(self._check(rc, "ls_occupancy_grid"))
 
     def applyReturnModel(self, model: ReturnModel, hits, rays=None, reflectivity=None, frame_index: int = 0):
         """Sensor returns from hit records (ls_apply_return_model_host): `hits` and `rays` as hitAttributes takes them, `reflectivity`

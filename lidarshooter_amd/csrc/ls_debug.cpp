@@ -10,6 +10,7 @@
 #include "ls_velocity.h"
 #include "ls_beam.h"
 #include "ls_cloud_format.h"
+#include "ls_voxel.h"
 
 #include <algorithm>
 #include <vector>
@@ -335,6 +336,34 @@ int ls_debug_beam_sweep_check(const ls_beam_model *model, const uint32_t *weight
 }
 
 // cloud_sources, then cloud_format_record: what a lane of k_format_cloud does for its record, or for the miss cell of cell_ray
+int ls_debug_voxel_walk(const ls_occupancy_grid_desc *grid, const float *sensor_to_grid3x4, const float ray32[8], float t_end,
+                        uint32_t *cells_out, uint32_t capacity, uint32_t *n_cells, uint32_t *occupied_cell_out)
+{
+    if (!grid || !ray32 || !n_cells || !occupied_cell_out || (capacity && !cells_out)) return LS_ERR_INVALID_ARGUMENT;
+    if (ls::voxel_args_invalid(*grid, sensor_to_grid3x4) || ls::voxel_grid_out_of_range(*grid)) return LS_ERR_INVALID_ARGUMENT;
+    const ls::VoxelGrid g = ls::voxel_grid(*grid, sensor_to_grid3x4);
+    *n_cells = 0;
+    *occupied_cell_out = ls::kVoxelNone;
+    float o[3] = {ray32[0], ray32[1], ray32[2]}, d[3] = {ray32[4], ray32[5], ray32[6]};
+    const float tmin = ray32[3], tmax = ray32[7];
+    // (k_voxel_carve's test of a caller's ray)
+    if (!(std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]) && std::isfinite(d[0]) && std::isfinite(d[1]) && std::isfinite(d[2]) &&
+          (d[0] != 0.f || d[1] != 0.f || d[2] != 0.f) && tmin <= tmax))
+        return LS_OK;
+    if (g.has_xf) ls::voxel_ray_to_grid(g.xf, o, d);
+    float t0, t1;
+    bool marks;
+    const bool carve = ls::voxel_span(g, tmin, tmax, !std::isnan(t_end), t_end, &t0, &t1, &marks);
+    if (marks) *occupied_cell_out = ls::voxel_occupied_cell(g, o, d, t_end, false);
+    if (!carve) return LS_OK;
+    ls::VoxelWalk w;
+    for (ls::voxel_walk_begin(g, o, d, t0, t1, w); w.live; ls::voxel_walk_next(g, w)) {
+        if (*n_cells < capacity) cells_out[*n_cells] = ls::voxel_index(g, w);
+        ++*n_cells;
+    }
+    return *n_cells > capacity ? LS_ERR_OUT_OF_RANGE : LS_OK;
+}
+
 int ls_debug_format_record(const ls_cloud_format *fmt, const void *point32, const ls_hit *hit, uint32_t echo_word, float col_time_value,
                            float chan_time_value, uint32_t V, uint32_t H, uint32_t cell_ray, void *out_bytes)
 {

@@ -12,6 +12,7 @@
 //   ls_cloud.cpp     ls_format_cloud: the records of a frame as a cloud in a driver's own record (ls_format.hip), its format helpers
 //   ls_scan.cpp      ls_trace_scene_sweep, ls_trace_scene_beams, ls_trace_scene_sweep_moving: their scratch around the queries' walk
 //                    (ls_sweep.hip, ls_beam.hip, ls_moving.hip)
+//   ls_voxel_host.cpp ls_occupancy_grid: the voxel grid a frame's rays carve (ls_voxel.hip), its descriptor's check
 //   ls_host_pool.cpp worker threads for host-side copies, point expansion
 //   ls_debug.cpp     include/lidarshooter_hip_debug.h (tests and bench.py only)
 #pragma once
@@ -317,6 +318,8 @@ struct ls_tracer {
         // ls_object_labels: one 64-byte accumulator per geomID below n_labels (ls::LabelAcc), and the V * H records of the handle's own
         // rays for its footprint (32 bytes each) -- one call at a time, as the sweep
         lsi::DevBuf<uint8_t> label_acc, label_rays;
+        // ls_occupancy_grid: per ray the (t bits << 32) | geom key of its closest counted record (one call at a time, as the sweep)
+        lsi::DevBuf<unsigned long long> voxel_keys;
         std::vector<RayQuerySlot> built;       // per layout entry
         std::vector<int> layout_ids;           // geometry ids of the layout the slots were made for ...
         std::vector<uint32_t> layout_firsts;   // ... and their first vertex, first triangle in it
