@@ -453,7 +453,10 @@ int ls_get_visit_counts(ls_tracer *tr, uint64_t counts[4]);
 
 /* ---- ray generation on its own: LidarDevice::allRaysGPU (LidarDeviceKernels.cu:25-126).
  * Writes the shard's rays as SoA float arrays of n = ls_total_rays() entries each, in device
- * memory owned by the caller: dir_x, dir_y, dir_z (origins are all zero, LidarDevice.cpp:320). */
+ * memory owned by the caller: dir_x, dir_y, dir_z (origins are all zero, LidarDevice.cpp:320).  The kernel runs on the handle's
+ * stream, behind whatever the device's default stream held when the call was made (a fill of the new buffers, say): one event
+ * recorded there, no host wait.  As any call that touches the default stream it must not be made while the calling thread captures a
+ * stream of its own; while the handle's frame graph is open it is not ordered at all. */
 int ls_generate_rays(ls_tracer *tr, float *d_dir_x, float *d_dir_y, float *d_dir_z);
 
 /* The same kernel's two outputs in the reference's own layout (LidarDeviceKernels.cu:38-51): n = ls_total_rays() records
@@ -463,7 +466,7 @@ int ls_generate_rays(ls_tracer *tr, float *d_dir_x, float *d_dir_y, float *d_dir
  *            OptiX programs use them: tmin 0, tmax 1e16 (OptixTracerModules.cu:45-46).
  *   d_hits:  lidarshooter::Hit, 24 bytes (Hit.hpp:16-29): t f32@0 = 1e16 ("no hit yet"), normal xyz f32@4 (left alone by
  *            the reference; written as 0 here), intensity f32@16 = 64.0, ring i32@20 = the channel index.
- * Either pointer may be NULL (that output is skipped). */
+ * Either pointer may be NULL (that output is skipped).  Stream order as ls_generate_rays. */
 int ls_generate_rays_aos(ls_tracer *tr, void *d_rays, void *d_hits);
 
 /* ---- ray queries: the closest hit of each of n CALLER rays against the scene as of the last successful ls_commit_scene
@@ -1123,6 +1126,64 @@ int ls_occupancy_grid(ls_tracer *tr, void *hip_stream, const ls_occupancy_grid_d
 int ls_occupancy_grid_host(ls_tracer *tr, const ls_occupancy_grid_desc *grid, const float *sensor_to_grid3x4,
                            const void *rays, uint32_t n_rays, const void *hits, uint32_t n, void *counts, void *geom);
 int ls_occupancy_grid_check(const ls_occupancy_grid_desc *grid);   /* host only, no device call: LS_OK or the refusal */
+
+/* ---- scene grid: the COMPLETE grid next to the observed one.  ls_occupancy_grid says what a frame saw of each cell; scene
+ * completion and occupancy prediction ground truth (SemanticKITTI SSC, Occ3D, nvblox / OctoMap evaluation) also asks, whatever the
+ * sensor happened to see, whether any surface of the scene lies in the cell and whose it is.  The two grids share the cell order,
+ * so they overlay: observed and occupied, observed and free, occupied but never observed (the completion target), unknown.
+ *   grid:     the descriptor below, a host pointer, copied during the call.
+ *   sensor_to_grid3x4: exactly as ls_occupancy_grid takes it.  NULL: the grid is in the sensor frame and a vertex is what the frame's
+ *             triangle test sees, bit for bit.  Non-NULL: that vertex goes through ((m0 x + m1 y) + m2 z) + m3 per row.
+ *   d_select: NULL, or n_select bytes in device memory indexed by geomID: a geometry whose byte is 0 is left out; geom >= n_select
+ *             (or NULL) means selected.  Static scenery and moving bodies can so go into separate grids.
+ *   d_counts: nx ny nz uint32_t, 16-byte aligned: the number of triangles of the committed scene that overlap the cell; every word
+ *             is written.
+ *   d_geom:   NULL, or nx ny nz uint32_t: the lowest geomID among those triangles, 0xFFFFFFFF where there is none.
+ * The scene is what ls_hit_attributes would see: the committed layout with the geometries' current buffers and poses.  A quad is its
+ * two triangles 2q, 2q + 1, and each counts on its own.  Only the surface counts: the interior of a closed mesh is not filled.
+ * Per selected triangle (csrc/ls_scene_grid.h: float32, every operation rounded once):
+ *   1. the three vertex indices are checked against the vertex count before an address is formed from them; a triangle that fails
+ *      is skipped;
+ *   2. q_k = v_k - origin per axis, v_k the transformed vertex; a triangle with a non-finite q is skipped;
+ *   3. per axis a: lo_a = floorf(min_k q_k[a] / cell), hi_a = floorf(max_k q_k[a] / cell), compared as floats before any cast; the
+ *      triangle is skipped if hi_a < 0 or lo_a >= n_a; otherwise both are clamped to [0, n_a - 1];
+ *   4. for every cell c of the range: ctr_a = ((float)c_a + 0.5f) * cell, h = 0.5f * cell, p_k = q_k - ctr; the edges are
+ *      e0 = q1 - q0, e1 = q2 - q1, e2 = q0 - q2 (from q, not from p);
+ *   5. the cell overlaps unless one of 13 axes separates: the 3 box axes (min_k p_k[a] > h or max_k p_k[a] < -h); the 9 axes
+ *      unit_i x e_j -- for i = x the projection of vertex k is (e_y * p_k.z) - (e_z * p_k.y) and r = h * (|e_z| + |e_y|), for i = y
+ *      (e_z * p_k.x) - (e_x * p_k.z) and r = h * (|e_x| + |e_z|), for i = z (e_x * p_k.y) - (e_y * p_k.x) and r = h * (|e_y| + |e_x|);
+ *      all three vertices are projected; the axis separates if min > r or max < -r --; and the plane axis, n = cross(e0, e1) as
+ *      products and differences, d = ((n.x * p_0.x) + (n.y * p_0.y)) + (n.z * p_0.z), r = h * ((|n.x| + |n.y|) + |n.z|), which
+ *      separates if d > r or d < -r;
+ *   6. the comparisons are written so that a NaN never separates; a cell index is in range by construction;
+ *   7. an overlapping cell gets counts += 1 and, with d_geom, geom = min(geom, geomID).
+ * A cell's box is closed, but the range is floorf's: a triangle that ends on a face plane reaches the cell above that plane and
+ * touches it; one that begins on the plane does not reach the cell below.  A segment or a point needs no special case.
+ * ls_debug_scene_grid_triangle runs the same sequence on the host for one triangle.  Every value is an integer count or a minimum:
+ * the grid is the same bytes whatever the order of the device's work, from call to call.
+ * LS_ERR_INVALID_ARGUMENT before any device call, in this order: a frame graph is open; NULL grid; NULL d_counts; n_select > 0 with
+ * NULL d_select; unknown flag bits; a non-finite origin or transform; cell not finite or not > 0; misaligned pointers for the
+ * device call (counts 16 bytes, geom 4).  Then LS_ERR_OUT_OF_RANGE for a dimension of 0 or above 2048, nx ny nz above 2^27 or a
+ * non-finite origin + n cell; then the commit state as ls_occupancy_grid (-1 with no commit or an empty scene: nothing is written).
+ * ls_scene_grid_check returns the descriptor's part of this (host only, no device call).  No hierarchy is touched; stream order,
+ * the one-call-at-a-time rule and the frame graph rule are those of ls_trace_rays.
+ * Not offered: solid (interior) fill; meshes that deform during the call; a majority label per cell; a call of the ITracer adapter. */
+#define LS_SCENE_GRID_ACCUMULATE 1u   /* add to what d_counts / d_geom hold instead of clearing them first */
+
+typedef struct ls_scene_grid_desc {   /* 32 bytes, no pointers */
+    float    origin[3];   /* minimum corner of cell (0,0,0), in the grid's frame */
+    float    cell;        /* edge of a cubic cell */
+    uint32_t dims[3];     /* nx, ny, nz; cell (x,y,z) is word (z*ny + y)*nx + x -- ls_occupancy_grid's order, so the two grids overlay */
+    uint32_t flags;
+} ls_scene_grid_desc;
+
+int ls_scene_grid(ls_tracer *tr, void *hip_stream, const ls_scene_grid_desc *grid, const float *sensor_to_grid3x4,
+                  const uint8_t *d_select, uint32_t n_select, void *d_counts, void *d_geom);
+/* The same with host memory (pageable, any alignment) in and out, on the handle's stream; returns when counts and geom are filled.
+ * With LS_SCENE_GRID_ACCUMULATE the two arrays travel to the device first. */
+int ls_scene_grid_host(ls_tracer *tr, const ls_scene_grid_desc *grid, const float *sensor_to_grid3x4,
+                       const uint8_t *select, uint32_t n_select, void *counts, void *geom);
+int ls_scene_grid_check(const ls_scene_grid_desc *grid);   /* host only, no device call: LS_OK or the refusal */
 
 /* ---- clouds in a driver's own PointCloud2 layout.  Every frame call above leaves the same fixed cloud: 32-byte XYZIR records
  * (XYZIRBytes.cpp:24-40), compacted, and next to it the ls_hit records (and, for beams, the echo words).  What a driver publishes

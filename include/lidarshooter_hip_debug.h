@@ -135,6 +135,18 @@ int ls_debug_hit_velocity(const float cast8[8], float t, const float sensor_twis
 int ls_debug_voxel_walk(const ls_occupancy_grid_desc *grid, const float *sensor_to_grid3x4, const float ray32[8], float t_end,
                         uint32_t *cells_out, uint32_t capacity, uint32_t *n_cells, uint32_t *occupied_cell_out);
 
+/* one triangle of ls_scene_grid on the host (no device, no handle): the float32 operation sequence k_scene_grid_small and
+ * k_scene_grid_big run per triangle and per cell (csrc/ls_scene_grid.h) -- q = v - origin, the clamped cell range and the 13-axis
+ * test of every cell of it.  tri9: the three vertices, already in the grid's frame.  -> cells_out[0 .. min(*n_cells, capacity)): the
+ * overlapping cells as word indices (z ny + y) nx + x, ascending; *n_cells: how many there are.  A triangle with a non-finite q or
+ * outside the grid has none.  LS_ERR_INVALID_ARGUMENT for NULL grid, tri9 or n_cells, NULL cells_out with capacity > 0 or a
+ * descriptor ls_scene_grid_check refuses; LS_ERR_OUT_OF_RANGE when *n_cells > capacity. */
+int ls_debug_scene_grid_triangle(const ls_scene_grid_desc *grid, const float tri9[9], uint32_t *cells_out, uint32_t capacity,
+                                 uint32_t *n_cells);
+/* how many triangles the handle's last ls_scene_grid call queued for k_scene_grid_big: the count word of the queue, read back after a
+ * wait for the handle's stream (a call on a caller's stream must have been waited for by the caller); 0 before the first call */
+int ls_debug_scene_grid_queued(ls_tracer *tr, uint32_t *n_queued);
+
 /* one record of ls_format_cloud on the host (no device, no handle): the operation sequence k_format_cloud runs per record
  * (csrc/ls_cloud_format.h).  point32: the 32-byte point, or NULL (zeros: the format names none of its fields); hit: the ls_hit, or
  * NULL -- the miss cell of cell_ray (an organized cloud's cell nobody fills); echo_word; col_time_value / chan_time_value: the

@@ -62,6 +62,7 @@ SYMBOLS = (
     "ls_hit_velocities", "ls_hit_velocities_host", "ls_twist_table_constant",
     "ls_object_labels", "ls_object_labels_host",
     "ls_occupancy_grid", "ls_occupancy_grid_host", "ls_occupancy_grid_check",
+    "ls_scene_grid", "ls_scene_grid_host", "ls_scene_grid_check",
     "ls_format_cloud", "ls_format_cloud_host", "ls_cloud_format_check", "ls_cloud_format_from_point_fields", "ls_column_times",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
@@ -70,7 +71,7 @@ DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_s
                  "ls_debug_hit_attributes_on_triangle", "ls_debug_philox4x32", "ls_debug_return_model", "ls_debug_sweep_ray",
                  "ls_debug_beam_ray", "ls_debug_beam_echoes", "ls_debug_beam_model_check",
                  "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check", "ls_debug_motion_ray",
-                 "ls_debug_motion_normal", "ls_debug_hit_velocity", "ls_debug_format_record", "ls_debug_voxel_walk",
+                 "ls_debug_motion_normal", "ls_debug_hit_velocity", "ls_debug_format_record", "ls_debug_voxel_walk", "ls_debug_scene_grid_triangle", "ls_debug_scene_grid_queued",
                  "ls_debug_band_map_fit", "ls_debug_band_guess", "ls_debug_tracer_band_map",
                  "ls_debug_force_group_cull", "ls_debug_download_cull", "ls_debug_cull_survivors", "ls_debug_cull_tables", "ls_debug_chan_query")
 # ls_debug_cull_survivors: which k_cull instantiation ran
@@ -220,6 +221,24 @@ class OccupancyGridDesc(C.Structure):
         d.cell = float(cell)
         d.dims = (C.c_uint32 * 3)(*[int(x) for x in dims])
         d.flags, d.min_range, d.max_range = int(flags), float(min_range), float(max_range)
+        return d
+
+
+# ls_scene_grid: per cell of a voxel grid the triangles of the committed scene that overlap it
+LS_SCENE_GRID_ACCUMULATE = 1
+
+
+class SceneGridDesc(C.Structure):
+    """ls_scene_grid_desc (32 bytes): cell (x, y, z) of the grid is word (z * ny + y) * nx + x, ls_occupancy_grid's order"""
+    _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float), ("dims", C.c_uint32 * 3), ("flags", C.c_uint32)]
+
+    @classmethod
+    def make(cls, origin, cell, dims, flags=0):
+        d = cls()
+        d.origin = (C.c_float * 3)(*[float(x) for x in origin])
+        d.cell = float(cell)
+        d.dims = (C.c_uint32 * 3)(*[int(x) for x in dims])
+        d.flags = int(flags)
         return d
 
 
@@ -373,6 +392,11 @@ def load() -> C.CDLL:
     L.ls_occupancy_grid_host.argtypes = [vp, C.POINTER(OccupancyGridDesc), vp, vp, u32, vp, u32, vp, vp]
     L.ls_occupancy_grid_check.argtypes = [C.POINTER(OccupancyGridDesc)]
     L.ls_debug_voxel_walk.argtypes = [C.POINTER(OccupancyGridDesc), vp, vp, C.c_float, vp, u32, u32p, u32p]
+    L.ls_scene_grid.argtypes = [vp, vp, C.POINTER(SceneGridDesc), vp, vp, u32, vp, vp]
+    L.ls_scene_grid_host.argtypes = [vp, C.POINTER(SceneGridDesc), vp, vp, u32, vp, vp]
+    L.ls_scene_grid_check.argtypes = [C.POINTER(SceneGridDesc)]
+    L.ls_debug_scene_grid_triangle.argtypes = [C.POINTER(SceneGridDesc), vp, vp, u32, u32p]
+    L.ls_debug_scene_grid_queued.argtypes = [vp, u32p]
     L.ls_debug_hit_velocity.argtypes = [f32p, C.c_float, f32p, f32p, f32p]
     L.ls_format_cloud.argtypes = [vp, vp, C.POINTER(CloudFormat), vp, vp, vp, vp, u32, vp, vp, vp]
     L.ls_format_cloud_host.argtypes = [vp, C.POINTER(CloudFormat), vp, vp, vp, u32, vp, vp, vp]
@@ -900,11 +924,12 @@ class Tracer:
         return -1 if rc == -1 else int(self._check(rc, "ls_object_labels"))
 
     @staticmethod
-    def _grid_shape(desc: OccupancyGridDesc):
-        """(nz, ny, nx) of a descriptor the library would not refuse for its size (the arrays are made before the call)"""
+    def _grid_shape(desc, call="ls_occupancy_grid"):
+        """(nz, ny, nx) of a descriptor (an OccupancyGridDesc or a SceneGridDesc) the library would not refuse for its size (the arrays
+        are made before the call)"""
         nx, ny, nz = (int(x) for x in desc.dims)
         if not (0 < nx <= OCCUPANCY_MAX_DIM and 0 < ny <= OCCUPANCY_MAX_DIM and 0 < nz <= OCCUPANCY_MAX_DIM and nx * ny * nz <= OCCUPANCY_MAX_CELLS):
-            raise LidarShooterHipError("ls_occupancy_grid: a grid dimension of 0 or above 2048, or more than 2^27 cells")
+            raise LidarShooterHipError(call + ": a grid dimension of 0 or above 2048, or more than 2^27 cells")
         return nz, ny, nx
 
     def occupancyGrid(self, desc: OccupancyGridDesc, hits, rays=None, sensor_to_grid=None, into=None):
@@ -944,6 +969,41 @@ class Tracer:
         rc = self.L.ls_occupancy_grid(self.h, stream, C.byref(desc), None if m is None else m.ctypes.data, d_rays or None, n_rays,
                                       d_hits or None, d_count or None, n, d_counts or None, d_geom or None)
         return -1 if rc == -1 else int(self._check(rc, "ls_occupancy_grid"))
+
+    def sceneGrid(self, desc: SceneGridDesc, select=None, sensor_to_grid=None, into=None):
+        """The voxels the committed scene's surface occupies (ls_scene_grid_host): `select` None or bytes indexed by geomID (0: the
+        geometry is left out), `sensor_to_grid` None or 12 floats (row-major 3 x 4), `into` None or a pair (counts, geom) to accumulate
+        on -- the call then runs with LS_SCENE_GRID_ACCUMULATE and returns new arrays.
+        -> (rc, counts uint32[nz, ny, nx], geom uint32[nz, ny, nx]); rc = -1 (no commit, empty scene): cleared arrays (zeros and
+        0xFFFFFFFF)."""
+        nz, ny, nx = self._grid_shape(desc, "ls_scene_grid")
+        d = SceneGridDesc.from_buffer_copy(desc)
+        if into is None:
+            counts, geom = np.zeros((nz, ny, nx), np.uint32), np.full((nz, ny, nx), INVALID, np.uint32)
+            d.flags &= ~LS_SCENE_GRID_ACCUMULATE
+        else:
+            counts = np.array(into[0], np.uint32, order="C").reshape(nz, ny, nx)
+            geom = np.array(into[1], np.uint32, order="C").reshape(nz, ny, nx)
+            d.flags |= LS_SCENE_GRID_ACCUMULATE
+        m = None if sensor_to_grid is None else np.ascontiguousarray(sensor_to_grid, np.float32).reshape(12)
+        sel = None if select is None else np.ascontiguousarray(select, np.uint8).reshape(-1)
+        rc = self.L.ls_scene_grid_host(self.h, C.byref(d), None if m is None else m.ctypes.data,
+                                       sel.ctypes.data if sel is not None and sel.size else None, 0 if sel is None else sel.size,
+                                       counts.ctypes.data, geom.ctypes.data)
+        if rc == -1:
+            return -1, np.zeros((nz, ny, nx), np.uint32), np.full((nz, ny, nx), INVALID, np.uint32)
+        self._check(rc, "ls_scene_grid_host")
+        return int(rc), counts, geom
+
+    def sceneGridDevice(self, desc: SceneGridDesc, d_counts: int, d_geom: int = 0, d_select: int = 0, n_select: int = 0, sensor_to_grid=None,
+                        stream=None) -> int:
+        """ls_scene_grid on device pointers (nx ny nz count words and, with d_geom != 0, as many geom words out; d_select = 0: every
+        geometry); enqueued on `stream` (a hipStream_t as an int, None: the handle's), no wait.  -> 0, or -1 on an empty /
+        uncommitted scene (nothing written)."""
+        m = None if sensor_to_grid is None else np.ascontiguousarray(sensor_to_grid, np.float32).reshape(12)
+        rc = self.L.ls_scene_grid(self.h, stream, C.byref(desc), None if m is None else m.ctypes.data, d_select or None, n_select,
+                                  d_counts or None, d_geom or None)
+        return -1 if rc == -1 else int(self._check(rc, "ls_scene_grid"))
 
     def applyReturnModel(self, model: ReturnModel, hits, rays=None, reflectivity=None, frame_index: int = 0):
         """Sensor returns from hit records (ls_apply_return_model_host): `hits` and `rays` as hitAttributes takes them, `reflectivity`

@@ -307,6 +307,7 @@ void hit_attr_release(ls_tracer *tr)
     a.table.release();
     a.motion.release();
     a.twist.release();
+    a.tri_first.release();
     release(a.park); release(a.block_counts);
 }
 

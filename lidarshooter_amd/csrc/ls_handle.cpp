@@ -659,10 +659,28 @@ int ls_expand_gathered_hits(ls_tracer *tr, const void *d_gathered, uint32_t worl
     return ls_expand_gathered_hits_on(tr, nullptr, d_gathered, world, capacity, d_points32, d_hits, d_n_points);
 }
 
+// The ray generators write into buffers the caller has just made, and a caller that fills a new allocation does so on the device's
+// default stream (a framework's zero-fill of a new tensor, a hipMemset): the handle's stream is non-blocking, so nothing orders that
+// fill before the kernel, and a fill that lands late wipes the rays.  These two calls are not part of a frame: they put the
+// handle's stream behind what the default stream holds at the time of the call (one event, no host wait).  Not while a frame
+// graph is open: the capture forbids work on the default stream.
+static int order_after_default_stream(ls_tracer *tr)
+{
+    if (tr->fg_open) return LS_OK;
+    hipEvent_t ev = nullptr;
+    LS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, nullptr);
+    if (e == hipSuccess) e = hipStreamWaitEvent(tr->stream, ev, 0);
+    (void)hipEventDestroy(ev);   // (released once the wait has passed it)
+    LS_HIP(e);
+    return LS_OK;
+}
+
 int ls_generate_rays(ls_tracer *tr, float *dx, float *dy, float *dz)
 {
     LS_ENTER(tr);
     if (!dx || !dy || !dz) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null output");
+    if (const int rc = order_after_default_stream(tr)) return rc;
     ls::launch_raygen(tr->stream, tables(tr), dx, dy, dz);
     LS_HIP(hipGetLastError());
     return LS_OK;
@@ -672,6 +690,7 @@ int ls_generate_rays_aos(ls_tracer *tr, void *d_rays, void *d_hits)
 {
     LS_ENTER(tr);
     if (!d_rays && !d_hits) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null outputs");
+    if (const int rc = order_after_default_stream(tr)) return rc;
     ls::launch_raygen_aos(tr->stream, tables(tr), d_rays, d_hits);
     LS_HIP(hipGetLastError());
     return LS_OK;

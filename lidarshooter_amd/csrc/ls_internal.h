@@ -13,6 +13,7 @@
 //   ls_scan.cpp      ls_trace_scene_sweep, ls_trace_scene_beams, ls_trace_scene_sweep_moving: their scratch around the queries' walk
 //                    (ls_sweep.hip, ls_beam.hip, ls_moving.hip)
 //   ls_voxel_host.cpp ls_occupancy_grid: the voxel grid a frame's rays carve (ls_voxel.hip), its descriptor's check
+//   ls_scene_grid_host.cpp ls_scene_grid: the voxels the committed scene's surface occupies (ls_scene_grid.hip), its descriptor's check
 //   ls_host_pool.cpp worker threads for host-side copies, point expansion
 //   ls_debug.cpp     include/lidarshooter_hip_debug.h (tests and bench.py only)
 #pragma once
@@ -320,6 +321,9 @@ struct ls_tracer {
         lsi::DevBuf<uint8_t> label_acc, label_rays;
         // ls_occupancy_grid: per ray the (t bits << 32) | geom key of its closest counted record (one call at a time, as the sweep)
         lsi::DevBuf<unsigned long long> voxel_keys;
+        // ls_scene_grid: the count word of k_scene_grid_big's queue (entry 0) and 8 bytes (geom, triangle) per triangle of the scene
+        // behind it (one call at a time, as the sweep)
+        lsi::DevBuf<uint2> scene_queue;
         std::vector<RayQuerySlot> built;       // per layout entry
         std::vector<int> layout_ids;           // geometry ids of the layout the slots were made for ...
         std::vector<uint32_t> layout_firsts;   // ... and their first vertex, first triangle in it
@@ -340,6 +344,8 @@ struct ls_tracer {
         lsi::StagedTable<const float *> motion;
         // ls_hit_velocities: a twist-table pointer per geomID next to them (nullptr: at rest), as long as they are
         lsi::StagedTable<const float *> twist;
+        // ls_scene_grid: where each geomID's triangles start in the flat triangle index, and the total behind them
+        lsi::StagedTable<uint32_t> tri_first;
     } ha;
     uint64_t upload_seq = 0;
 
