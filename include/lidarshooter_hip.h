@@ -1185,6 +1185,63 @@ int ls_scene_grid_host(ls_tracer *tr, const ls_scene_grid_desc *grid, const floa
                        const uint8_t *select, uint32_t n_select, void *counts, void *geom);
 int ls_scene_grid_check(const ls_scene_grid_desc *grid);   /* host only, no device call: LS_OK or the refusal */
 
+/* ---- scene distance grid: the third grid of the family, over the same cells.  The consumers of ls_scene_grid (nvblox / voxblox TSDF
+ * and ESDF evaluation, implicit-surface and occupancy networks trained on truncated distance targets, clearance maps for planning)
+ * also ask how far each cell's CENTRE is from the nearest surface of the scene, up to a truncation distance.  Every triangle visits
+ * only the cells within that distance of it (a scatter: no hierarchy is built or walked), and the result is a minimum, the same bytes
+ * in any order.
+ *   grid:     the descriptor below, a host pointer, copied during the call.
+ *   sensor_to_grid3x4, d_select / n_select, the scene that is seen and the quad rule: word for word ls_scene_grid's -- the committed
+ *             layout with the geometries' current buffers and poses; a quad is its triangles 2q and 2q + 1.
+ *   d_cells:  nx ny nz records of 8 bytes, 16-byte aligned: geom u32 @0, dist f32 @4; read as one little-endian 64-bit word a record
+ *             is (bits(dist) << 32) | geom.  A cell with no surface within trunc of its centre holds {0xFFFFFFFF, +inf} =
+ *             0x7F800000FFFFFFFF.  Every record is written.
+ * Per selected triangle (csrc/ls_distance_grid.h: float32, every operation rounded once, no fmaf), v_k its vertices in the grid's
+ * frame exactly as ls_scene_grid obtains them (indices checked before an address is formed, the frame's transform, the call's):
+ *   1. q_k = v_k - origin per axis; a triangle with a non-finite q is skipped;
+ *   2. per axis a: lo_a = floorf((min_k q_k[a] - trunc) / cell), hi_a = floorf((max_k q_k[a] + trunc) / cell), compared as floats
+ *      before any cast; the triangle is skipped if hi_a < 0 or lo_a >= n_a; otherwise both are clamped to [0, n_a - 1].  In exact
+ *      arithmetic the first cell left out on either side has its centre at least half a cell beyond trunc from the triangle's box,
+ *      so the range is part of the definition without changing the answer for any sane input (|q| / cell < 2^20);
+ *   3. per cell c of the range: ctr_a = ((float)c_a + 0.5f) * cell; closest_on_triangle(ctr, q_0, q_1, q_2) of csrc/ls_closest.h
+ *      (ls_closest_points' sequence) gives d2; the pair counts iff d2 is finite and dist = sqrtf(d2) <= trunc.  A triangle without
+ *      area never counts (closest_on_triangle gives it d2 = +inf) -- unlike ls_scene_grid, where a segment marks cells;
+ *   4. a counting pair sends (bits(dist) << 32) | geomID to its cell, whose word becomes the 64-bit unsigned minimum: the smallest
+ *      rounded distance, and the lowest geomID among the triangles that attain it.  sqrtf is correctly rounded and monotone, so this
+ *      is the sqrtf of the smallest d2.  Every value is a minimum: the same bytes whatever the order of the device's work;
+ *   5. with LS_DIST_GRID_ACCUMULATE the words d_cells holds are the starting values, compared as 64-bit words whatever their bits:
+ *      the minimum over several poses, or over static scenery and moving bodies selected into one grid.
+ * ls_debug_distance_grid_triangle runs steps 1 to 3 on the host for one triangle.
+ * LS_ERR_INVALID_ARGUMENT before any device call, in this order: a frame graph is open; NULL grid; NULL d_cells; n_select > 0 with NULL
+ * d_select; unknown flag bits or a non-zero reserved word; a non-finite origin or transform; cell not finite or not > 0; trunc not
+ * finite or < 0; a misaligned d_cells (16 bytes; the device call only).  Then LS_ERR_OUT_OF_RANGE for a dimension of 0 or above 2048,
+ * nx ny nz above 2^27, a non-finite origin + n cell, or trunc > 32.0f * cell (the float32 product): the band bounds the work per
+ * triangle.  Then the commit state as ls_scene_grid (-1 with no commit or an empty scene: nothing is written).
+ * ls_scene_distance_grid_check returns the descriptor's part of this (host only, no device call).  No hierarchy is touched and
+ * LS_INFO_RAY_QUERY_BUILT is left as it is; stream order, the one-call-at-a-time rule and the frame graph rule are those of
+ * ls_trace_rays.
+ * Not offered: a sign (the scene's meshes need not be closed, and a face-normal sign is wrong at edges); the nearest primitive or
+ * point (ls_closest_points gives them per point); distances beyond trunc; non-cubic cells; meshes that deform during the call; a call
+ * of the ITracer adapter. */
+#define LS_DIST_GRID_ACCUMULATE 1u   /* take the minimum with what d_cells holds instead of clearing it first */
+
+typedef struct ls_distance_grid_desc {   /* 48 bytes, no pointers */
+    float    origin[3];   /* minimum corner of cell (0,0,0), in the grid's frame */
+    float    cell;        /* edge of a cubic cell */
+    uint32_t dims[3];     /* nx, ny, nz; cell (x,y,z) is record (z*ny + y)*nx + x: the order of the other two grids */
+    uint32_t flags;
+    float    trunc;       /* truncation distance, finite, >= 0 */
+    uint32_t reserved[3]; /* 0 */
+} ls_distance_grid_desc;
+
+int ls_scene_distance_grid(ls_tracer *tr, void *hip_stream, const ls_distance_grid_desc *grid, const float *sensor_to_grid3x4,
+                           const uint8_t *d_select, uint32_t n_select, void *d_cells);
+/* The same with host memory (pageable, any alignment) in and out, on the handle's stream; returns when cells is filled.  With
+ * LS_DIST_GRID_ACCUMULATE the array travels to the device first. */
+int ls_scene_distance_grid_host(ls_tracer *tr, const ls_distance_grid_desc *grid, const float *sensor_to_grid3x4,
+                                const uint8_t *select, uint32_t n_select, void *cells);
+int ls_scene_distance_grid_check(const ls_distance_grid_desc *grid);   /* host only, no device call */
+
 /* ---- clouds in a driver's own PointCloud2 layout.  Every frame call above leaves the same fixed cloud: 32-byte XYZIR records
  * (XYZIRBytes.cpp:24-40), compacted, and next to it the ls_hit records (and, for beams, the echo words).  What a driver publishes
  * differs: Velodyne's 22-byte XYZIRT with a per-point `time` (what LIO-SAM, FAST-LIO and KISS-ICP deskew by), Ouster's organized

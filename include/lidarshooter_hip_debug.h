@@ -147,6 +147,20 @@ int ls_debug_scene_grid_triangle(const ls_scene_grid_desc *grid, const float tri
  * wait for the handle's stream (a call on a caller's stream must have been waited for by the caller); 0 before the first call */
 int ls_debug_scene_grid_queued(ls_tracer *tr, uint32_t *n_queued);
 
+/* one triangle of ls_scene_distance_grid on the host (no device, no handle): the float32 operation sequence k_distance_grid_small and
+ * k_distance_grid_big run per triangle and per cell (csrc/ls_distance_grid.h) -- q = v - origin, the widened, clamped cell range and
+ * closest_on_triangle from every cell centre of it.  tri9: the three vertices, already in the grid's frame.  -> cells_out / dist_out
+ * [0 .. min(*n_cells, capacity)): the cells that count (dist <= trunc) as record indices (z ny + y) nx + x, ascending, and their dist;
+ * *n_cells: how many there are.  A triangle with a non-finite q, without area or farther than trunc from the grid has none.
+ * LS_ERR_INVALID_ARGUMENT for NULL grid, tri9 or n_cells, NULL cells_out or dist_out with capacity > 0 or a descriptor
+ * ls_scene_distance_grid_check refuses; LS_ERR_OUT_OF_RANGE when *n_cells > capacity. */
+int ls_debug_distance_grid_triangle(const ls_distance_grid_desc *grid, const float tri9[9], uint32_t *cells_out, float *dist_out,
+                                    uint32_t capacity, uint32_t *n_cells);
+/* how many triangles the handle's last ls_scene_distance_grid call queued for k_distance_grid_big: the count word of the queue, read
+ * back after a wait for the handle's stream (a call on a caller's stream must have been waited for by the caller); 0 before the
+ * first call */
+int ls_debug_distance_grid_queued(ls_tracer *tr, uint32_t *n_queued);
+
 /* one record of ls_format_cloud on the host (no device, no handle): the operation sequence k_format_cloud runs per record
  * (csrc/ls_cloud_format.h).  point32: the 32-byte point, or NULL (zeros: the format names none of its fields); hit: the ls_hit, or
  * NULL -- the miss cell of cell_ray (an organized cloud's cell nobody fills); echo_word; col_time_value / chan_time_value: the

@@ -63,6 +63,7 @@ SYMBOLS = (
     "ls_object_labels", "ls_object_labels_host",
     "ls_occupancy_grid", "ls_occupancy_grid_host", "ls_occupancy_grid_check",
     "ls_scene_grid", "ls_scene_grid_host", "ls_scene_grid_check",
+    "ls_scene_distance_grid", "ls_scene_distance_grid_host", "ls_scene_distance_grid_check",
     "ls_format_cloud", "ls_format_cloud_host", "ls_cloud_format_check", "ls_cloud_format_from_point_fields", "ls_column_times",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
@@ -72,6 +73,7 @@ DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_s
                  "ls_debug_beam_ray", "ls_debug_beam_echoes", "ls_debug_beam_model_check",
                  "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check", "ls_debug_motion_ray",
                  "ls_debug_motion_normal", "ls_debug_hit_velocity", "ls_debug_format_record", "ls_debug_voxel_walk", "ls_debug_scene_grid_triangle", "ls_debug_scene_grid_queued",
+                 "ls_debug_distance_grid_triangle", "ls_debug_distance_grid_queued",
                  "ls_debug_band_map_fit", "ls_debug_band_guess", "ls_debug_tracer_band_map",
                  "ls_debug_force_group_cull", "ls_debug_download_cull", "ls_debug_cull_survivors", "ls_debug_cull_tables", "ls_debug_chan_query")
 # ls_debug_cull_survivors: which k_cull instantiation ran
@@ -242,6 +244,28 @@ class SceneGridDesc(C.Structure):
         return d
 
 
+# ls_scene_distance_grid: per cell of a voxel grid the distance from its centre to the nearest surface of the committed scene within
+# trunc; a record read as one 64-bit word is (bits(dist) << 32) | geom, and a cell with no surface in reach holds DIST_GRID_REST
+LS_DIST_GRID_ACCUMULATE = 1
+DIST_GRID_DTYPE = np.dtype([("geom", "<u4"), ("dist", "<f4")])
+DIST_GRID_REST = 0x7F800000FFFFFFFF
+
+
+class DistanceGridDesc(C.Structure):
+    """ls_distance_grid_desc (48 bytes): cell (x, y, z) of the grid is record (z * ny + y) * nx + x, the other two grids' order"""
+    _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float), ("dims", C.c_uint32 * 3), ("flags", C.c_uint32), ("trunc", C.c_float),
+                ("reserved", C.c_uint32 * 3)]
+
+    @classmethod
+    def make(cls, origin, cell, dims, flags=0, trunc=0.0):
+        d = cls()
+        d.origin = (C.c_float * 3)(*[float(x) for x in origin])
+        d.cell = float(cell)
+        d.dims = (C.c_uint32 * 3)(*[int(x) for x in dims])
+        d.flags, d.trunc = int(flags), float(trunc)
+        return d
+
+
 NODE_DTYPE = np.dtype([("llo", "<f4", 3), ("left", "<u4"), ("lhi", "<f4", 3), ("right", "<u4"),
                        ("rlo", "<f4", 3), ("pad0", "<u4"), ("rhi", "<f4", 3), ("pad1", "<u4")])
 LEAF_BIT = 0x80000000
@@ -397,6 +421,11 @@ def load() -> C.CDLL:
     L.ls_scene_grid_check.argtypes = [C.POINTER(SceneGridDesc)]
     L.ls_debug_scene_grid_triangle.argtypes = [C.POINTER(SceneGridDesc), vp, vp, u32, u32p]
     L.ls_debug_scene_grid_queued.argtypes = [vp, u32p]
+    L.ls_scene_distance_grid.argtypes = [vp, vp, C.POINTER(DistanceGridDesc), vp, vp, u32, vp]
+    L.ls_scene_distance_grid_host.argtypes = [vp, C.POINTER(DistanceGridDesc), vp, vp, u32, vp]
+    L.ls_scene_distance_grid_check.argtypes = [C.POINTER(DistanceGridDesc)]
+    L.ls_debug_distance_grid_triangle.argtypes = [C.POINTER(DistanceGridDesc), vp, vp, vp, u32, u32p]
+    L.ls_debug_distance_grid_queued.argtypes = [vp, u32p]
     L.ls_debug_hit_velocity.argtypes = [f32p, C.c_float, f32p, f32p, f32p]
     L.ls_format_cloud.argtypes = [vp, vp, C.POINTER(CloudFormat), vp, vp, vp, vp, u32, vp, vp, vp]
     L.ls_format_cloud_host.argtypes = [vp, C.POINTER(CloudFormat), vp, vp, vp, u32, vp, vp, vp]
@@ -1004,6 +1033,42 @@ class Tracer:
         rc = self.L.ls_scene_grid(self.h, stream, C.byref(desc), None if m is None else m.ctypes.data, d_select or None, n_select,
                                   d_counts or None, d_geom or None)
         return -1 if rc == -1 else int(self._check(rc, "ls_scene_grid"))
+
+    def sceneDistanceGrid(self, desc: DistanceGridDesc, select=None, sensor_to_grid=None, into=None):
+        """The truncated distance field of the committed scene (ls_scene_distance_grid_host): `select` and `sensor_to_grid` as sceneGrid
+        takes them, `into` None or a pair (dist, geom) to take the minimum with -- the call then runs with LS_DIST_GRID_ACCUMULATE
+        and returns new arrays.
+        -> (rc, dist float32[nz, ny, nx], geom uint32[nz, ny, nx]); a cell with no surface within trunc of its centre: +inf and
+        0xFFFFFFFF; rc = -1 (no commit, empty scene): every cell so."""
+        nz, ny, nx = self._grid_shape(desc, "ls_scene_distance_grid")
+        d = DistanceGridDesc.from_buffer_copy(desc)
+        cells = np.zeros((nz, ny, nx), DIST_GRID_DTYPE)
+        if into is None:
+            cells.view(np.uint64)[...] = DIST_GRID_REST
+            d.flags &= ~LS_DIST_GRID_ACCUMULATE
+        else:
+            cells["dist"] = np.asarray(into[0], np.float32).reshape(nz, ny, nx)
+            cells["geom"] = np.asarray(into[1], np.uint32).reshape(nz, ny, nx)
+            d.flags |= LS_DIST_GRID_ACCUMULATE
+        m = None if sensor_to_grid is None else np.ascontiguousarray(sensor_to_grid, np.float32).reshape(12)
+        sel = None if select is None else np.ascontiguousarray(select, np.uint8).reshape(-1)
+        rc = self.L.ls_scene_distance_grid_host(self.h, C.byref(d), None if m is None else m.ctypes.data,
+                                                sel.ctypes.data if sel is not None and sel.size else None, 0 if sel is None else sel.size,
+                                                cells.ctypes.data)
+        if rc == -1:
+            return -1, np.full((nz, ny, nx), np.inf, np.float32), np.full((nz, ny, nx), INVALID, np.uint32)
+        self._check(rc, "ls_scene_distance_grid_host")
+        return int(rc), np.ascontiguousarray(cells["dist"]), np.ascontiguousarray(cells["geom"])
+
+    def sceneDistanceGridDevice(self, desc: DistanceGridDesc, d_cells: int, d_select: int = 0, n_select: int = 0, sensor_to_grid=None,
+                                stream=None) -> int:
+        """ls_scene_distance_grid on device pointers (nx ny nz 8-byte records {geom, dist} out, 16-byte aligned; d_select = 0: every
+        geometry); enqueued on `stream` (a hipStream_t as an int, None: the handle's), no wait.  -> 0, or -1 on an empty /
+        uncommitted scene (nothing written)."""
+        m = None if sensor_to_grid is None else np.ascontiguousarray(sensor_to_grid, np.float32).reshape(12)
+        rc = self.L.ls_scene_distance_grid(self.h, stream, C.byref(desc), None if m is None else m.ctypes.data, d_select or None, n_select,
+                                           d_cells or None)
+        return -1 if rc == -1 else int(self._check(rc, "ls_scene_distance_grid"))
 
     def applyReturnModel(self, model: ReturnModel, hits, rays=None, reflectivity=None, frame_index: int = 0):
         """Sensor returns from hit records (ls_apply_return_model_host): `hits` and `rays` as hitAttributes takes them, `reflectivity`

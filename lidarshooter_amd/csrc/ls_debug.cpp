@@ -12,6 +12,7 @@
 #include "ls_cloud_format.h"
 #include "ls_voxel.h"
 #include "ls_scene_grid.h"
+#include "ls_distance_grid.h"
 
 #include <algorithm>
 #include <vector>
@@ -392,6 +393,41 @@ int ls_debug_scene_grid_queued(ls_tracer *tr, uint32_t *n_queued)
     if (!tr->rq.scene_queue.p) return LS_OK;
     LS_HIP(hipStreamSynchronize(tr->stream));
     LS_HIP(hipMemcpy(n_queued, tr->rq.scene_queue.p, 4, hipMemcpyDeviceToHost));
+    return LS_OK;
+}
+
+int ls_debug_distance_grid_triangle(const ls_distance_grid_desc *grid, const float tri9[9], uint32_t *cells_out, float *dist_out, uint32_t capacity,
+                                    uint32_t *n_cells)
+{
+    if (!grid || !tri9 || !n_cells || (capacity && (!cells_out || !dist_out))) return LS_ERR_INVALID_ARGUMENT;
+    if (ls_scene_distance_grid_check(grid) != LS_OK) return LS_ERR_INVALID_ARGUMENT;
+    const ls::DistGrid g = ls::dist_grid(*grid, nullptr);
+    *n_cells = 0;
+    ls::DistTri t;
+    ls::SceneRange r;
+    if (!ls::dist_tri_setup(g, tri9[0], tri9[1], tri9[2], tri9[3], tri9[4], tri9[5], tri9[6], tri9[7], tri9[8], t, r)) return LS_OK;
+    for (int cz = r.loz; cz <= r.hiz; ++cz)
+        for (int cy = r.loy; cy <= r.hiy; ++cy)
+            for (int cx = r.lox; cx <= r.hix; ++cx) {
+                float dist;
+                if (!ls::dist_cell(t, g.trunc, g.cell, cx, cy, cz, &dist)) continue;
+                if (*n_cells < capacity) {
+                    cells_out[*n_cells] = ls::dist_cell_index(g, cx, cy, cz);
+                    dist_out[*n_cells] = dist;
+                }
+                ++*n_cells;
+            }
+    return *n_cells > capacity ? LS_ERR_OUT_OF_RANGE : LS_OK;
+}
+
+int ls_debug_distance_grid_queued(ls_tracer *tr, uint32_t *n_queued)
+{
+    LS_ENTER(tr);
+    if (!n_queued) return fail(tr, LS_ERR_INVALID_ARGUMENT, "null output");
+    *n_queued = 0;
+    if (!tr->rq.dist_queue.p) return LS_OK;
+    LS_HIP(hipStreamSynchronize(tr->stream));
+    LS_HIP(hipMemcpy(n_queued, tr->rq.dist_queue.p, 4, hipMemcpyDeviceToHost));
     return LS_OK;
 }
 

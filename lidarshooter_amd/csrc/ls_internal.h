@@ -14,6 +14,7 @@
 //                    (ls_sweep.hip, ls_beam.hip, ls_moving.hip)
 //   ls_voxel_host.cpp ls_occupancy_grid: the voxel grid a frame's rays carve (ls_voxel.hip), its descriptor's check
 //   ls_scene_grid_host.cpp ls_scene_grid: the voxels the committed scene's surface occupies (ls_scene_grid.hip), its descriptor's check
+//   ls_distance_grid_host.cpp ls_scene_distance_grid: the truncated distance from every cell centre to that surface (ls_distance_grid.hip)
 //   ls_host_pool.cpp worker threads for host-side copies, point expansion
 //   ls_debug.cpp     include/lidarshooter_hip_debug.h (tests and bench.py only)
 #pragma once
@@ -324,6 +325,8 @@ struct ls_tracer {
         // ls_scene_grid: the count word of k_scene_grid_big's queue (entry 0) and 8 bytes (geom, triangle) per triangle of the scene
         // behind it (one call at a time, as the sweep)
         lsi::DevBuf<uint2> scene_queue;
+        // ls_scene_distance_grid: the same for k_distance_grid_big's queue (one call at a time, as the sweep)
+        lsi::DevBuf<uint2> dist_queue;
         std::vector<RayQuerySlot> built;       // per layout entry
         std::vector<int> layout_ids;           // geometry ids of the layout the slots were made for ...
         std::vector<uint32_t> layout_firsts;   // ... and their first vertex, first triangle in it
