@@ -1242,6 +1242,77 @@ int ls_scene_distance_grid_host(ls_tracer *tr, const ls_distance_grid_desc *grid
                                 const uint8_t *select, uint32_t n_select, void *cells);
 int ls_scene_distance_grid_check(const ls_distance_grid_desc *grid);   /* host only, no device call */
 
+/* ---- surface samples: the POINT form of the scene's ground truth, next to the three grids.  Points spread uniformly, by area, over
+ * the whole surface of the selected geometries, whatever the sensor saw: the complete cloud beside a frame's partial one (PCN / KITTI
+ * completion pairs, point-based scene completion), oriented on-surface samples (point, unit normal, owner) for implicit-surface
+ * training beside ls_scene_distance_grid's band, the mesh side of Chamfer distance and F-score (ls_closest_points gives cloud -> mesh;
+ * mesh -> cloud needs points drawn from the mesh), and the surface area of a selection, from which a sample density is chosen.  The
+ * vertices are the frame's, bit for bit, and the same call gives the same bytes on every run.
+ *   desc:     the descriptor below, a host pointer, copied during the call.
+ *   sensor_to_out3x4, d_select / n_select, the scene that is seen and the quad rule: word for word ls_scene_grid's -- NULL: the output
+ *             frame is the sensor frame and a vertex is what the frame's triangle test sees; non-NULL: that vertex goes through
+ *             ((m0 x + m1 y) + m2 z) + m3 per row; a geometry whose select byte is 0 is left out, geom >= n_select (or NULL) means
+ *             selected; the committed layout with the geometries' current buffers and poses; a quad is its triangles 2q and 2q + 1 of
+ *             the geometry's triangle list.  The three vertex indices of a triangle are checked against the vertex count before an
+ *             address is formed from them.
+ *   d_samples: n_samples records of 48 bytes, 16-byte aligned; may be NULL only when n_samples == 0.  Every record is written:
+ *             px, py, pz  f32 @0   the point, in the output frame
+ *             geom        u32 @12  geomID; 0xFFFFFFFF in an invalid record
+ *             nx, ny, nz  f32 @16  unit normal along (v1 - v0) x (v2 - v0)
+ *             prim        u32 @28  as ls_hit.prim (a quad's index for a quad geometry)
+ *             u, v        f32 @32  point = (1 - u - v) v0 + u v1 + v v2
+ *             tri         u32 @40  triangle inside the geometry, as ls_hit_attributes' tri
+ *             flags       u32 @44  bit 0 = valid
+ *   d_info:   NULL, or 16 bytes, 8-byte aligned: weight_total u64 @0 (W below), exponent i32 @8 (e below), n_weighted u32 @12 (the
+ *             triangles with weight > 0).  The selection's area is weight_total * 2^exponent, up to the weights' flooring (less than
+ *             n_weighted * 2^exponent below the sum of the float32 areas).  n_samples == 0 with d_info asks for a selection's area.
+ * The definition (csrc/ls_surface_sample.h: float32, every operation rounded once, no fmaf; the integers exact).  Per triangle i of
+ * the flat index -- the geometries in ascending geomID, each one's triangles in order --, q_k its vertices in the output frame:
+ *   1. weight 0 for an unselected geometry, a free id, an index >= the vertex count, a non-finite coordinate;
+ *   2. N = (q1 - q0) x (q2 - q0) as products and differences (ls_scene_grid's form: the normal is NOT bit-equal to ls_hit_attributes',
+ *      which fuses); m = max |N_k|, weight 0 unless m > 0 and finite; g = N / m; len = sqrtf((gx gx + gy gy) + gz gz); n = g / len;
+ *      the area a = (0.5f * m) * len, weight 0 unless a is finite;
+ *   3. A = max_i a_i (a maximum of bit patterns: it has no order).  A == 0: W = 0, e = 0.  Otherwise A = f 2^E with f in [1, 2)
+ *      (subnormals included) and e = E - 30;
+ *   4. w_i = (uint64)floorf(ldexpf(a_i, -e)): the largest weight lies in [2^30, 2^31), and a triangle 2^30 times smaller than the
+ *      largest has weight 0 and is never drawn;
+ *   5. P[0] = 0, P[i + 1] = P[i] + w_i, W = P[n_tris] (< 2^63): integer sums, the same bytes in any order;
+ *   6. sample j: Philox4x32-10 with key (seed, 1) and counter (lo32(j), hi32(j), 0, 0) gives x0 .. x3.  Only j keys the sample: a call
+ *      for a slice [first_sample, first_sample + n_samples) draws what the full call draws there;
+ *   7. r = (x0 << 32) | x1, T = hi64(r W); the triangle is the largest i < n_tris with P[i] <= T: one of weight > 0;
+ *   8. alpha = x2 >> 8, beta = x3 >> 8; if alpha + beta > 2^24 (integers): alpha = 2^24 - alpha, beta = 2^24 - beta; gamma = 2^24 -
+ *      alpha - beta; u = (float)alpha 2^-24, v = (float)beta 2^-24, w = (float)gamma 2^-24, all exact;
+ *   9. p = ((w q0 + u q1) + v q2) per axis; the record gets p, n, the ids, u, v and flags 1;
+ *  10. W == 0 (nothing selected, or nothing with an area): every record is zeros with geom = 0xFFFFFFFF and flags 0; LS_OK.
+ * ls_debug_surface_weights, ls_debug_surface_pick and ls_debug_surface_point run steps 2 to 5, 7 and 8 to 9 on the host.
+ * LS_ERR_INVALID_ARGUMENT before any device call, nothing written, in this order: a frame graph is open; NULL desc; NULL d_samples
+ * with n_samples > 0; n_select > 0 with NULL d_select; unknown flag bits or a non-zero reserved word; a non-finite transform;
+ * misaligned pointers for the device call (samples 16 bytes, info 8).  Then the commit state as ls_scene_grid (-1 with no commit or
+ * an empty scene: nothing is written).  LS_ERR_OUT_OF_RANGE for a scene of more than 2^32 - 256 triangles.
+ * ls_surface_sample_check returns the descriptor's part of this (host only, no device call).  No hierarchy is touched and
+ * LS_INFO_RAY_QUERY_BUILT is left as it is; stream order, the one-call-at-a-time rule and the frame graph rule are those of
+ * ls_trace_rays.  The call keeps 12 bytes per triangle of the scene on the handle (released with the query state), and every call
+ * makes the weights anew: 2^20 samples in slices of 2^10 pay for them 2^10 times.
+ * Not offered: sampling restricted to a box or to the visible surface; per-vertex attribute interpolation (the record carries u, v
+ * and tri for it); an offset along the normal (the caller has n); stratified or blue-noise sets; meshes that deform during the call;
+ * a call of the ITracer adapter. */
+#define LS_SURFACE_SAMPLE_FLAGS 0u        /* no flag yet: any bit set is refused */
+
+typedef struct ls_surface_sample_desc {   /* 32 bytes, no pointers */
+    uint64_t first_sample;   /* index j of the first sample of this call */
+    uint32_t n_samples;      /* samples j = first_sample .. first_sample + n_samples - 1 (mod 2^64); 0 is allowed */
+    uint32_t seed;
+    uint32_t flags;
+    uint32_t reserved[3];    /* 0 */
+} ls_surface_sample_desc;
+
+int ls_sample_surface(ls_tracer *tr, void *hip_stream, const ls_surface_sample_desc *desc, const float *sensor_to_out3x4,
+                      const uint8_t *d_select, uint32_t n_select, void *d_samples, void *d_info);
+/* The same with host memory (pageable, any alignment) in and out, on the handle's stream; returns when samples and info are filled. */
+int ls_sample_surface_host(ls_tracer *tr, const ls_surface_sample_desc *desc, const float *sensor_to_out3x4,
+                           const uint8_t *select, uint32_t n_select, void *samples, void *info);
+int ls_surface_sample_check(const ls_surface_sample_desc *desc);   /* host only, no device call */
+
 /* ---- clouds in a driver's own PointCloud2 layout.  Every frame call above leaves the same fixed cloud: 32-byte XYZIR records
  * (XYZIRBytes.cpp:24-40), compacted, and next to it the ls_hit records (and, for beams, the echo words).  What a driver publishes
  * differs: Velodyne's 22-byte XYZIRT with a per-point `time` (what LIO-SAM, FAST-LIO and KISS-ICP deskew by), Ouster's organized

@@ -161,6 +161,17 @@ int ls_debug_distance_grid_triangle(const ls_distance_grid_desc *grid, const flo
  * first call */
 int ls_debug_distance_grid_queued(ls_tracer *tr, uint32_t *n_queued);
 
+/* ls_sample_surface on the host (no device, no handle): the float32 / integer sequences its kernels run (csrc/ls_surface_sample.h).
+ * ls_debug_surface_weights: steps 2 to 5 over n triangles already in the output frame (tris9: 9 floats each; every one counts as
+ * selected) -> area_out[n] (+0 for a triangle of weight 0), weight_out[n], prefix_out[n + 1] and the 16 bytes of the call's info
+ * (weight_total, exponent, n_weighted); any output may be NULL.
+ * ls_debug_surface_pick: step 7 for the 64-bit word r64 over a prefix of n + 1 entries -> *tri_out, or 0xFFFFFFFF when prefix[n] is 0.
+ * ls_debug_surface_point: steps 2, 8 and 9 for one triangle and the words x2, x3 -> out9 = the point, the unit normal, u, v, w.
+ * LS_ERR_INVALID_ARGUMENT for a NULL input or result pointer. */
+int ls_debug_surface_weights(const float *tris9, uint32_t n, float *area_out, uint64_t *weight_out, uint64_t *prefix_out, void *info_out);
+int ls_debug_surface_pick(const uint64_t *prefix, uint32_t n, uint64_t r64, uint32_t *tri_out);
+int ls_debug_surface_point(const float tri9[9], uint32_t x2, uint32_t x3, float out9[9]);
+
 /* one record of ls_format_cloud on the host (no device, no handle): the operation sequence k_format_cloud runs per record
  * (csrc/ls_cloud_format.h).  point32: the 32-byte point, or NULL (zeros: the format names none of its fields); hit: the ls_hit, or
  * NULL -- the miss cell of cell_ray (an organized cloud's cell nobody fills); echo_word; col_time_value / chan_time_value: the

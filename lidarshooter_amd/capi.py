@@ -64,6 +64,7 @@ SYMBOLS = (
     "ls_occupancy_grid", "ls_occupancy_grid_host", "ls_occupancy_grid_check",
     "ls_scene_grid", "ls_scene_grid_host", "ls_scene_grid_check",
     "ls_scene_distance_grid", "ls_scene_distance_grid_host", "ls_scene_distance_grid_check",
+    "ls_sample_surface", "ls_sample_surface_host", "ls_surface_sample_check",
     "ls_format_cloud", "ls_format_cloud_host", "ls_cloud_format_check", "ls_cloud_format_from_point_fields", "ls_column_times",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
@@ -74,6 +75,7 @@ DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_s
                  "ls_debug_beam_sweep_ray", "ls_debug_beam_echoes_weighted", "ls_debug_beam_sweep_check", "ls_debug_motion_ray",
                  "ls_debug_motion_normal", "ls_debug_hit_velocity", "ls_debug_format_record", "ls_debug_voxel_walk", "ls_debug_scene_grid_triangle", "ls_debug_scene_grid_queued",
                  "ls_debug_distance_grid_triangle", "ls_debug_distance_grid_queued",
+                 "ls_debug_surface_weights", "ls_debug_surface_pick", "ls_debug_surface_point",
                  "ls_debug_band_map_fit", "ls_debug_band_guess", "ls_debug_tracer_band_map",
                  "ls_debug_force_group_cull", "ls_debug_download_cull", "ls_debug_cull_survivors", "ls_debug_cull_tables", "ls_debug_chan_query")
 # ls_debug_cull_survivors: which k_cull instantiation ran
@@ -266,6 +268,24 @@ class DistanceGridDesc(C.Structure):
         return d
 
 
+# ls_sample_surface: points drawn from the surface of the committed scene in proportion to area; the call's info says what the
+# weights add up to: the selection's area is weight_total * 2 ** exponent, up to the weights' flooring
+SURFACE_SAMPLE_DTYPE = np.dtype([("p", "<f4", 3), ("geom", "<u4"), ("n", "<f4", 3), ("prim", "<u4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4"),
+                                 ("flags", "<u4")])
+SURFACE_INFO_DTYPE = np.dtype([("weight_total", "<u8"), ("exponent", "<i4"), ("n_weighted", "<u4")])
+
+
+class SurfaceSampleDesc(C.Structure):
+    """ls_surface_sample_desc (32 bytes): samples first_sample .. first_sample + n_samples - 1 of the sequence `seed` names"""
+    _fields_ = [("first_sample", C.c_uint64), ("n_samples", C.c_uint32), ("seed", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+    @classmethod
+    def make(cls, n_samples, seed=0, first_sample=0, flags=0):
+        d = cls()
+        d.first_sample, d.n_samples, d.seed, d.flags = int(first_sample) & 0xFFFFFFFFFFFFFFFF, int(n_samples), int(seed) & 0xFFFFFFFF, int(flags)
+        return d
+
+
 NODE_DTYPE = np.dtype([("llo", "<f4", 3), ("left", "<u4"), ("lhi", "<f4", 3), ("right", "<u4"),
                        ("rlo", "<f4", 3), ("pad0", "<u4"), ("rhi", "<f4", 3), ("pad1", "<u4")])
 LEAF_BIT = 0x80000000
@@ -426,6 +446,12 @@ def load() -> C.CDLL:
     L.ls_scene_distance_grid_check.argtypes = [C.POINTER(DistanceGridDesc)]
     L.ls_debug_distance_grid_triangle.argtypes = [C.POINTER(DistanceGridDesc), vp, vp, vp, u32, u32p]
     L.ls_debug_distance_grid_queued.argtypes = [vp, u32p]
+    L.ls_sample_surface.argtypes = [vp, vp, C.POINTER(SurfaceSampleDesc), vp, vp, u32, vp, vp]
+    L.ls_sample_surface_host.argtypes = [vp, C.POINTER(SurfaceSampleDesc), vp, vp, u32, vp, vp]
+    L.ls_surface_sample_check.argtypes = [C.POINTER(SurfaceSampleDesc)]
+    L.ls_debug_surface_weights.argtypes = [vp, u32, vp, vp, vp, vp]
+    L.ls_debug_surface_pick.argtypes = [vp, u32, C.c_uint64, u32p]
+    L.ls_debug_surface_point.argtypes = [vp, u32, u32, vp]
     L.ls_debug_hit_velocity.argtypes = [f32p, C.c_float, f32p, f32p, f32p]
     L.ls_format_cloud.argtypes = [vp, vp, C.POINTER(CloudFormat), vp, vp, vp, vp, u32, vp, vp, vp]
     L.ls_format_cloud_host.argtypes = [vp, C.POINTER(CloudFormat), vp, vp, vp, u32, vp, vp, vp]
@@ -1069,6 +1095,40 @@ class Tracer:
         rc = self.L.ls_scene_distance_grid(self.h, stream, C.byref(desc), None if m is None else m.ctypes.data, d_select or None, n_select,
                                            d_cells or None)
         return -1 if rc == -1 else int(self._check(rc, "ls_scene_distance_grid"))
+
+    @staticmethod
+    def emptySurfaceSamples(n: int):
+        """n invalid records: zeros with geom = 0xFFFFFFFF"""
+        out = np.zeros(n, SURFACE_SAMPLE_DTYPE)
+        out["geom"] = INVALID
+        return out
+
+    def sampleSurface(self, desc: SurfaceSampleDesc, select=None, sensor_to_out=None):
+        """Points drawn from the surface of the committed scene in proportion to area (ls_sample_surface_host): `select` None or bytes
+        indexed by geomID (0: the geometry is left out), `sensor_to_out` None or 12 floats (row-major 3 x 4).
+        -> (rc, samples SURFACE_SAMPLE_DTYPE[n_samples], info SURFACE_INFO_DTYPE[()]); rc = -1 (no commit, empty scene): invalid
+        records and a zero info."""
+        n = int(desc.n_samples)
+        samples, info = np.zeros(n, SURFACE_SAMPLE_DTYPE), np.zeros(1, SURFACE_INFO_DTYPE)
+        m = None if sensor_to_out is None else np.ascontiguousarray(sensor_to_out, np.float32).reshape(12)
+        sel = None if select is None else np.ascontiguousarray(select, np.uint8).reshape(-1)
+        rc = self.L.ls_sample_surface_host(self.h, C.byref(desc), None if m is None else m.ctypes.data,
+                                           sel.ctypes.data if sel is not None and sel.size else None, 0 if sel is None else sel.size,
+                                           samples.ctypes.data if n else None, info.ctypes.data)
+        if rc == -1:
+            return -1, self.emptySurfaceSamples(n), np.zeros(1, SURFACE_INFO_DTYPE)[0]
+        self._check(rc, "ls_sample_surface_host")
+        return int(rc), samples, info[0]
+
+    def sampleSurfaceDevice(self, desc: SurfaceSampleDesc, d_samples: int, d_info: int = 0, d_select: int = 0, n_select: int = 0,
+                            sensor_to_out=None, stream=None) -> int:
+        """ls_sample_surface on device pointers (n_samples 48-byte records out, 16-byte aligned, and, with d_info != 0, the 16 bytes of
+        the info; d_select = 0: every geometry); enqueued on `stream` (a hipStream_t as an int, None: the handle's), no wait.  -> 0,
+        or -1 on an empty / uncommitted scene (nothing written)."""
+        m = None if sensor_to_out is None else np.ascontiguousarray(sensor_to_out, np.float32).reshape(12)
+        rc = self.L.ls_sample_surface(self.h, stream, C.byref(desc), None if m is None else m.ctypes.data, d_select or None, n_select,
+                                      d_samples or None, d_info or None)
+        return -1 if rc == -1 else int(self._check(rc, "ls_sample_surface"))
 
     def applyReturnModel(self, model: ReturnModel, hits, rays=None, reflectivity=None, frame_index: int = 0):
         """Sensor returns from hit records (ls_apply_return_model_host): `hits` and `rays` as hitAttributes takes them, `reflectivity`

@@ -13,6 +13,7 @@
 #include "ls_voxel.h"
 #include "ls_scene_grid.h"
 #include "ls_distance_grid.h"
+#include "ls_surface_sample.h"
 
 #include <algorithm>
 #include <vector>
@@ -428,6 +429,56 @@ int ls_debug_distance_grid_queued(ls_tracer *tr, uint32_t *n_queued)
     if (!tr->rq.dist_queue.p) return LS_OK;
     LS_HIP(hipStreamSynchronize(tr->stream));
     LS_HIP(hipMemcpy(n_queued, tr->rq.dist_queue.p, 4, hipMemcpyDeviceToHost));
+    return LS_OK;
+}
+
+int ls_debug_surface_weights(const float *tris9, uint32_t n, float *area_out, uint64_t *weight_out, uint64_t *prefix_out, void *info_out)
+{
+    if (n && !tris9) return LS_ERR_INVALID_ARGUMENT;
+    std::vector<float> area(n);
+    uint32_t top = 0u;
+    float normal[3];
+    for (uint32_t i = 0; i < n; ++i) {
+        area[i] = ls::surface_tri_area(tris9 + 9 * (size_t)i, normal);
+        uint32_t bits;
+        std::memcpy(&bits, &area[i], 4);
+        top = std::max(top, bits);
+    }
+    const int e = ls::surface_exponent(top);
+    uint64_t sum = 0;
+    uint32_t weighted = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t w = ls::surface_weight(area[i], e);
+        if (area_out) area_out[i] = area[i];
+        if (weight_out) weight_out[i] = w;
+        if (prefix_out) prefix_out[i] = sum;
+        sum += w;
+        weighted += w != 0;
+    }
+    if (prefix_out) prefix_out[n] = sum;
+    if (info_out) {
+        const int32_t e32 = e;
+        std::memcpy(info_out, &sum, 8);
+        std::memcpy(static_cast<uint8_t *>(info_out) + 8, &e32, 4);
+        std::memcpy(static_cast<uint8_t *>(info_out) + 12, &weighted, 4);
+    }
+    return LS_OK;
+}
+
+int ls_debug_surface_pick(const uint64_t *prefix, uint32_t n, uint64_t r64, uint32_t *tri_out)
+{
+    if (!prefix || !tri_out) return LS_ERR_INVALID_ARGUMENT;
+    const uint64_t W = prefix[n];
+    *tri_out = W ? ls::surface_bisect(prefix, 0u, n, ls::surface_mulhi(r64, W)) : 0xFFFFFFFFu;
+    return LS_OK;
+}
+
+int ls_debug_surface_point(const float tri9[9], uint32_t x2, uint32_t x3, float out9[9])
+{
+    if (!tri9 || !out9) return LS_ERR_INVALID_ARGUMENT;
+    ls::surface_tri_area(tri9, out9 + 3);
+    ls::surface_bary(x2, x3, &out9[6], &out9[7], &out9[8]);
+    ls::surface_point(tri9, out9[6], out9[7], out9[8], out9);
     return LS_OK;
 }
 

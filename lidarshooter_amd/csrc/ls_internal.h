@@ -15,6 +15,7 @@
 //   ls_voxel_host.cpp ls_occupancy_grid: the voxel grid a frame's rays carve (ls_voxel.hip), its descriptor's check
 //   ls_scene_grid_host.cpp ls_scene_grid: the voxels the committed scene's surface occupies (ls_scene_grid.hip), its descriptor's check
 //   ls_distance_grid_host.cpp ls_scene_distance_grid: the truncated distance from every cell centre to that surface (ls_distance_grid.hip)
+//   ls_surface_sample_host.cpp ls_sample_surface: points drawn from that surface in proportion to area (ls_surface_sample.hip)
 //   ls_host_pool.cpp worker threads for host-side copies, point expansion
 //   ls_debug.cpp     include/lidarshooter_hip_debug.h (tests and bench.py only)
 #pragma once
@@ -327,6 +328,10 @@ struct ls_tracer {
         lsi::DevBuf<uint2> scene_queue;
         // ls_scene_distance_grid: the same for k_distance_grid_big's queue (one call at a time, as the sweep)
         lsi::DevBuf<uint2> dist_queue;
+        // ls_sample_surface: the bits of the largest area (entry 0) and of every triangle's behind it; the weights' exclusive prefix
+        // P[0 .. n_tris] and, behind it, a pair {sum, count} per 256 triangles (one call at a time, as the sweep)
+        lsi::DevBuf<uint32_t> surface_area;
+        lsi::DevBuf<uint64_t> surface_prefix;
         std::vector<RayQuerySlot> built;       // per layout entry
         std::vector<int> layout_ids;           // geometry ids of the layout the slots were made for ...
         std::vector<uint32_t> layout_firsts;   // ... and their first vertex, first triangle in it
