@@ -20,9 +20,9 @@
 
 #include "../../include/lidarshooter_hip.h"
 #include "ls_closest.h"
+#include "ls_grid_box.h"
 #include "ls_kernels.h"
 #include "ls_scene_grid.h"
-#include "ls_voxel.h"
 
 #if defined(__HIPCC__)
 #define LS_DGRID_HD __host__ __device__ __forceinline__
@@ -48,29 +48,19 @@ struct DistGrid {
     float xf[12];   // sensor -> grid, row-major 3 x 4 (read only with has_xf)
 };
 
-// the grid's box as ls_occupancy_grid describes one: the limits and the checks of ls_voxel.h apply to it as they stand
-inline ls_occupancy_grid_desc dist_grid_as_voxel(const ls_distance_grid_desc &g)
-{
-    ls_occupancy_grid_desc v{};
-    for (int a = 0; a < 3; ++a) { v.origin[a] = g.origin[a]; v.dims[a] = g.dims[a]; }
-    v.cell = g.cell;
-    v.max_range = 1.0f;
-    return v;
-}
-
 // What the call refuses of a descriptor and a transform (nullptr: none), in the header's order, as two steps -- the device entry
 // point's alignment test stands between them: the message of an LS_ERR_INVALID_ARGUMENT, then that of an LS_ERR_OUT_OF_RANGE
 inline const char *dist_grid_args_invalid(const ls_distance_grid_desc &g, const float *xf)
 {
     if ((g.flags & ~kDistGridFlags) || g.reserved[0] || g.reserved[1] || g.reserved[2]) return "unknown flags or non-zero reserved words";
-    if (const char *why = voxel_args_invalid(dist_grid_as_voxel(g), xf)) return why;   // the origin, the transform, the cell
+    if (const char *why = grid_box_invalid(g.origin, g.cell, xf)) return why;
     if (!isfinite(g.trunc) || !(g.trunc >= 0.0f)) return "trunc is not finite or negative";
     return nullptr;
 }
 
 inline const char *dist_grid_out_of_range(const ls_distance_grid_desc &g)
 {
-    if (const char *why = voxel_grid_out_of_range(dist_grid_as_voxel(g))) return why;
+    if (const char *why = grid_box_out_of_range(g.origin, g.dims, g.cell)) return why;
     if (g.trunc > kDistGridMaxBand * g.cell) return "trunc above 32 cells";
     return nullptr;
 }
@@ -78,10 +68,8 @@ inline const char *dist_grid_out_of_range(const ls_distance_grid_desc &g)
 inline DistGrid dist_grid(const ls_distance_grid_desc &g, const float *sensor_to_grid3x4)
 {
     DistGrid v{};
-    for (int a = 0; a < 3; ++a) { v.origin[a] = g.origin[a]; v.n[a] = g.dims[a]; }
-    v.cell = g.cell; v.flags = g.flags; v.trunc = g.trunc;
-    v.has_xf = sensor_to_grid3x4 ? 1u : 0u;
-    for (int k = 0; k < 12; ++k) v.xf[k] = sensor_to_grid3x4 ? sensor_to_grid3x4[k] : 0.0f;
+    grid_set_box(v, g, sensor_to_grid3x4);
+    v.flags = g.flags; v.trunc = g.trunc;
     return v;
 }
 
@@ -126,10 +114,7 @@ LS_DGRID_HD bool dist_cell(const DistTri &t, float trunc, float cell, int cx, in
     return *dist <= trunc;
 }
 
-LS_DGRID_HD uint32_t dist_cell_index(const DistGrid &g, int cx, int cy, int cz)
-{
-    return ((uint32_t)cz * g.n[1] + (uint32_t)cy) * g.n[0] + (uint32_t)cx;
-}
+LS_DGRID_HD uint32_t dist_cell_index(const DistGrid &g, int cx, int cy, int cz) { return grid_cell_index(g.n, cx, cy, cz); }
 
 // step 4: what a counting pair sends to its cell.  dist >= 0: its bits ascend with it
 LS_DGRID_HD unsigned long long dist_key(uint32_t dist_bits, uint32_t geom) { return ((unsigned long long)dist_bits << 32) | geom; }

@@ -3,8 +3,8 @@
 // geomID among the triangles that attain it.
 //
 //   k_distance_grid_clear   every record to {0xFFFFFFFF, +inf} (unless the call accumulates) and the queue's count word to zero;
-//   k_distance_grid_small   one WAVE per triangle of the scene: the triangle, its vertices through the frame's transform
-//                           (xform_vertex) and the call's, and its widened, clamped cell range (ls_distance_grid.h) are uniform
+//   k_distance_grid_small   one WAVE per triangle of the scene's flat index: the triangle, its vertices (ls_scene_tris.h)
+//                           and its widened, clamped cell range (ls_distance_grid.h) are uniform
 //                           over the wave; a range of at most `small` cells is worked off by the wave, its 64 lanes striding over
 //                           the cells; a larger one is appended to a queue -- one atomicAdd per wave;
 //   k_distance_grid_big     the queued triangles, on k_scene_grid_big's fixed launch: one to 32 blocks per entry, as many as the
@@ -16,7 +16,7 @@
 // clamped integer range, at most 2^27 cells; the big launch is a fixed grid whatever the queue holds; no workgroup waits for
 // another: a launch ends whatever the vertices hold.
 #include "ls_distance_grid.h"
-#include "ls_device.h"
+#include "ls_scene_tris.h"
 
 namespace ls {
 
@@ -33,22 +33,12 @@ __global__ __launch_bounds__(kBlock) void k_distance_grid_clear(unsigned long lo
         cells[2u * i] = kDistGridRest;
 }
 
-// Triangle `tri` of geometry `geom` (both in range of the table) in the grid's frame: k_scene_grid_small's loader.  The three
-// indices are checked against the vertex count before an address is formed from them.  false: no such geometry, an index out of
-// range, a non-finite vertex or a band outside the grid
+// Triangle `tri` of geometry ge (both in range of the table) in the grid's frame (scene_tri_vertices).  false: no such geometry,
+// an index out of range, a non-finite vertex or a band outside the grid
 __device__ __forceinline__ bool dist_tri_load(const DistGrid &g, const AttrGeom &ge, uint32_t tri, DistTri &t, SceneRange &r)
 {
-    if (ge.verts == nullptr) return false;
-    const uint32_t i0 = ge.idx[3 * (size_t)tri], i1 = ge.idx[3 * (size_t)tri + 1], i2 = ge.idx[3 * (size_t)tri + 2];
-    if (!(i0 < ge.n_verts && i1 < ge.n_verts && i2 < ge.n_verts)) return false;
-    V3 a = xform_vertex(ge.m, ge.verts + (size_t)i0 * ge.stride);
-    V3 b = xform_vertex(ge.m, ge.verts + (size_t)i1 * ge.stride);
-    V3 c = xform_vertex(ge.m, ge.verts + (size_t)i2 * ge.stride);
-    if (g.has_xf) {
-        scene_vertex_to_grid(g.xf, a.x, a.y, a.z);
-        scene_vertex_to_grid(g.xf, b.x, b.y, b.z);
-        scene_vertex_to_grid(g.xf, c.x, c.y, c.z);
-    }
+    V3 a, b, c;
+    if (!scene_tri_vertices(g.has_xf != 0u, g.xf, ge, tri, a, b, c)) return false;
     return dist_tri_setup(g, a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z, t, r);
 }
 
@@ -76,13 +66,7 @@ __global__ __launch_bounds__(kBlock) void k_distance_grid_small(DistGrid g, cons
     const uint32_t i = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)));
     const uint32_t lane = threadIdx.x & 63u;
     if (i >= n_tris) return;
-    // the geometry whose slice holds i: the last one with tri_first[gid] <= i (tri_first[0] = 0, tri_first[n_table] = n_tris > i)
-    uint32_t lo = 0u, hi = n_table;
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (tri_first[mid] <= i) lo = mid; else hi = mid;
-    }
-    const uint32_t gid = lo, tri = i - tri_first[gid];
+    const uint32_t gid = scene_geom_of(tri_first, n_table, i), tri = i - tri_first[gid];
     if (!(gid >= n_select || select[gid] != 0)) return;
     DistTri t;
     SceneRange r;

@@ -1,8 +1,8 @@
 // ls_distance_grid_host.cpp -- ls_scene_distance_grid, its host-memory variant and the descriptor's check: per cell of a voxel grid
 // the distance from its centre to the nearest surface of the committed scene within a truncation distance, and whose it is
-// (ls_distance_grid.hip; the arithmetic is ls_distance_grid.h).  The scene is the gathers' table (tables_prepare, ls_gather.cpp) with
-// ls_scene_grid's triangle offset per geomID next to it; the call's place among what the handle issues is that of every query
-// (query_enter / query_leave).  No hierarchy is touched and LS_INFO_RAY_QUERY_BUILT is left as it is.
+// (ls_distance_grid.hip; the arithmetic is ls_distance_grid.h).  The scene is the flat triangle index (scene_tris_prepare;
+// ls_scene_tris.h); the call's place among what the handle issues is that of every query (query_enter / query_leave).  No hierarchy
+// is touched and LS_INFO_RAY_QUERY_BUILT is left as it is.
 #include "ls_internal.h"
 #include "ls_distance_grid.h"
 
@@ -35,25 +35,12 @@ int dist_grid_check(ls_tracer *tr, const ls_distance_grid_desc *grid, const floa
 
 int dist_grid_issue(ls_tracer *tr, hipStream_t s, const ls::DistGrid &g, const uint8_t *d_select, uint32_t n_select, void *d_cells)
 {
-    ls_tracer::HitAttr &a = tr->ha;
+    const ls_tracer::HitAttr &a = tr->ha;
     int rc;
-    if ((rc = tables_prepare(tr, s, nullptr))) return rc;
-    const uint32_t n_table = (uint32_t)a.table.current.size();
-    // where each geomID's triangles start in the flat index (a free id: none), the total behind them: ls_scene_grid's table
-    std::vector<uint32_t> first((size_t)n_table + 1);
-    unsigned long long total = 0;
-    for (uint32_t k = 0; k < n_table; ++k) {
-        const ls::AttrGeom &e = a.table.current[k];
-        first[k] = (uint32_t)total;
-        if (e.verts) total += e.quad ? 2ull * e.n_elems : e.n_elems;
-    }
-    if (total > 0xFFFFFFFFull) return fail(tr, LS_ERR_OUT_OF_RANGE, "more than 2^32 triangles");
-    const uint32_t n_tris = first[n_table] = (uint32_t)total;
-    if ((rc = a.tri_first.upload_if_changed(tr, s, first))) return rc;
-    // the queue: its count word (in an entry of its own), then 8 bytes per triangle of the scene -- it cannot overflow
-    if ((rc = ensure(tr, tr->rq.dist_queue, (size_t)n_tris + 1))) return rc;
-    uint32_t *count = reinterpret_cast<uint32_t *>(tr->rq.dist_queue.p);
-    uint2 *queue = tr->rq.dist_queue.p + 1;
+    uint32_t n_table, n_tris, *count;
+    uint2 *queue;
+    if ((rc = scene_tris_prepare(tr, s, 0xFFFFFFFFull, "more than 2^32 triangles", &n_table, &n_tris))) return rc;
+    if ((rc = scene_queue_ensure(tr, tr->rq.dist_queue, n_tris, &count, &queue))) return rc;
     unsigned long long *cells = static_cast<unsigned long long *>(d_cells);
     const int small = tune_int("LS_DIST_GRID_SMALL", kDistGridSmall);
     const bool preread = tune_int("LS_DIST_GRID_PREREAD", kDistGridPreread) != 0;
@@ -99,21 +86,15 @@ int ls_scene_distance_grid_host(ls_tracer *tr, const ls_distance_grid_desc *grid
     if ((rc = dist_grid_check(tr, grid, sensor_to_grid3x4, select, n_select, cells, true))) return rc;
     const hipStream_t s = tr->stream;
     if ((rc = query_enter(tr, s))) return rc;
-    const size_t n_cells = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];
-    const bool acc = (grid->flags & LS_DIST_GRID_ACCUMULATE) != 0u;
     Staging st;
     const int p_select = st.in(select, n_select);
     // an accumulating call goes on from what the caller's array holds: it travels both ways
-    const int p_in = acc ? st.in(cells, n_cells * 8) : -1, p_out = acc ? -1 : st.out(cells, n_cells, 8);
+    const int p_cells = st.inout(cells, ls::grid_cells(grid->dims), 8, (grid->flags & LS_DIST_GRID_ACCUMULATE) != 0u);
     Staged io;
     if ((rc = st.commit(tr, s, io))) return rc;
-    void *d_cells = io.dev(acc ? p_in : p_out);
     const ls::DistGrid g = ls::dist_grid(*grid, sensor_to_grid3x4);
-    if ((rc = dist_grid_issue(tr, s, g, io.dev<const uint8_t>(p_select), n_select, d_cells))) return rc;
-    if (!acc) return io.fetch(tr);
-    LS_HIP(hipMemcpyAsync(cells, d_cells, n_cells * 8, hipMemcpyDeviceToHost, s));
-    LS_HIP(hipStreamSynchronize(s));
-    return LS_OK;
+    if ((rc = dist_grid_issue(tr, s, g, io.dev<const uint8_t>(p_select), n_select, io.dev(p_cells)))) return rc;
+    return io.fetch(tr);
 }
 
 }  // extern "C"

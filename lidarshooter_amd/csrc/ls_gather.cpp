@@ -47,6 +47,25 @@ int tables_prepare(ls_tracer *tr, hipStream_t s, const Moving *mv)
     return tr->ha.motion.upload_if_changed(tr, s, by_id);
 }
 
+// that table and, next to it, HitAttr::tri_first: where each geomID's triangles start in the flat triangle index (a free id: none),
+// the total behind them (ls_scene_tris.h).  More than max_tris triangles: LS_ERR_OUT_OF_RANGE with the caller's message
+int scene_tris_prepare(ls_tracer *tr, hipStream_t s, unsigned long long max_tris, const char *too_many, uint32_t *n_table, uint32_t *n_tris)
+{
+    ls_tracer::HitAttr &a = tr->ha;
+    if (const int rc = tables_prepare(tr, s, nullptr)) return rc;
+    *n_table = (uint32_t)a.table.current.size();
+    std::vector<uint32_t> first((size_t)*n_table + 1);
+    unsigned long long total = 0;
+    for (uint32_t k = 0; k < *n_table; ++k) {
+        const ls::AttrGeom &e = a.table.current[k];
+        first[k] = (uint32_t)total;
+        if (e.verts) total += e.quad ? 2ull * e.n_elems : e.n_elems;
+    }
+    if (total > max_tris) return fail(tr, LS_ERR_OUT_OF_RANGE, too_many);
+    *n_tris = first[*n_table] = (uint32_t)total;
+    return a.tri_first.upload_if_changed(tr, s, first);
+}
+
 namespace {
 
 // what the moving calls refuse after their own NULL checks, in this order: ls_trace_scene_sweep_moving's pose table, flags and

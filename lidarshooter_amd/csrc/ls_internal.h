@@ -8,7 +8,8 @@
 //   ls_query.cpp     ls_trace_rays / ls_occluded_rays / ls_closest_points: the query set of per-geometry hierarchies (built lazily),
 //                    batches of geometries per launch; what every query entry point shares (stream hand-over, staging, read-back)
 //   ls_gather.cpp    ls_hit_attributes: the per-geomID table of its gather kernel; ls_apply_return_model: the same table, its scratch;
-//                    their _moving pairs for the records of ls_trace_scene_sweep_moving (ls_attr_moving.hip): a motion table per geomID
+//                    their _moving pairs for the records of ls_trace_scene_sweep_moving (ls_attr_moving.hip): a motion table per geomID;
+//                    the scene's flat triangle index next to that table, for the scene-side queries (ls_scene_tris.h)
 //   ls_cloud.cpp     ls_format_cloud: the records of a frame as a cloud in a driver's own record (ls_format.hip), its format helpers
 //   ls_scan.cpp      ls_trace_scene_sweep, ls_trace_scene_beams, ls_trace_scene_sweep_moving: their scratch around the queries' walk
 //                    (ls_sweep.hip, ls_beam.hip, ls_moving.hip)
@@ -543,6 +544,18 @@ int query_leave(ls_tracer *tr, hipStream_t s);
 int query_footprint(ls_tracer *tr, hipStream_t s, const void *d_rays, uint32_t n, bool own_rays, uint32_t n_labels, void *d_acc);
 // ls_gather.cpp: the per-geomID table of the gathers (tr->ha.table) brought up to date on s; mv: a moving call's motion tables too
 int tables_prepare(ls_tracer *tr, hipStream_t s, const Moving *mv);
+// ... and the scene's flat triangle index next to it (tr->ha.tri_first; ls_scene_tris.h): *n_table entries, *n_tris triangles; more
+// than max_tris of them: LS_ERR_OUT_OF_RANGE with the message too_many
+int scene_tris_prepare(ls_tracer *tr, hipStream_t s, unsigned long long max_tris, const char *too_many, uint32_t *n_table, uint32_t *n_tris);
+// the queue of a scene query's big kernel: the count word (in an entry of its own), then 8 bytes per triangle of the scene -- it
+// cannot overflow
+inline int scene_queue_ensure(ls_tracer *tr, DevBuf<uint2> &q, uint32_t n_tris, uint32_t **count, uint2 **first)
+{
+    if (const int rc = ensure(tr, q, (size_t)n_tris + 1)) return rc;
+    *count = reinterpret_cast<uint32_t *>(q.p);
+    *first = q.p + 1;
+    return LS_OK;
+}
 // the tail of every device entry point: the query's place on s around what it issues
 template <typename Issue>
 inline int query_run(ls_tracer *tr, hipStream_t s, Issue &&issue)
@@ -552,8 +565,9 @@ inline int query_run(ls_tracer *tr, hipStream_t s, Issue &&issue)
     return query_leave(tr, s);
 }
 // The host-memory variants stage in RayQuery::io, on the handle's stream.  A call declares every piece first -- in(): copied to the
-// device by commit(); out(): `records` records of `bytes` each, read back afterwards; scratch(): neither -- and a null or empty
-// piece is absent: no room, no copy, nullptr for an address.  commit() sizes q.io (a growing buffer: the frame path's frames in
+// device by commit(); out(): `records` records of `bytes` each, read back afterwards; inout(): an out() that commit() also copies in
+// when the call accumulates into what the caller's array holds; scratch(): neither -- and a null or empty piece is absent: no room,
+// no copy, nullptr for an address.  commit() sizes q.io (a growing buffer: the frame path's frames in
 // flight never read it), starts the copies and fills in the Staged, which alone gives a piece's device address: no pointer can be
 // formed before the buffer has its final place.  Every piece starts 16-byte aligned.
 struct StagePiece {
@@ -584,7 +598,8 @@ private:
 class Staging {
 public:
     int in(const void *src, size_t bytes) { return add(const_cast<void *>(src), src ? bytes : 0, 0, true); }
-    int out(void *dst, size_t records, size_t bytes) { return add(dst, dst ? records * bytes : 0, bytes, false); }
+    int out(void *dst, size_t records, size_t bytes) { return inout(dst, records, bytes, false); }
+    int inout(void *p, size_t records, size_t bytes, bool copy_in) { return add(p, p ? records * bytes : 0, bytes, copy_in); }
     int scratch(size_t bytes) { return add(nullptr, bytes, 0, false); }
     int commit(ls_tracer *tr, hipStream_t s, Staged &io);
 

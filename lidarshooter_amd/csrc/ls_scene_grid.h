@@ -28,8 +28,8 @@
 #include <stdint.h>
 
 #include "../../include/lidarshooter_hip.h"
+#include "ls_grid_box.h"
 #include "ls_kernels.h"
-#include "ls_voxel.h"
 
 #if defined(__HIPCC__)
 #define LS_SGRID_HD __host__ __device__ __forceinline__
@@ -52,43 +52,22 @@ struct SceneGrid {
     float xf[12];   // sensor -> grid, row-major 3 x 4 (read only with has_xf)
 };
 
-// the grid's box as ls_occupancy_grid describes one: the limits and the checks of ls_voxel.h apply to it as they stand
-inline ls_occupancy_grid_desc scene_grid_as_voxel(const ls_scene_grid_desc &g)
-{
-    ls_occupancy_grid_desc v{};
-    for (int a = 0; a < 3; ++a) { v.origin[a] = g.origin[a]; v.dims[a] = g.dims[a]; }
-    v.cell = g.cell;
-    v.max_range = 1.0f;
-    return v;
-}
-
 // What the call refuses of a descriptor and a transform (nullptr: none), in the header's order, as two steps -- the device entry
 // point's alignment test stands between them: the message of an LS_ERR_INVALID_ARGUMENT, then that of an LS_ERR_OUT_OF_RANGE
 inline const char *scene_grid_args_invalid(const ls_scene_grid_desc &g, const float *xf)
 {
     if (g.flags & ~kSceneGridFlags) return "unknown flags";
-    return voxel_args_invalid(scene_grid_as_voxel(g), xf);   // the origin, the transform, the cell
+    return grid_box_invalid(g.origin, g.cell, xf);
 }
 
-inline const char *scene_grid_out_of_range(const ls_scene_grid_desc &g) { return voxel_grid_out_of_range(scene_grid_as_voxel(g)); }
+inline const char *scene_grid_out_of_range(const ls_scene_grid_desc &g) { return grid_box_out_of_range(g.origin, g.dims, g.cell); }
 
 inline SceneGrid scene_grid(const ls_scene_grid_desc &g, const float *sensor_to_grid3x4)
 {
     SceneGrid v{};
-    for (int a = 0; a < 3; ++a) { v.origin[a] = g.origin[a]; v.n[a] = g.dims[a]; }
-    v.cell = g.cell; v.flags = g.flags;
-    v.has_xf = sensor_to_grid3x4 ? 1u : 0u;
-    for (int k = 0; k < 12; ++k) v.xf[k] = sensor_to_grid3x4 ? sensor_to_grid3x4[k] : 0.0f;
+    grid_set_box(v, g, sensor_to_grid3x4);
+    v.flags = g.flags;
     return v;
-}
-
-// a sensor-frame vertex in the grid's frame: ls_cloud_to_world's products and sums in its order
-LS_SGRID_HD void scene_vertex_to_grid(const float *m, float &x, float &y, float &z)
-{
-    const float a = x, b = y, c = z;
-    x = ((m[0] * a + m[1] * b) + m[2] * c) + m[3];
-    y = ((m[4] * a + m[5] * b) + m[6] * c) + m[7];
-    z = ((m[8] * a + m[9] * b) + m[10] * c) + m[11];
 }
 
 // a triangle as the cells' test reads it: named scalars, so that the device keeps them in registers
@@ -179,10 +158,7 @@ LS_SGRID_HD bool scene_cell_overlaps(const SceneTri &t, int cx, int cy, int cz)
     return !(d > t.rn || d < -t.rn);
 }
 
-LS_SGRID_HD uint32_t scene_cell_index(const SceneGrid &g, int cx, int cy, int cz)
-{
-    return ((uint32_t)cz * g.n[1] + (uint32_t)cy) * g.n[0] + (uint32_t)cx;
-}
+LS_SGRID_HD uint32_t scene_cell_index(const SceneGrid &g, int cx, int cy, int cz) { return grid_cell_index(g.n, cx, cy, cz); }
 
 // ---- the launches of ls_scene_grid.hip ---------------------------------------------------------------------------------------------
 

@@ -2,8 +2,8 @@
 // number of triangles of the committed scene that overlap it and the lowest geomID among them.
 //
 //   k_scene_grid_clear   the grid to zero / 0xFFFFFFFF (unless the call accumulates) and the queue's count word to zero;
-//   k_scene_grid_small   one lane per triangle of the scene: the vertices through the frame's transform (xform_vertex) and the call's,
-//                        the clamped cell range (ls_scene_grid.h); a range of at most `small` cells is tested by the lane itself, a
+//   k_scene_grid_small   one lane per triangle of the scene's flat index: its vertices (ls_scene_tris.h), the clamped cell
+//                        range (ls_scene_grid.h); a range of at most `small` cells is tested by the lane itself, a
 //                        larger one is appended to a queue -- one ballot and one atomicAdd per wave;
 //   k_scene_grid_big     the queued triangles: blockIdx.x strides over the queue, blockIdx.y over the triangle's tiles of 8 x 8 x 8
 //                        cells, the lanes of the block over the cells of a tile, so that one ground triangle under a 2048 x 2048
@@ -14,7 +14,7 @@
 // order of the triangles and of the waves.  Every loop bound comes from the clamped integer range, at most 2^27 cells: a launch
 // ends whatever the vertices hold.
 #include "ls_scene_grid.h"
-#include "ls_device.h"
+#include "ls_scene_tris.h"
 
 namespace ls {
 
@@ -35,22 +35,12 @@ __global__ __launch_bounds__(kBlock) void k_scene_grid_clear(uint4 *__restrict__
         for (uint32_t k = 4u * i; k < n_cells && k < 4u * i + 4u; ++k) geom[k] = kInvalid;
 }
 
-// Triangle `tri` of geometry `geom` (both in range of the table) in the grid's frame.  The three indices are checked against the
-// vertex count before an address is formed from them.  false: no such geometry, an index out of range, a non-finite vertex or a
-// triangle outside the grid
+// Triangle `tri` of geometry ge (both in range of the table) in the grid's frame (scene_tri_vertices).  false: no such geometry,
+// an index out of range, a non-finite vertex or a triangle outside the grid
 __device__ __forceinline__ bool scene_tri_load(const SceneGrid &g, const AttrGeom &ge, uint32_t tri, SceneTri &t, SceneRange &r)
 {
-    if (ge.verts == nullptr) return false;
-    const uint32_t i0 = ge.idx[3 * (size_t)tri], i1 = ge.idx[3 * (size_t)tri + 1], i2 = ge.idx[3 * (size_t)tri + 2];
-    if (!(i0 < ge.n_verts && i1 < ge.n_verts && i2 < ge.n_verts)) return false;
-    V3 a = xform_vertex(ge.m, ge.verts + (size_t)i0 * ge.stride);
-    V3 b = xform_vertex(ge.m, ge.verts + (size_t)i1 * ge.stride);
-    V3 c = xform_vertex(ge.m, ge.verts + (size_t)i2 * ge.stride);
-    if (g.has_xf) {
-        scene_vertex_to_grid(g.xf, a.x, a.y, a.z);
-        scene_vertex_to_grid(g.xf, b.x, b.y, b.z);
-        scene_vertex_to_grid(g.xf, c.x, c.y, c.z);
-    }
+    V3 a, b, c;
+    if (!scene_tri_vertices(g.has_xf != 0u, g.xf, ge, tri, a, b, c)) return false;
     return scene_tri_setup(g, a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z, t, r);
 }
 
@@ -71,13 +61,7 @@ __global__ __launch_bounds__(kBlock) void k_scene_grid_small(SceneGrid g, const 
     SceneRange r;
     uint32_t gid = 0u, tri = 0u, cells = 0u;   // cells = 0: this lane has no triangle
     if (i < n_tris) {
-        // the geometry whose slice holds i: the last one with tri_first[gid] <= i (tri_first[0] = 0, tri_first[n_table] = n_tris > i)
-        uint32_t lo = 0u, hi = n_table;
-        while (hi - lo > 1u) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (tri_first[mid] <= i) lo = mid; else hi = mid;
-        }
-        gid = lo;
+        gid = scene_geom_of(tri_first, n_table, i);
         tri = i - tri_first[gid];
         const bool selected = gid >= n_select || select[gid] != 0;
         if (selected && scene_tri_load(g, table[gid], tri, t, r)) cells = scene_range_cells(r);

@@ -1,8 +1,7 @@
 // ls_scene_grid_host.cpp -- ls_scene_grid, its host-memory variant and the descriptor's check: per cell of a voxel grid the triangles
 // of the committed scene that overlap it and the lowest geomID among them (ls_scene_grid.hip; the arithmetic is ls_scene_grid.h).
-// The scene is the gathers' table (tables_prepare, ls_gather.cpp) with a triangle offset per geomID next to it; the call's place
-// among what the handle issues is that of every query (query_enter / query_leave).  No hierarchy is touched and
-// LS_INFO_RAY_QUERY_BUILT is left as it is.
+// The scene is the flat triangle index (scene_tris_prepare; ls_scene_tris.h); the call's place among what the handle issues is that
+// of every query (query_enter / query_leave).  No hierarchy is touched and LS_INFO_RAY_QUERY_BUILT is left as it is.
 #include "ls_internal.h"
 #include "ls_scene_grid.h"
 
@@ -36,25 +35,12 @@ int scene_grid_check(ls_tracer *tr, const ls_scene_grid_desc *grid, const float 
 
 int scene_grid_issue(ls_tracer *tr, hipStream_t s, const ls::SceneGrid &g, const uint8_t *d_select, uint32_t n_select, void *d_counts, void *d_geom)
 {
-    ls_tracer::HitAttr &a = tr->ha;
+    const ls_tracer::HitAttr &a = tr->ha;
     int rc;
-    if ((rc = tables_prepare(tr, s, nullptr))) return rc;
-    const uint32_t n_table = (uint32_t)a.table.current.size();
-    // where each geomID's triangles start in the flat index (a free id: none), the total behind them
-    std::vector<uint32_t> first((size_t)n_table + 1);
-    unsigned long long total = 0;
-    for (uint32_t k = 0; k < n_table; ++k) {
-        const ls::AttrGeom &e = a.table.current[k];
-        first[k] = (uint32_t)total;
-        if (e.verts) total += e.quad ? 2ull * e.n_elems : e.n_elems;
-    }
-    if (total > 0xFFFFFFFFull) return fail(tr, LS_ERR_OUT_OF_RANGE, "more than 2^32 triangles");
-    const uint32_t n_tris = first[n_table] = (uint32_t)total;
-    if ((rc = a.tri_first.upload_if_changed(tr, s, first))) return rc;
-    // the queue: its count word (in an entry of its own), then 8 bytes per triangle of the scene -- it cannot overflow
-    if ((rc = ensure(tr, tr->rq.scene_queue, (size_t)n_tris + 1))) return rc;
-    uint32_t *count = reinterpret_cast<uint32_t *>(tr->rq.scene_queue.p);
-    uint2 *queue = tr->rq.scene_queue.p + 1;
+    uint32_t n_table, n_tris, *count;
+    uint2 *queue;
+    if ((rc = scene_tris_prepare(tr, s, 0xFFFFFFFFull, "more than 2^32 triangles", &n_table, &n_tris))) return rc;
+    if ((rc = scene_queue_ensure(tr, tr->rq.scene_queue, n_tris, &count, &queue))) return rc;
     uint32_t *counts = static_cast<uint32_t *>(d_counts), *geom = static_cast<uint32_t *>(d_geom);
     const int small = tune_int("LS_SCENE_GRID_SMALL", kSceneGridSmall);
     ls::launch_scene_grid_clear(s, g, counts, geom, count);
@@ -99,23 +85,17 @@ int ls_scene_grid_host(ls_tracer *tr, const ls_scene_grid_desc *grid, const floa
     if ((rc = scene_grid_check(tr, grid, sensor_to_grid3x4, select, n_select, counts, geom, true))) return rc;
     const hipStream_t s = tr->stream;
     if ((rc = query_enter(tr, s))) return rc;
-    const size_t cells = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];
+    const size_t cells = ls::grid_cells(grid->dims);
     const bool acc = (grid->flags & LS_SCENE_GRID_ACCUMULATE) != 0u;
     Staging st;
     const int p_select = st.in(select, n_select);
     // an accumulating call goes on from what the caller's arrays hold: they travel both ways
-    const int p_counts_in = acc ? st.in(counts, cells * 4) : -1, p_geom_in = acc ? st.in(geom, cells * 4) : -1;
-    const int p_counts = acc ? -1 : st.out(counts, cells, 4), p_geom = acc ? -1 : st.out(geom, cells, 4);
+    const int p_counts = st.inout(counts, cells, 4, acc), p_geom = st.inout(geom, cells, 4, acc);
     Staged io;
     if ((rc = st.commit(tr, s, io))) return rc;
-    void *d_counts = io.dev(acc ? p_counts_in : p_counts), *d_geom = io.dev(acc ? p_geom_in : p_geom);
     const ls::SceneGrid g = ls::scene_grid(*grid, sensor_to_grid3x4);
-    if ((rc = scene_grid_issue(tr, s, g, io.dev<const uint8_t>(p_select), n_select, d_counts, d_geom))) return rc;
-    if (!acc) return io.fetch(tr);
-    LS_HIP(hipMemcpyAsync(counts, d_counts, cells * 4, hipMemcpyDeviceToHost, s));
-    if (geom) LS_HIP(hipMemcpyAsync(geom, d_geom, cells * 4, hipMemcpyDeviceToHost, s));
-    LS_HIP(hipStreamSynchronize(s));
-    return LS_OK;
+    if ((rc = scene_grid_issue(tr, s, g, io.dev<const uint8_t>(p_select), n_select, io.dev(p_counts), io.dev(p_geom)))) return rc;
+    return io.fetch(tr);
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 // (ls_surface_sample_host.cpp).
 //
 // Everything float is float32 and every operation rounds once (the library is compiled with -ffp-contract=off); there is no fmaf.
-// Per triangle i of the flat index, q_k its vertices in the output frame (ls_scene_grid's vertex path, without an origin):
+// Per triangle i of the flat index, q_k its vertices in the output frame (ls_scene_tris.h's vertex path):
 //   1. weight 0 for an unselected geometry, a free id, an index >= n_verts, a non-finite coordinate;
 //   2. N = (q1 - q0) x (q2 - q0) as products and differences -- scene_tri_setup's form (ls_scene_grid.h), NOT attr_cross's fused one
 //      (ls_hit_attr.h): the normal of a sample is not bit-equal to ls_hit_attributes' --; m = max |N_k|, weight 0 unless m > 0 and
@@ -28,8 +28,8 @@
 
 #include "../../include/lidarshooter_hip.h"
 #include "ls_kernels.h"
+#include "ls_grid_box.h"
 #include "ls_return_model.h"
-#include "ls_scene_grid.h"
 
 #if defined(__HIPCC__)
 #define LS_SURF_HD __host__ __device__ __forceinline__
@@ -64,8 +64,7 @@ inline SurfaceSample surface_sample(const ls_surface_sample_desc &d, const float
 {
     SurfaceSample v{};
     v.first = d.first_sample; v.n = d.n_samples; v.seed = d.seed;
-    v.has_xf = sensor_to_out3x4 ? 1u : 0u;
-    for (int k = 0; k < 12; ++k) v.xf[k] = sensor_to_out3x4 ? sensor_to_out3x4[k] : 0.0f;
+    grid_set_xf(v, sensor_to_out3x4);
     return v;
 }
 

@@ -1,9 +1,8 @@
 // ls_surface_sample.hip -- the kernels of ls_sample_surface (include/lidarshooter_hip.h): points drawn from the
 // surface of the committed scene in proportion to area, each with its unit normal, its owner and its barycentrics.
 //
-//   k_surface_area         one lane per triangle of the scene: the vertices through the frame's transform (xform_vertex) and the
-//                          call's, as k_scene_grid_small obtains them; the area's bits to area[1 + i], and their maximum -- reduced in
-//                          the wave, one atomicMax per wave -- to area[0];
+//   k_surface_area         one lane per triangle of the scene's flat index: its vertices (ls_scene_tris.h); the area's bits to
+//                          area[1 + i], and their maximum -- reduced in the wave, one atomicMax per wave -- to area[0];
 //   k_surface_block_sums   the weights (from the areas and the maximum) of every 256 triangles summed, and how many are > 0;
 //   k_surface_prefix       every workgroup adds up the sums of the workgroups before its own (ls_pack.h's style: no workgroup waits
 //                          for another, no atomic append), scans its own 256 weights and writes P; the last one writes P[n_tris]
@@ -15,7 +14,7 @@
 // comes from a count (n_table, n_tris, the number of workgroups, 32 trips of a bisection) and never from data; every index is
 // checked before an address is formed from it.
 #include "ls_surface_sample.h"
-#include "ls_device.h"
+#include "ls_scene_tris.h"
 
 namespace ls {
 
@@ -23,33 +22,12 @@ namespace {
 
 static_assert(kSurfaceBlock == kBlock, "the scan below is written for four waves");
 
-// the geometry whose slice of the flat index holds i < n_tris: the last one with tri_first[gid] <= i (k_scene_grid_small's bisection)
-__device__ __forceinline__ uint32_t surface_geom_of(const uint32_t *__restrict__ tri_first, uint32_t n_table, uint32_t i)
-{
-    uint32_t lo = 0u, hi = n_table;
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (tri_first[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// Triangle `tri` of geometry ge (in range of the table) in the output frame: scene_tri_load's vertex path (ls_scene_grid.hip) without
-// the grid.  The three indices are checked against the vertex count before an address is formed from them.  false: no such geometry
-// or an index out of range
+// Triangle `tri` of geometry ge (in range of the table) in the output frame (scene_tri_vertices).  false: no such geometry or an
+// index out of range
 __device__ __forceinline__ bool surface_tri_load(const SurfaceSample &d, const AttrGeom &ge, uint32_t tri, float *q)
 {
-    if (ge.verts == nullptr) return false;
-    const uint32_t i0 = ge.idx[3 * (size_t)tri], i1 = ge.idx[3 * (size_t)tri + 1], i2 = ge.idx[3 * (size_t)tri + 2];
-    if (!(i0 < ge.n_verts && i1 < ge.n_verts && i2 < ge.n_verts)) return false;
-    V3 a = xform_vertex(ge.m, ge.verts + (size_t)i0 * ge.stride);
-    V3 b = xform_vertex(ge.m, ge.verts + (size_t)i1 * ge.stride);
-    V3 c = xform_vertex(ge.m, ge.verts + (size_t)i2 * ge.stride);
-    if (d.has_xf) {
-        scene_vertex_to_grid(d.xf, a.x, a.y, a.z);
-        scene_vertex_to_grid(d.xf, b.x, b.y, b.z);
-        scene_vertex_to_grid(d.xf, c.x, c.y, c.z);
-    }
+    V3 a, b, c;
+    if (!scene_tri_vertices(d.has_xf != 0u, d.xf, ge, tri, a, b, c)) return false;
     q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = b.x; q[4] = b.y; q[5] = b.z; q[6] = c.x; q[7] = c.y; q[8] = c.z;
     return true;
 }
@@ -81,7 +59,7 @@ __global__ __launch_bounds__(kBlock) void k_surface_area(SurfaceSample d, const 
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     uint32_t bits = 0u;
     if (i < n_tris) {
-        const uint32_t gid = surface_geom_of(tri_first, n_table, i);
+        const uint32_t gid = scene_geom_of(tri_first, n_table, i);
         const uint32_t tri = i - tri_first[gid];
         const bool selected = gid >= n_select || select[gid] != 0;
         float q[9], n[3];
@@ -192,7 +170,7 @@ __global__ __launch_bounds__(kBlock) void k_surface_sample(SurfaceSample d, cons
             hi = b < n_tris ? (uint32_t)b : n_tris;
         }
         const uint32_t i = surface_bisect(prefix, lo, hi, T);   // (below n_tris: lo < hi <= n_tris)
-        const uint32_t gid = surface_geom_of(tri_first, n_table, i);
+        const uint32_t gid = scene_geom_of(tri_first, n_table, i);
         const uint32_t tri = i - tri_first[gid];
         const AttrGeom &ge = table[gid];
         float q[9], n[3], p[3], u, v, w;

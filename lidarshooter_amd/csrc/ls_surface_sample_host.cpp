@@ -1,8 +1,7 @@
 // ls_surface_sample_host.cpp -- ls_sample_surface, its host-memory variant and the descriptor's check: points drawn from the surface
 // of the committed scene in proportion to area (ls_surface_sample.hip; the arithmetic is ls_surface_sample.h).  The scene is the
-// gathers' table (tables_prepare, ls_gather.cpp) with ls_scene_grid's triangle offset per geomID next to it; the call's place among
-// what the handle issues is that of every query (query_enter / query_leave).  No hierarchy is touched and LS_INFO_RAY_QUERY_BUILT is
-// left as it is.
+// flat triangle index (scene_tris_prepare; ls_scene_tris.h); the call's place among what the handle issues is that of every query
+// (query_enter / query_leave).  No hierarchy is touched and LS_INFO_RAY_QUERY_BUILT is left as it is.
 #include "ls_internal.h"
 #include "ls_surface_sample.h"
 
@@ -32,21 +31,11 @@ int surface_sample_check(ls_tracer *tr, const ls_surface_sample_desc *desc, cons
 int surface_sample_issue(ls_tracer *tr, hipStream_t s, const ls::SurfaceSample &d, const uint8_t *d_select, uint32_t n_select, void *d_samples,
                          void *d_info)
 {
-    ls_tracer::HitAttr &a = tr->ha;
+    const ls_tracer::HitAttr &a = tr->ha;
     int rc;
-    if ((rc = tables_prepare(tr, s, nullptr))) return rc;
-    const uint32_t n_table = (uint32_t)a.table.current.size();
-    // where each geomID's triangles start in the flat index (a free id: none), the total behind them: ls_scene_grid's table
-    std::vector<uint32_t> first((size_t)n_table + 1);
-    unsigned long long total = 0;
-    for (uint32_t k = 0; k < n_table; ++k) {
-        const ls::AttrGeom &e = a.table.current[k];
-        first[k] = (uint32_t)total;
-        if (e.verts) total += e.quad ? 2ull * e.n_elems : e.n_elems;
-    }
-    if (total > 0xFFFFFF00ull) return fail(tr, LS_ERR_OUT_OF_RANGE, "more than 2^32 - 256 triangles");   // (a lane per triangle, in 32 bits)
-    const uint32_t n_tris = first[n_table] = (uint32_t)total;
-    if ((rc = a.tri_first.upload_if_changed(tr, s, first))) return rc;
+    uint32_t n_table, n_tris;
+    // (a lane per triangle, in 32 bits)
+    if ((rc = scene_tris_prepare(tr, s, 0xFFFFFF00ull, "more than 2^32 - 256 triangles", &n_table, &n_tris))) return rc;
     // the maximum's word and an area word per triangle; P[0 .. n_tris] and the workgroups' pairs {sum, count} behind it
     if ((rc = ensure(tr, tr->rq.surface_area, (size_t)n_tris + 1))) return rc;
     if ((rc = ensure(tr, tr->rq.surface_prefix, (size_t)n_tris + 1 + 2 * (size_t)ls::surface_blocks(n_tris)))) return rc;

@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "../../include/lidarshooter_hip.h"
+#include "ls_grid_box.h"
 #include "ls_kernels.h"
 
 #if defined(__HIPCC__)
@@ -24,8 +25,6 @@
 
 namespace ls {
 
-constexpr uint32_t kVoxelMaxDim = 2048;          // cells per axis
-constexpr uint32_t kVoxelMaxCells = 1u << 27;    // cells of a grid
 constexpr uint32_t kVoxelFlags = LS_OCC_CARVE_MISSES | LS_OCC_ACCUMULATE;
 
 // the descriptor as the kernels take it, with the call's transform next to it
@@ -39,39 +38,23 @@ struct VoxelGrid {
 
 // What the call refuses of a descriptor and a transform (nullptr: none), in the header's order, as two steps -- the device entry
 // point's alignment test stands between them.  voxel_args_invalid: the message of an LS_ERR_INVALID_ARGUMENT, or nullptr;
-// voxel_grid_out_of_range: that of an LS_ERR_OUT_OF_RANGE.
+// voxel_grid_out_of_range: that of an LS_ERR_OUT_OF_RANGE.  The box's share of both is ls_grid_box.h's.
 inline const char *voxel_args_invalid(const ls_occupancy_grid_desc &g, const float *xf)
 {
     if ((g.flags & ~kVoxelFlags) || g.reserved[0] || g.reserved[1]) return "unknown flags or non-zero reserved words";
-    if (!isfinite(g.origin[0]) || !isfinite(g.origin[1]) || !isfinite(g.origin[2])) return "the grid's origin is not finite";
-    for (int k = 0; xf && k < 12; ++k)
-        if (!isfinite(xf[k])) return "sensor_to_grid is not finite";
-    if (!isfinite(g.cell) || !(g.cell > 0.0f)) return "the cell edge is not a finite positive number";
+    if (const char *why = grid_box_invalid(g.origin, g.cell, xf)) return why;
     if (!isfinite(g.min_range) || !(g.min_range >= 0.0f)) return "min_range is not finite or negative";
     if (!isfinite(g.max_range) || !(g.max_range >= g.min_range)) return "max_range is not finite or below min_range";
     return nullptr;
 }
 
-inline const char *voxel_grid_out_of_range(const ls_occupancy_grid_desc &g)
-{
-    unsigned long long cells = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (g.dims[a] == 0 || g.dims[a] > kVoxelMaxDim) return "a grid dimension of 0 or above 2048";
-        cells *= g.dims[a];
-    }
-    if (cells > kVoxelMaxCells) return "more than 2^27 cells";
-    for (int a = 0; a < 3; ++a)
-        if (!isfinite(g.origin[a] + (float)g.dims[a] * g.cell)) return "the grid's upper corner is not finite";
-    return nullptr;
-}
+inline const char *voxel_grid_out_of_range(const ls_occupancy_grid_desc &g) { return grid_box_out_of_range(g.origin, g.dims, g.cell); }
 
 inline VoxelGrid voxel_grid(const ls_occupancy_grid_desc &g, const float *sensor_to_grid3x4)
 {
     VoxelGrid v{};
-    for (int a = 0; a < 3; ++a) { v.origin[a] = g.origin[a]; v.n[a] = g.dims[a]; }
-    v.cell = g.cell; v.flags = g.flags; v.min_range = g.min_range; v.max_range = g.max_range;
-    v.has_xf = sensor_to_grid3x4 ? 1u : 0u;
-    for (int k = 0; k < 12; ++k) v.xf[k] = sensor_to_grid3x4 ? sensor_to_grid3x4[k] : 0.0f;
+    grid_set_box(v, g, sensor_to_grid3x4);
+    v.flags = g.flags; v.min_range = g.min_range; v.max_range = g.max_range;
     return v;
 }
 
@@ -110,7 +93,8 @@ LS_VOXEL_HD uint32_t voxel_cell_of(const VoxelGrid &g, float px, float py, float
 {
     const float fx = floorf((px - g.origin[0]) / g.cell), fy = floorf((py - g.origin[1]) / g.cell), fz = floorf((pz - g.origin[2]) / g.cell);
     if (!(fx >= 0.0f && fx < (float)g.n[0] && fy >= 0.0f && fy < (float)g.n[1] && fz >= 0.0f && fz < (float)g.n[2])) return kVoxelNone;
-    return ((uint32_t)fz * g.n[1] + (uint32_t)fy) * g.n[0] + (uint32_t)fx;
+    const uint32_t cz = (uint32_t)fz, cy = (uint32_t)fy, cx = (uint32_t)fx;
+    return grid_cell_index(g.n, (int)cx, (int)cy, (int)cz);
 }
 
 // the record's point: one product and one sum per axis; a handle's own ray without a transform starts at the origin and has no sum
@@ -135,10 +119,7 @@ struct VoxelWalk {
 
 LS_VOXEL_HD float voxel_boundary(int c, float q, float d, float cell) { return ((float)(c + (d > 0.0f ? 1 : 0)) * cell - q) / d; }
 
-LS_VOXEL_HD uint32_t voxel_index(const VoxelGrid &g, const VoxelWalk &w)
-{
-    return ((uint32_t)w.c2 * g.n[1] + (uint32_t)w.c1) * g.n[0] + (uint32_t)w.c0;
-}
+LS_VOXEL_HD uint32_t voxel_index(const VoxelGrid &g, const VoxelWalk &w) { return grid_cell_index(g.n, w.c0, w.c1, w.c2); }
 
 // clip [t0, t1] of the ray (o, d) against the grid and find its first cell; w.live = false: no cells
 LS_VOXEL_HD void voxel_walk_begin(const VoxelGrid &g, const float *o, const float *d, float t0, float t1, VoxelWalk &w)

@@ -84,23 +84,17 @@ int ls_occupancy_grid_host(ls_tracer *tr, const ls_occupancy_grid_desc *grid, co
     if ((rc = voxel_check(tr, grid, sensor_to_grid3x4, rays, n_rays, hits, nullptr, n, counts, geom, true))) return rc;
     const hipStream_t s = tr->stream;
     if ((rc = query_enter(tr, s))) return rc;
-    const size_t cells = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];
+    const size_t cells = ls::grid_cells(grid->dims);
     const bool acc = (grid->flags & LS_OCC_ACCUMULATE) != 0u;
     Staging st;
     const int p_hits = st.in(hits, (size_t)n * 16), p_rays = st.in(rays, (size_t)n_rays * 32);
     // an accumulating call goes on from what the caller's arrays hold: they travel both ways
-    const int p_counts_in = acc ? st.in(counts, cells * 8) : -1, p_geom_in = acc ? st.in(geom, cells * 4) : -1;
-    const int p_counts = acc ? -1 : st.out(counts, cells, 8), p_geom = acc ? -1 : st.out(geom, cells, 4);
+    const int p_counts = st.inout(counts, cells, 8, acc), p_geom = st.inout(geom, cells, 4, acc);
     Staged io;
     if ((rc = st.commit(tr, s, io))) return rc;
-    void *d_counts = io.dev(acc ? p_counts_in : p_counts), *d_geom = io.dev(acc ? p_geom_in : p_geom);
     const ls::VoxelGrid g = ls::voxel_grid(*grid, sensor_to_grid3x4);
-    if ((rc = voxel_issue(tr, s, g, io.dev(p_rays), n_rays, rays == nullptr, io.dev(p_hits), nullptr, n, d_counts, d_geom))) return rc;
-    if (!acc) return io.fetch(tr);
-    LS_HIP(hipMemcpyAsync(counts, d_counts, cells * 8, hipMemcpyDeviceToHost, s));
-    if (geom) LS_HIP(hipMemcpyAsync(geom, d_geom, cells * 4, hipMemcpyDeviceToHost, s));
-    LS_HIP(hipStreamSynchronize(s));
-    return LS_OK;
+    if ((rc = voxel_issue(tr, s, g, io.dev(p_rays), n_rays, rays == nullptr, io.dev(p_hits), nullptr, n, io.dev(p_counts), io.dev(p_geom)))) return rc;
+    return io.fetch(tr);
 }
 
 }  // extern "C"
