@@ -164,6 +164,8 @@ int ls_update_geometry_device(ls_tracer *tr, const char *name, const float affin
  * during the following commitScene / traceScene calls (the vertex transform is fused into the trace
  * kernel, so nothing needs to be staged).  The caller must leave the buffers unchanged and alive until
  * that traceScene has completed on the handle's stream, or until the next update of this geometry.
+ * New contents of a shared buffer are announced by handing it over again: the library keeps data derived
+ * from the mesh (group bounds, standing lists), and a transform-only update says the mesh did not change.
  * d_tri_idx = NULL keeps the previously shared / copied indices. */
 int ls_update_geometry_device_shared(ls_tracer *tr, const char *name, const float affine3x4[12], const void *d_verts,
                                      uint32_t vert_stride, const uint32_t *d_tri_idx);
@@ -373,6 +375,19 @@ int ls_tracer_set_hit_buffers(ls_tracer *tr, void *d_hits, uint32_t *d_n_points,
                                  *    26 -> 6-8 us for a sharded group frame (tools/micro/graph_launch.hip).  A runtime
                                  *    that refuses the capture leaves the handle on plain launches
                                  *    (LS_INFO_FRAME_GRAPH_STATE).                                                        */
+#define LS_OPT_STANDING 17      /* projection engine: 1 (default) a geometry that has not changed for a few commits -- its
+                                 *    vertices, indices and pose, the sensor's pose and raster, the shard, its place in the
+                                 *    scene -- gets a STANDING LIST: one 64-byte record per triangle whose footprint on the
+                                 *    raster holds a cell (a sixth of a large ground mesh), built once by a launch of its own;
+                                 *    frames then expand the list instead of streaming the mesh.  Any change drops the list at
+                                 *    the next commit (a frame checks once more before it uses one) and a geometry that keeps
+                                 *    moving stops getting builds.  At most min(n, max(n / 4, 4096)) records for n triangles:
+                                 *    16 bytes per triangle; a mesh with more footprints is never standing.  Not used by
+                                 *    frames with LS_OPT_COUNT_VISITS, LS_OPT_TIMING or LS_OPT_PIPELINE = 1, nor between
+                                 *    ls_frame_graph_begin and ls_frame_graph_end.  With LS_OPT_FRAME_GRAPH a list that comes
+                                 *    into use or goes is another launch sequence: the graphs are captured anew, so a list is taken
+                                 *    into use there only after 64 unchanged commits, or when no graph is cached.  0: frames always
+                                 *    stream the meshes.  Identical results.  Takes effect at the next frame.               */
 int ls_tracer_set_option(ls_tracer *tr, int option, int value);
 
 /* A frame graph that also holds work of the CALLER's (include/lidarshooter_group.h: the frame's collective and the
@@ -430,6 +445,9 @@ int ls_parallel_copy(void *dst, const void *src, uint64_t bytes);
 #define LS_INFO_BVH_WIDE 16                /* 1: the last trace walked the four-wide nodes (LS_OPT_BVH_WIDE, instanced mode, every geometry's made) */
 #define LS_INFO_FRAME_GRAPH_PATCH_WAITS 15 /* patches that first had to wait for the previous launch of their graph (the host ran more than three frames ahead) */
 #define LS_INFO_RAY_QUERY_BUILT 17         /* geometries whose query hierarchy the last ls_trace_rays* / ls_occluded_rays* / ls_closest_points* built or refitted (see there) */
+#define LS_INFO_STANDING_GEOMETRIES 18     /* LS_OPT_STANDING: geometries the last frame traced from their standing lists   */
+#define LS_INFO_STANDING_BUILDS 19         /* standing lists built so far                                                    */
+#define LS_INFO_STANDING_RECORDS 20        /* records in the lists the last frame used                                       */
 long ls_get_info(ls_tracer *tr, int what);
 
 /* Mean stage durations (milliseconds, hipEvents on the handle's stream) over every frame recorded

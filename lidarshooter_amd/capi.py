@@ -35,6 +35,8 @@ RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direction", "<f4"
 REFHIT_DTYPE = np.dtype([("t", "<f4"), ("normal", "<f4", 3), ("intensity", "<f4"), ("ring", "<i4")])       # Hit.hpp:16-29
 LS_INFO_BVH_INSTANCED = 7
 LS_INFO_RAY_QUERY_BUILT = 17
+LS_OPT_STANDING = 17
+LS_INFO_STANDING_GEOMETRIES, LS_INFO_STANDING_BUILDS, LS_INFO_STANDING_RECORDS = 18, 19, 20
 LS_INFO_CONCURRENT_STREAMS, LS_INFO_PIPELINE_MODE, LS_INFO_DEVICE_STATUS, LS_INFO_HOST_THREADS, LS_INFO_AZIMUTH_COUNT = 1, 2, 3, 4, 5
 ENGINE_AUTO, ENGINE_BVH, ENGINE_PROJECTION = 0, 1, 2
 STAGES = ("transform", "morton", "sort", "leaves", "range_tree", "hierarchy", "trace", "trace_aux", "pack")

@@ -100,6 +100,83 @@ int prepare_blocks(ls_tracer *tr, Geometry &g)
     return LS_OK;
 }
 
+// ---- standing lists (ls_standing.h) ----------------------------------------------------------------------------------
+// In the reference's use most geometries stand still most of the time: the sensor pose comes from a config file, the ground
+// mesh is static, AffineMesh integrates a joystick velocity that is mostly zero, and the ITracer adapter turns an unchanged
+// pcl::PolygonMesh into ls_update_geometry_transform.  The policy below needs no device wait anywhere.
+void standing_drop(Standing &st)
+{
+    if (st.state != Standing::kNone)
+        st.wait = st.served < kStandingBreakEven ? std::min(st.wait * 2u, kStandingMaxWait) : kStandingFirstWait;
+    st.state = Standing::kNone;
+    st.count = 0;
+    st.served = 0;
+    st.in_graphs = false;
+}
+
+// the list of `ge`, built on the handle's stream behind every frame in flight (an earlier list in the same buffer may still be
+// read); the record count follows into pinned memory and an event behind it, which a later commit looks at
+static int standing_build(ls_tracer *tr, Geometry &ge, uint32_t tfirst)
+{
+    Standing &st = ge.standing;
+    int rc;
+    if ((rc = order_after_projects(tr))) return rc;
+    // the list is an optimisation: a scene that committed without it still commits when there is no memory for it -- the geometry
+    // keeps the ordinary path, as one whose footprints do not fit, until its key changes
+    if (!st.d_recs) {
+        st.cap = ls::standing_capacity(ge.n_tris);
+        if (hipMalloc(reinterpret_cast<void **>(&st.d_recs), (size_t)st.cap * sizeof(ls::StandingRecord)) != hipSuccess) st.d_recs = nullptr;
+    }
+    if (st.d_recs && !st.d_count && hipMalloc(reinterpret_cast<void **>(&st.d_count), 4) != hipSuccess) st.d_count = nullptr;
+    if (st.d_count && !st.h_count && hipHostMalloc(reinterpret_cast<void **>(&st.h_count), 4, hipHostMallocDefault) != hipSuccess) st.h_count = nullptr;
+    if (st.h_count && !st.ev && hipEventCreateWithFlags(&st.ev, hipEventDisableTiming) != hipSuccess) st.ev = nullptr;
+    if (!st.d_recs || !st.d_count || !st.h_count || !st.ev) {
+        (void)hipGetLastError();
+        st.state = Standing::kTooLong;
+        return LS_OK;
+    }
+    LS_HIP(ls::launch_standing_build(tr->stream, project_params(tr), project_source(tr, ge, tfirst), st.d_recs, st.cap, st.d_count));
+    LS_HIP(hipGetLastError());
+    LS_HIP(hipMemcpyAsync(st.h_count, st.d_count, 4, hipMemcpyDeviceToHost, tr->stream));
+    LS_HIP(hipEventRecord(st.ev, tr->stream));
+    st.state = Standing::kBuilding;
+    st.served = 0;
+    ++tr->standing_builds;
+    return LS_OK;
+}
+
+// every geometry of the layout, at the end of a commit of the projection engine: its key against the last commit's
+int standing_commit(ls_tracer *tr)
+{
+    const bool allowed = standing_allowed(tr);
+    for (const auto &le : tr->layout) {
+        Geometry &ge = tr->geoms.find(le.name)->second;
+        Standing &st = ge.standing;
+        const StandingKey key = standing_key(tr, ge, le.tfirst);
+        if (!st.key_valid || std::memcmp(&key, &st.key, sizeof(key)) != 0) {
+            standing_drop(st);
+            st.key = key;
+            st.key_valid = true;
+            st.same = 0;
+            continue;
+        }
+        if (st.same < 0xFFFFFFFFu) ++st.same;
+        if (st.state == Standing::kBuilding) {
+            const hipError_t e = hipEventQuery(st.ev);   // (never a wait)
+            if (e == hipSuccess) {
+                st.count = *st.h_count;
+                st.state = st.count <= st.cap ? Standing::kUsable : Standing::kTooLong;   // too long: the ordinary path, until the key changes
+            } else {
+                (void)hipGetLastError();   // (not ready is no error of this commit)
+                if (e != hipErrorNotReady) return fail(tr, LS_ERR_HIP, "hipEventQuery failed on a standing list's build");
+            }
+        }
+        if (st.state == Standing::kNone && allowed && st.same >= st.wait)
+            if (const int rc = standing_build(tr, ge, le.tfirst)) return rc;
+    }
+    return LS_OK;
+}
+
 // ---- BVH engine, instanced mode (LS_OPT_BVH_INSTANCED) --------------------------------------------------------------
 // mesh -> sensor of one geometry is p = Mlin v + Mtr with Mlin = Rinv A_lin, Mtr = Rinv (a - t).  Its inverse (double
 // precision) gives the sensor origin and the direction map in mesh space; false if the matrix is (nearly) singular --
@@ -444,6 +521,8 @@ int commit_locked(ls_tracer *tr)
         // (per vertex upload) so that k_cull can drop whole 64-triangle blocks before their indices are read.
         for (Geometry *ge : order)
             if ((rc = prepare_blocks(tr, *ge))) return rc;
+        // ... and a geometry that has not changed for a few commits the list of its triangles with a footprint
+        if ((rc = standing_commit(tr))) return rc;
         mark(tr, 1);
     }
     for (Geometry *ge : order) ge->idx_dirty = false;

@@ -126,6 +126,7 @@ static int upload_tables(ls_tracer *tr)
     if (tr->d_tables) (void)hipFree(tr->d_tables);
     tr->d_tables = d;
     tr->host_tables = tab;
+    ++tr->sensor_gen;   // (the standing lists' keys: new tables, band map, raster)
     return LS_OK;
 }
 
@@ -434,6 +435,7 @@ int ls_tracer_set_shard(ls_tracer *tr, uint32_t first_az, uint32_t n_az)
     if (rc) return rc;
     tr->az0 = first_az;
     tr->naz = n_az;
+    ++tr->sensor_gen;   // (the standing lists' keys)
     __atomic_store_n(tr->h_status + 1, 0u, __ATOMIC_RELAXED);   // (the survivor hint spoke for the old shard; a frame still running may write it once more: a hint, not a promise)
     tr->traced = false;
     tr->keys_armed = false;
@@ -498,6 +500,9 @@ long ls_get_info(ls_tracer *tr, int what)
     case LS_INFO_FRAME_GRAPH_PATCH_WAITS: return (long)tr->fg_patch_waits;
     case LS_INFO_BVH_WIDE: return (tr->bvh_inst && tr->wide_valid && tr->wide_in_use) ? 1 : 0;
     case LS_INFO_RAY_QUERY_BUILT: return tr->rq.last_built;
+    case LS_INFO_STANDING_GEOMETRIES: return tr->standing_geometries;
+    case LS_INFO_STANDING_BUILDS: return tr->standing_builds;
+    case LS_INFO_STANDING_RECORDS: return tr->standing_records;
     default: return fail(tr, LS_ERR_INVALID_ARGUMENT, "unknown info key");
     }
 }
@@ -616,6 +621,10 @@ int ls_tracer_set_option(ls_tracer *tr, int option, int value)
         tr->opt_frame_graph = value;
         return LS_OK;
     }
+    case LS_OPT_STANDING:
+        if (value < 0 || value > 1) return fail(tr, LS_ERR_INVALID_ARGUMENT, "LS_OPT_STANDING: 0 or 1");
+        tr->opt_standing = value;   // (a frame looks at it as it is issued; lists already built stay and are used again with 1)
+        return LS_OK;
     case LS_OPT_ENGINE:
         if (value < 0 || value > 2) return fail(tr, LS_ERR_INVALID_ARGUMENT, "engine must be 0 (auto), 1 (BVH) or 2 (projection)");
         if (value == 2 && !tr->projection_ok) return fail(tr, LS_ERR_INVALID_ARGUMENT, "projection engine needs channel angles within [-90, 90] degrees");

@@ -24,6 +24,7 @@
 #include "../../include/lidarshooter_hip.h"
 #include "../../include/lidarshooter_hip_debug.h"   // (LS_OPT_DEBUG_FAULT)
 #include "ls_kernels.h"
+#include "ls_standing.h"
 #include "ls_launch.h"
 #include "ls_tuning.h"
 
@@ -43,6 +44,47 @@
 #endif
 
 namespace lsi {
+
+// Everything a record of a geometry's standing list depends on (ls_standing.h), compared byte for byte -- at every commit with
+// the key of the commit before, which decides whether a list is built, kept or dropped (ls_commit.cpp: standing_commit), and
+// once more by the frame that is about to use the list (ls_trace.cpp).  Zeroed before it is filled (padding).
+struct StandingKey {
+    uint64_t vert_gen, idx_gen;       // which uploads / hand-overs the mesh is
+    uint64_t sensor_gen;              // ls_tracer::sensor_gen: the sensor's tables, band map, raster
+    const void *raw;
+    const uint32_t *idx;
+    uint32_t n_tris, stride, quad;
+    uint32_t az0, naz;                // the shard
+    uint32_t tfirst;                  // the geometry's first global triangle id in the layout
+    uint32_t big_cells;
+    float margin_az, margin_elev;
+    float affine[12], rinv[9], t[3];
+};
+
+// A geometry's standing list and the policy's state.  A list is built once the key has been equal at `wait` commits in a row;
+// one that is dropped before it has served kStandingBreakEven frames doubles `wait` (at most kStandingMaxWait), one that has
+// served that many puts it back to kStandingFirstWait: a geometry that keeps moving stops costing builds.
+constexpr uint32_t kStandingFirstWait = 2, kStandingMaxWait = 256;
+constexpr uint64_t kStandingBreakEven = 72;   // frames: a build of the headline mesh 183 us, 2.5 us saved per frame (EXPERIMENTS.md E27)
+// Under LS_OPT_FRAME_GRAPH a list that comes into use costs three captures (a wait for the stream, the capture, the instantiation:
+// of the order of 100 us each, not measured) against a few microseconds saved per frame: of the order of a hundred frames to pay back
+constexpr uint32_t kStandingGraphWait = 64;
+struct Standing {
+    enum State { kNone = 0, kBuilding, kUsable, kTooLong };
+    StandingKey key;
+    bool key_valid = false;
+    uint32_t same = 0;                 // commits in a row that found the key unchanged
+    uint32_t wait = kStandingFirstWait;
+    State state = kNone;
+    ls::StandingRecord *d_recs = nullptr;   // standing_capacity(n_tris) records, kept across drops for the next build
+    uint32_t cap = 0;
+    uint32_t *d_count = nullptr;       // the build's record count ...
+    uint32_t *h_count = nullptr;       // ... copied to this pinned word behind the build ...
+    hipEvent_t ev = nullptr;           // ... and this event behind the copy: a commit that finds it complete reads the word
+    uint32_t count = 0;                // kUsable: records in the list
+    uint64_t served = 0;               // frames traced from the current list
+    bool in_graphs = false;            // the captured frame graphs may hold its launch (ls_trace.cpp: route_standing)
+};
 
 struct Geometry {
     std::string name;
@@ -80,6 +122,7 @@ struct Geometry {
     // which upload the vertices / indices are (ls_tracer::upload_seq at the time): the ray-query set compares them with what its
     // hierarchies were built from (blas_dirty is the frame path's, consumed by the commit)
     uint64_t vert_gen = 0, idx_gen = 0;
+    Standing standing;          // projection engine: the triangles with a footprint, kept while nothing they depend on changes
     const void *raw() const { return shared_raw ? shared_raw : d_raw; }
     const uint32_t *idx() const { return shared_idx ? shared_idx : d_idx; }
     float affine[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
@@ -200,6 +243,12 @@ struct ls_tracer {
     const void *last_d_hits = nullptr;     // its hit records and count (device)
     const uint32_t *last_d_n = nullptr;
     std::vector<ls::GeomSource> project_srcs;  // scratch of trace_locked
+    // standing lists (ls_standing.h): LS_OPT_STANDING; bumped whenever the sensor's tables, band map, raster or shard change;
+    // the lists the frame being issued is traced from (scratch of trace_locked); LS_INFO_STANDING_*
+    int opt_standing = 1;
+    uint64_t sensor_gen = 0;
+    std::vector<ls::StandingBatch> standing_batches;
+    long standing_geometries = 0, standing_records = 0, standing_builds = 0;
     ls::RangeTree rt{};
     uint32_t range_entries = 0;
     uint32_t *d_maxabs = nullptr;
@@ -485,6 +534,13 @@ bool cull_enabled(const ls_tracer *tr, const Geometry &g);
 bool cull_size_ok(const ls_tracer *tr, uint32_t n_tris);   // large enough for 64 triangles per wave (or ls_debug_force_group_cull)
 // the committed geometries as the projection engine's next frame reads them (ls_trace.cpp): culling data attached where it is current
 int project_sources(ls_tracer *tr, std::vector<ls::GeomSource> &srcs, bool &any_culled);
+ls::GeomSource project_source(const ls_tracer *tr, const Geometry &ge, uint32_t tfirst);   // one of them
+// standing lists: whether frames may be traced from them at all as the handle's options stand (ls_trace.cpp); a geometry's key
+// as of now; a list let go (the policy's back-off; its buffer stays); the policy, at the end of a commit (ls_commit.cpp)
+bool standing_allowed(const ls_tracer *tr);
+StandingKey standing_key(const ls_tracer *tr, const Geometry &ge, uint32_t tfirst);
+void standing_drop(Standing &st);
+int standing_commit(ls_tracer *tr);
 bool shard_sector(const ls_tracer *tr, double &lo_deg, double &hi_deg);   // ls_trace.cpp
 bool inst_inverse(const ls_tracer *tr, const Geometry &ge, double *minv9, double *o3, double *cond);
 int commit_locked(ls_tracer *tr);

@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <vector>
 #include "ls_kernels.h"
+#include "ls_standing.h"
 #include "ls_device.h"
 #include "ls_launch.h"
 #include "ls_tuning.h"
@@ -311,6 +312,113 @@ __device__ __forceinline__ uint32_t lanes_below(unsigned long long mask)
 #define TL_HOST_HOOK(s)
 #endif
 
+// ---- the steps k_project's waves share with the standing list's kernels (ls_standing.hip): the list's build runs the first
+//      two to make its records, a frame traced from the list the last three on them
+// the three corners of a triangle as uploaded -> the sensor frame
+__device__ __forceinline__ void xform_corners(const GeomSource &src, const float (&raw)[9], V3 &v0, V3 &v1, V3 &v2)
+{
+    if (src.xform == 1) {
+        v0 = xform_vertex(src.m, reinterpret_cast<const uint8_t *>(raw));
+        v1 = xform_vertex(src.m, reinterpret_cast<const uint8_t *>(raw + 3));
+        v2 = xform_vertex(src.m, reinterpret_cast<const uint8_t *>(raw + 6));
+    } else if (src.xform == 2) {  // mesh transform is exactly the identity: sensor pose only
+        v0 = xform_vertex_sensor_only(src.m, reinterpret_cast<const uint8_t *>(raw));
+        v1 = xform_vertex_sensor_only(src.m, reinterpret_cast<const uint8_t *>(raw + 3));
+        v2 = xform_vertex_sensor_only(src.m, reinterpret_cast<const uint8_t *>(raw + 6));
+    } else {
+        v0 = {raw[0], raw[1], raw[2]}; v1 = {raw[3], raw[4], raw[5]}; v2 = {raw[6], raw[7], raw[8]};
+    }
+}
+
+// multi-GPU shards: a triangle wholly on the outer side of one of the two vertical planes that bound
+// the shard's azimuth sector (padded; only when the sector is narrower than 180 degrees) cannot be hit
+// by its rays.  Meshes are spatially coherent, so whole waves skip the footprint and the cell tests.
+__device__ __forceinline__ bool outside_sector(const ProjectParams &pp, V3 v0, V3 v1, V3 v2)
+{
+    bool outside = false;
+    if (pp.sector_on) {
+        const float a0 = pp.sec_a[0] * v0.y - pp.sec_a[1] * v0.x, a1 = pp.sec_a[0] * v1.y - pp.sec_a[1] * v1.x,
+                    a2 = pp.sec_a[0] * v2.y - pp.sec_a[1] * v2.x;   // cross(d_a, p): < 0 right of the first boundary
+        const float b0 = v0.x * pp.sec_b[1] - v0.y * pp.sec_b[0], b1 = v1.x * pp.sec_b[1] - v1.y * pp.sec_b[0],
+                    b2 = v2.x * pp.sec_b[1] - v2.y * pp.sec_b[0];   // cross(p, d_b): < 0 left of the second boundary
+        outside = (a0 < 0.0f && a1 < 0.0f && a2 < 0.0f) || (b0 < 0.0f && b1 < 0.0f && b2 < 0.0f);
+    }
+    return outside;
+}
+
+// a footprint too large for one wave goes to the frame's queue; false: the queue is full, the wave expands it after all
+__device__ __forceinline__ bool queue_big(BigItem *__restrict__ big, uint32_t big_capacity, uint32_t *__restrict__ big_count, V3 v0, V3 e1,
+                                          V3 e2, float NgC, uint32_t gid, const Foot &f)
+{
+    bool queued = false;
+    const uint32_t slot = atomicAdd(big_count, 1u);
+    if (slot < big_capacity) {
+        BigItem it;
+        it.v0[0] = v0.x; it.v0[1] = v0.y; it.v0[2] = v0.z;
+        it.e1[0] = e1.x; it.e1[1] = e1.y; it.e1[2] = e1.z;
+        it.e2[0] = e2.x; it.e2[1] = e2.y; it.e2[2] = e2.z;
+        it.NgC = NgC; it.gid = gid; it.i0 = f.i0; it.nch = f.nch;
+        it.h0a = f.h0a; it.na = f.na; it.h0b = f.h0b; it.nb = f.nb;
+        it.pad[0] = it.pad[1] = it.pad[2] = 0;
+        big[slot] = it;
+        queued = true;
+    }
+    return queued;
+}
+
+// a footprint the wave expands itself, into its slot of the wave's staging area
+__device__ __forceinline__ void stage_foot(ProjectLds &lds, uint32_t w, uint32_t slot, V3 v0, V3 e1, V3 e2, float NgC, uint32_t gid,
+                                           const Foot &f)
+{
+    auto &s_tri = lds.tri;
+    auto &s_meta = lds.meta;
+    s_tri[w][0][slot] = v0.x; s_tri[w][1][slot] = v0.y; s_tri[w][2][slot] = v0.z;
+    s_tri[w][3][slot] = e1.x; s_tri[w][4][slot] = e1.y; s_tri[w][5][slot] = e1.z;
+    s_tri[w][6][slot] = e2.x; s_tri[w][7][slot] = e2.y; s_tri[w][8][slot] = e2.z;
+    s_tri[w][9][slot] = NgC;
+    s_meta[w][0][slot] = gid; s_meta[w][1][slot] = f.i0; s_meta[w][2][slot] = f.h0a;
+    s_meta[w][3][slot] = f.na; s_meta[w][4][slot] = f.h0b; s_meta[w][5][slot] = f.nb;
+}
+
+// the wave's staged footprints, packed to the front of its staging area (a lane with cells != 0 staged one in `slot`, its rank
+// among them), expanded: their cells spread evenly over the 64 lanes, each tested exactly.  -> the wave's cell count
+__device__ __forceinline__ uint32_t expand_staged(const ProjectParams &pp, const ChanTables &ct, ProjectLds &lds, uint32_t w, uint32_t lane,
+                                                  uint32_t cells, uint32_t slot, unsigned long long *__restrict__ best)
+{
+    auto &s_tri = lds.tri;
+    auto &s_meta = lds.meta;
+    auto &s_pref = lds.pref;
+    // wave-level inclusive scan of the cell counts
+    const uint32_t incl = wave_inclusive_scan(cells);
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    const uint32_t n_slots = (uint32_t)__popcll(__ballot(cells != 0));
+    if (cells) s_pref[w][slot] = incl - cells;
+    wave_lds_fence();
+    // lane s < n_slots holds the first cell of staged footprint s
+    const uint32_t first = lane < n_slots ? s_pref[w][lane] : 0xFFFFFFFFu;
+    for (uint32_t jb = 0; jb < total; jb += 64u) {
+        // the footprint that owns cell jb + lane, by rank: footprints that started before this chunk +
+        // starts inside the chunk up to this lane (a flag per first cell, then one ballot) - 1
+        lds.flag[w][lane] = 0;
+        wave_lds_fence();
+        if (first - jb < 64u) lds.flag[w][first - jb] = 1;
+        wave_lds_fence();
+        const uint32_t before = (uint32_t)__popcll(__ballot(first < jb));
+        const unsigned long long starts = __ballot(lds.flag[w][lane] != 0);
+        const uint32_t j = jb + lane;
+        if (j < total) {
+            const uint32_t lo = before + lanes_below(starts) + (uint32_t)((starts >> lane) & 1ull) - 1u;
+            const uint32_t m = j - s_pref[w][lo];
+            uint32_t v, h;
+            foot_cell(ct, s_meta[w][1][lo], s_meta[w][2][lo], s_meta[w][3][lo], s_meta[w][4][lo], s_meta[w][5][lo], m, v, h);
+            test_cell(pp, ct, {s_tri[w][0][lo], s_tri[w][1][lo], s_tri[w][2][lo]}, {s_tri[w][3][lo], s_tri[w][4][lo], s_tri[w][5][lo]},
+                      {s_tri[w][6][lo], s_tri[w][7][lo], s_tri[w][8][lo]}, s_tri[w][9][lo], s_meta[w][0][lo], v, h, best);
+        }
+        wave_lds_fence();
+    }
+    return total;
+}
+
 // DEAL (with CULLED): a segment's survivors are dealt to its waves at a stride instead of taken in runs (azimuth shards).  A
 // template argument, not a flag read at run time: behind a uniform branch the list entry's read-ahead (it goes out together
 // with the segment's count) turned into a dependent load and the full raster's culled launch at ten million triangles took
@@ -322,9 +430,6 @@ __device__ __forceinline__ void project_body(const ProjectParams &pp, const Geom
                                              uint32_t big_capacity, uint32_t *__restrict__ big_count,
                                              unsigned long long *__restrict__ stats, const uint32_t *__restrict__ cull_list)
 {
-    auto &s_tri = lds.tri;
-    auto &s_meta = lds.meta;
-    auto &s_pref = lds.pref;
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     TL_BEGIN();
     TL_MARK(tl_0);
@@ -462,29 +567,9 @@ __device__ __forceinline__ void project_body(const ProjectParams &pp, const Geom
     uint32_t cells = 0, slot = 0;
     if (k < src.ntris) {
         V3 v0, v1, v2;
-        if (src.xform == 1) {
-            v0 = xform_vertex(src.m, reinterpret_cast<const uint8_t *>(raw));
-            v1 = xform_vertex(src.m, reinterpret_cast<const uint8_t *>(raw + 3));
-            v2 = xform_vertex(src.m, reinterpret_cast<const uint8_t *>(raw + 6));
-        } else if (src.xform == 2) {  // mesh transform is exactly the identity: sensor pose only
-            v0 = xform_vertex_sensor_only(src.m, reinterpret_cast<const uint8_t *>(raw));
-            v1 = xform_vertex_sensor_only(src.m, reinterpret_cast<const uint8_t *>(raw + 3));
-            v2 = xform_vertex_sensor_only(src.m, reinterpret_cast<const uint8_t *>(raw + 6));
-        } else {
-            v0 = {raw[0], raw[1], raw[2]}; v1 = {raw[3], raw[4], raw[5]}; v2 = {raw[6], raw[7], raw[8]};
-        }
+        xform_corners(src, raw, v0, v1, v2);
         if (pp.debug == 1) { if (v0.x + v1.y + v2.z == 12345.678f) best[0] = 0; return; }
-        // multi-GPU shards: a triangle wholly on the outer side of one of the two vertical planes that bound
-        // the shard's azimuth sector (padded; only when the sector is narrower than 180 degrees) cannot be hit
-        // by its rays.  Meshes are spatially coherent, so whole waves skip the footprint and the cell tests.
-        bool outside = false;
-        if (pp.sector_on) {
-            const float a0 = pp.sec_a[0] * v0.y - pp.sec_a[1] * v0.x, a1 = pp.sec_a[0] * v1.y - pp.sec_a[1] * v1.x,
-                        a2 = pp.sec_a[0] * v2.y - pp.sec_a[1] * v2.x;   // cross(d_a, p): < 0 right of the first boundary
-            const float b0 = v0.x * pp.sec_b[1] - v0.y * pp.sec_b[0], b1 = v1.x * pp.sec_b[1] - v1.y * pp.sec_b[0],
-                        b2 = v2.x * pp.sec_b[1] - v2.y * pp.sec_b[0];   // cross(p, d_b): < 0 left of the second boundary
-            outside = (a0 < 0.0f && a1 < 0.0f && a2 < 0.0f) || (b0 < 0.0f && b1 < 0.0f && b2 < 0.0f);
-        }
+        const bool outside = outside_sector(pp, v0, v1, v2);
         Foot f = {0, 0, 0, 0, 0, 0};
         if (!outside) band(pp, ct, v0, v1, v2, f.i0, f.nch);
         if (pp.debug == 3) { if (f.nch == 0xFFFFFFFFu) best[0] = 0; return; }
@@ -498,65 +583,20 @@ __device__ __forceinline__ void project_body(const ProjectParams &pp, const Geom
             // than kGeomsPerLaunch such geometries -- perm carries the sorted position back to the caller's triangle)
             const uint32_t gid = src.gid_first + (CULLED ? tri_id : (src.perm ? src.perm[k] : k));
             bool queued = false;
-            if (cells > pp.big_cells) {
-                const uint32_t slot = atomicAdd(big_count, 1u);
-                if (slot < big_capacity) {
-                    BigItem it;
-                    it.v0[0] = v0.x; it.v0[1] = v0.y; it.v0[2] = v0.z;
-                    it.e1[0] = e1.x; it.e1[1] = e1.y; it.e1[2] = e1.z;
-                    it.e2[0] = e2.x; it.e2[1] = e2.y; it.e2[2] = e2.z;
-                    it.NgC = NgC; it.gid = gid; it.i0 = f.i0; it.nch = f.nch;
-                    it.h0a = f.h0a; it.na = f.na; it.h0b = f.h0b; it.nb = f.nb;
-                    it.pad[0] = it.pad[1] = it.pad[2] = 0;
-                    big[slot] = it;
-                    queued = true;
-                }
-            }
+            if (cells > pp.big_cells) queued = queue_big(big, big_capacity, big_count, v0, e1, e2, NgC, gid, f);
             if (queued) {
                 cells = 0;
             } else {
                 // the lanes in this branch are exactly the footprints the wave expands itself: they are
                 // staged packed to the front (slot = rank among them), which makes "the footprint that
-                // owns cell j" a rank, computable with a ballot (below)
+                // owns cell j" a rank, computable with a ballot (expand_staged)
                 slot = lanes_below(__ballot(true));
-                s_tri[w][0][slot] = v0.x; s_tri[w][1][slot] = v0.y; s_tri[w][2][slot] = v0.z;
-                s_tri[w][3][slot] = e1.x; s_tri[w][4][slot] = e1.y; s_tri[w][5][slot] = e1.z;
-                s_tri[w][6][slot] = e2.x; s_tri[w][7][slot] = e2.y; s_tri[w][8][slot] = e2.z;
-                s_tri[w][9][slot] = NgC;
-                s_meta[w][0][slot] = gid; s_meta[w][1][slot] = f.i0; s_meta[w][2][slot] = f.h0a;
-                s_meta[w][3][slot] = f.na; s_meta[w][4][slot] = f.h0b; s_meta[w][5][slot] = f.nb;
+                stage_foot(lds, w, slot, v0, e1, e2, NgC, gid, f);
             }
         }
     }
     TL_MARK(tl_3);   // footprints done
-    // wave-level inclusive scan of the cell counts
-    const uint32_t incl = wave_inclusive_scan(cells);
-    total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    const uint32_t n_slots = (uint32_t)__popcll(__ballot(cells != 0));
-    if (cells) s_pref[w][slot] = incl - cells;
-    wave_lds_fence();
-    // lane s < n_slots holds the first cell of staged footprint s
-    const uint32_t first = lane < n_slots ? s_pref[w][lane] : 0xFFFFFFFFu;
-    for (uint32_t jb = 0; jb < total; jb += 64u) {
-        // the footprint that owns cell jb + lane, by rank: footprints that started before this chunk +
-        // starts inside the chunk up to this lane (a flag per first cell, then one ballot) - 1
-        lds.flag[w][lane] = 0;
-        wave_lds_fence();
-        if (first - jb < 64u) lds.flag[w][first - jb] = 1;
-        wave_lds_fence();
-        const uint32_t before = (uint32_t)__popcll(__ballot(first < jb));
-        const unsigned long long starts = __ballot(lds.flag[w][lane] != 0);
-        const uint32_t j = jb + lane;
-        if (j < total) {
-            const uint32_t lo = before + lanes_below(starts) + (uint32_t)((starts >> lane) & 1ull) - 1u;
-            const uint32_t m = j - s_pref[w][lo];
-            uint32_t v, h;
-            foot_cell(ct, s_meta[w][1][lo], s_meta[w][2][lo], s_meta[w][3][lo], s_meta[w][4][lo], s_meta[w][5][lo], m, v, h);
-            test_cell(pp, ct, {s_tri[w][0][lo], s_tri[w][1][lo], s_tri[w][2][lo]}, {s_tri[w][3][lo], s_tri[w][4][lo], s_tri[w][5][lo]},
-                      {s_tri[w][6][lo], s_tri[w][7][lo], s_tri[w][8][lo]}, s_tri[w][9][lo], s_meta[w][0][lo], v, h, best);
-        }
-        wave_lds_fence();
-    }
+    total = expand_staged(pp, ct, lds, w, lane, cells, slot, best);
     if (COUNT && lane == 0 && total) atomicAdd(&stats[0], (unsigned long long)total);
     if (!CULLED) break;
     rank += batch.seg_blocks[gi] * (kBlock / 64);   // the segment's next wave-load that nobody else takes
@@ -1470,6 +1510,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(80))) void k
 }
 
 }  // namespace
+
+// the standing list's kernels and launches: made of the device functions above, so part of this translation unit
+#include "ls_standing.hip"
 
 void launch_project_finish(hipStream_t s, const ProjectParams &pp, unsigned long long *best, const void *big,
                            uint32_t big_capacity, const uint32_t *big_count, uint32_t *block_counts,

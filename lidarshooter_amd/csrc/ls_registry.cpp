@@ -240,6 +240,11 @@ void free_geometry(Geometry &g)
     if (g.d_corners) (void)hipFree(g.d_corners);
     g.d_perm = g.d_idx_sorted = nullptr;
     g.d_boxes = g.d_corners = nullptr;
+    if (g.standing.d_recs) (void)hipFree(g.standing.d_recs);
+    if (g.standing.d_count) (void)hipFree(g.standing.d_count);
+    if (g.standing.h_count) (void)hipHostFree(g.standing.h_count);
+    if (g.standing.ev) (void)hipEventDestroy(g.standing.ev);
+    g.standing = Standing();
     if (g.ev_stage_v) (void)hipEventDestroy(g.ev_stage_v);
     if (g.ev_stage_i) (void)hipEventDestroy(g.ev_stage_i);
     g.d_raw = nullptr;

@@ -97,6 +97,30 @@ ls::ProjectParams project_params(const ls_tracer *tr)
     return pp;
 }
 
+ls::GeomSource project_source(const ls_tracer *tr, const Geometry &ge, uint32_t tfirst)
+{
+    ls::GeomSource src;
+    std::memset(static_cast<void *>(&src), 0, sizeof(src));   // (padding too: the frame graph compares argument bytes)
+    src.verts = static_cast<const uint8_t *>(ge.raw());
+    src.stride = ge.stride;
+    src.idx = ge.idx();
+    src.ntris = ge.n_tris;
+    src.gid_first = tfirst;
+    static const float kIdentity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    src.xform = std::memcmp(ge.affine, kIdentity, sizeof(kIdentity)) == 0 ? 2 : 1;
+    std::memcpy(src.m.a, ge.affine, sizeof(src.m.a));
+    std::memcpy(src.m.rinv, tr->rinv, sizeof(src.m.rinv));
+    std::memcpy(src.m.t, tr->t, sizeof(src.m.t));
+    // block culling data is current (prepare_blocks ran at the commit) unless an update came in since
+    const bool culled = cull_enabled(tr, ge) && ge.d_boxes && ge.d_corners && !ge.order_stale && !ge.bounds_stale &&
+                        cull_size_ok(tr, ge.n_tris);
+    src.perm = culled ? ge.d_perm : nullptr;
+    src.boxes = culled ? ge.d_boxes : nullptr;
+    src.corners = culled ? ge.d_corners : nullptr;
+    if (culled) src.idx = ge.d_idx_sorted;
+    return src;
+}
+
 int project_sources(ls_tracer *tr, std::vector<ls::GeomSource> &srcs, bool &any_culled)
 {
     srcs.clear();
@@ -104,31 +128,96 @@ int project_sources(ls_tracer *tr, std::vector<ls::GeomSource> &srcs, bool &any_
     for (const auto &le : tr->layout) {
         auto it = tr->geoms.find(le.name);
         if (it == tr->geoms.end()) return fail(tr, LS_ERR_NOT_COMMITTED, "geometry removed since the last commit");
-        const Geometry &ge = it->second;
-        ls::GeomSource src;
-        std::memset(static_cast<void *>(&src), 0, sizeof(src));   // (padding too: the frame graph compares argument bytes)
-        src.verts = static_cast<const uint8_t *>(ge.raw());
-        src.stride = ge.stride;
-        src.idx = ge.idx();
-        src.ntris = ge.n_tris;
-        src.gid_first = le.tfirst;
-        static const float kIdentity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-        src.xform = std::memcmp(ge.affine, kIdentity, sizeof(kIdentity)) == 0 ? 2 : 1;
-        std::memcpy(src.m.a, ge.affine, sizeof(src.m.a));
-        std::memcpy(src.m.rinv, tr->rinv, sizeof(src.m.rinv));
-        std::memcpy(src.m.t, tr->t, sizeof(src.m.t));
-        // block culling data is current (prepare_blocks ran at the commit) unless an update came in since
-        const bool culled = cull_enabled(tr, ge) && ge.d_boxes && ge.d_corners && !ge.order_stale && !ge.bounds_stale &&
-                            cull_size_ok(tr, ge.n_tris);
-        src.perm = culled ? ge.d_perm : nullptr;
-        src.boxes = culled ? ge.d_boxes : nullptr;
-        src.corners = culled ? ge.d_corners : nullptr;
-        if (culled) src.idx = ge.d_idx_sorted;
-        any_culled = any_culled || culled;
-        srcs.push_back(src);
+        srcs.push_back(project_source(tr, it->second, le.tfirst));
+        any_culled = any_culled || srcs.back().boxes;
     }
     return LS_OK;
 }
+
+// Frames that count, time their stages, run in rider mode (k_frame fuses the mesh workgroups with the riders) or stop k_project
+// early for a diagnosis are traced from the meshes, as they always were -- and no list is built while one of these holds
+bool standing_allowed(const ls_tracer *tr)
+{
+    static const int debug = tune_int("LS_PROJECT_DEBUG", 0);   // (project_params' pp.debug)
+    return tr->opt_standing && !tr->opt_count && !tr->opt_timing && tr->opt_pipeline != 1 && !debug && use_projection(tr) &&
+           tr->V <= ls::kStandingMaxChannels;
+}
+
+StandingKey standing_key(const ls_tracer *tr, const Geometry &ge, uint32_t tfirst)
+{
+    StandingKey k;
+    std::memset(static_cast<void *>(&k), 0, sizeof(k));
+    k.vert_gen = ge.vert_gen;
+    k.idx_gen = ge.idx_gen;
+    k.sensor_gen = tr->sensor_gen;
+    k.raw = ge.raw();
+    k.idx = ge.idx();
+    k.n_tris = ge.n_tris;
+    k.stride = ge.stride;
+    k.quad = ge.quad ? 1u : 0u;
+    k.az0 = tr->az0;
+    k.naz = tr->naz;
+    k.tfirst = tfirst;
+    k.big_cells = project_params(tr).big_cells;
+    k.margin_az = kProjectMarginDeg;
+    k.margin_elev = kProjectElevMarginDeg;
+    std::memcpy(k.affine, ge.affine, sizeof(k.affine));
+    std::memcpy(k.rinv, tr->rinv, sizeof(k.rinv));
+    std::memcpy(k.t, tr->t, sizeof(k.t));
+    return k;
+}
+
+namespace {
+
+// The geometries of this frame that are traced from their standing lists -- usable, and the key they were built under still the
+// geometry's key -- as batches of up to kGeomsPerLaunch lists; their entries of srcs are emptied, which leaves them out of the
+// culled batch (no k_cull work for them) and of the unculled ones.  any_culled: whether a geometry with bounds is left.
+// graphed: the frame goes out as a captured frame graph.  A list that comes into use there is another launch sequence, i.e. three
+// graphs captured anew, each behind a wait for its stream: a geometry joins only at a frame that finds no graph cached at all (they
+// are about to be captured anyway), or once it has stood for kStandingGraphWait commits.
+void route_standing(ls_tracer *tr, std::vector<ls::GeomSource> &srcs, bool &any_culled, uint64_t &standing_bits, bool graphed)
+{
+    tr->standing_batches.clear();
+    tr->standing_geometries = tr->standing_records = 0;
+    standing_bits = 1469598103934665603ull;
+    // (a frame graph that also holds a caller's work -- ls_frame_graph_begin: a group's collective -- keeps its launch sequence:
+    // a list coming into use would discard the graph and make the caller issue its part again)
+    if (!standing_allowed(tr) || tr->fg_bracket) return;
+    any_culled = false;
+    for (size_t i = 0; i < srcs.size(); ++i) {
+        Geometry &ge = tr->geoms.find(tr->layout[i].name)->second;   // (project_sources found it)
+        Standing &st = ge.standing;
+        bool use = st.state == Standing::kUsable && st.key_valid;
+        if (use) {
+            const StandingKey now = standing_key(tr, ge, tr->layout[i].tfirst);
+            use = std::memcmp(&now, &st.key, sizeof(now)) == 0;
+        }
+        if (use && graphed && !st.in_graphs) {
+            const bool none_cached = !tr->fgraph[0].exec && !tr->fgraph[1].exec && !tr->fgraph[2].exec;
+            if (none_cached || st.same >= kStandingGraphWait) st.in_graphs = true;
+            else use = false;
+        }
+        standing_bits = (standing_bits ^ (use ? 2u : 1u)) * 1099511628211ull;
+        if (!use) {
+            any_culled = any_culled || srcs[i].boxes;
+            continue;
+        }
+        if (tr->standing_batches.empty() || tr->standing_batches.back().n == (uint32_t)ls::kGeomsPerLaunch) {
+            tr->standing_batches.emplace_back();
+            std::memset(static_cast<void *>(&tr->standing_batches.back()), 0, sizeof(ls::StandingBatch));   // (the frame graph compares argument bytes)
+        }
+        ls::standing_batch_add(tr->standing_batches.back(), st.d_recs, st.count);
+        ++st.served;
+        ++tr->standing_geometries;
+        tr->standing_records += (long)st.count;
+        srcs[i].ntris = 0;
+        srcs[i].perm = nullptr;
+        srcs[i].boxes = nullptr;
+        srcs[i].corners = nullptr;
+    }
+}
+
+}  // namespace
 
 namespace {
 
@@ -408,11 +497,13 @@ void frame_graph_free(FrameGraph &fg)
 }
 
 // what decides the SEQUENCE of launches of a frame (their arguments may change from frame to frame: those are patched)
-uint64_t frame_signature(const ls_tracer *tr, const std::vector<ls::GeomSource> &srcs, uint32_t slot)
+// (standing_bits: a bit per geometry for "traced from its standing list", route_standing)
+uint64_t frame_signature(const ls_tracer *tr, const std::vector<ls::GeomSource> &srcs, uint64_t standing_bits, uint32_t slot)
 {
     uint64_t h = 1469598103934665603ull;
     auto mix = [&](uint64_t v) { h = (h ^ v) * 1099511628211ull; };
     mix(tr->fg_bracket ? tr->fg_tag | 1ull : 0ull);
+    mix(standing_bits);
     mix(slot);
     mix(tr->V);
     mix(shard_rays(tr) ? 1u : 0u);
@@ -718,6 +809,8 @@ int trace_once(ls_tracer *tr, uint32_t frame, ls_frame *out, bool readback)
         std::vector<ls::GeomSource> &srcs = tr->project_srcs;
         bool any_culled = false;
         if ((rc = project_sources(tr, srcs, any_culled))) return rc;
+        uint64_t standing_bits = 0;
+        route_standing(tr, srcs, any_culled, standing_bits, multi && tr->opt_frame_graph && !tr->fg_broken);
         // survivor list of this frame's k_cull: one of three (as many frames as can be in flight)
         uint32_t *cull_list = nullptr;
         if (any_culled) {
@@ -786,12 +879,14 @@ int trace_once(ls_tracer *tr, uint32_t frame, ls_frame *out, bool readback)
         } else {
             // LS_OPT_FRAME_GRAPH (three-stream mode): the launches below are captured into this slot's graph, or only
             // described and compared with it; either way the frame then goes out as one graph launch
-            if (multi && tr->opt_frame_graph && !tr->fg_broken && (rc = frame_graph_open(tr, slot, s, frame_signature(tr, srcs, slot)))) return rc;
+            if (multi && tr->opt_frame_graph && !tr->fg_broken && (rc = frame_graph_open(tr, slot, s, frame_signature(tr, srcs, standing_bits, slot)))) return rc;
             // one launch per 16 geometries (the descriptors travel as kernel arguments)
             if (ride) mark(tr, 8, &ev_k1);
             { static const int no_hits = tune_int("LS_PACK_NO_HITS", 0); if (no_hits && !readback) d_hits = nullptr; }   // (experiment: what the 16-byte hit records cost)
             ls::launch_project(s, pp, srcs.data(), (uint32_t)srcs.size(), keys, bigq, tr->big_capacity, big_count, stats, nullptr, cull_list,
                                ev_k0, ev_k1, survivors_hint);
+            // the geometries traced from their standing lists: one launch per kGeomsPerLaunch of them, its grid exact
+            for (const ls::StandingBatch &sb : tr->standing_batches) ls::launch_project_standing(s, pp, sb, keys, bigq, tr->big_capacity, big_count);
             if (!ride) mark(tr, 8);
             // Three-stream mode, a shard of at most kFuseBlocks ray blocks: finish + pack as ONE launch (k_finish_pack: the
             // chained prefix of rider mode; a few hundred workgroups, all resident at once, publish within a microsecond of
@@ -858,6 +953,7 @@ int trace_once(ls_tracer *tr, uint32_t frame, ls_frame *out, bool readback)
         tr->last_d_n = d_n;
     } else {
         if (!tr->bvh_built) return fail(tr, LS_ERR_NOT_COMMITTED, "the BVH engine was selected after the last commit");
+        tr->standing_geometries = tr->standing_records = 0;   // (LS_INFO_STANDING_*: this frame uses no list)
         if ((rc = flush_pipeline(tr))) return rc;
         // the ray queues' heads are zero: the last BVH frame's k_rowcount left them so (a frame that never got that far, or
         // the first one, zeroes them here)
