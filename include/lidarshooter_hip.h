@@ -387,7 +387,11 @@ int ls_tracer_set_hit_buffers(ls_tracer *tr, void *d_hits, uint32_t *d_n_points,
                                  *    ls_frame_graph_begin and ls_frame_graph_end.  With LS_OPT_FRAME_GRAPH a list that comes
                                  *    into use or goes is another launch sequence: the graphs are captured anew, so a list is taken
                                  *    into use there only after 64 unchanged commits, or when no graph is cached.  0: frames always
-                                 *    stream the meshes.  Identical results.  Takes effect at the next frame.               */
+                                 *    stream the meshes.  Identical results.  Takes effect at the next frame.
+                                 *    While the set of geometries traced from their lists stays the same from frame to frame,
+                                 *    the per-ray minimum those lists give is kept too (the STANDING BASE, 8 bytes per ray of
+                                 *    the shard): frames start from it and launch nothing for the standing geometries.  Not
+                                 *    with LS_OPT_FRAME_GRAPH, nor in the two-step trace.  0 switches lists and base off.    */
 int ls_tracer_set_option(ls_tracer *tr, int option, int value);
 
 /* A frame graph that also holds work of the CALLER's (include/lidarshooter_group.h: the frame's collective and the
@@ -448,6 +452,9 @@ int ls_parallel_copy(void *dst, const void *src, uint64_t bytes);
 #define LS_INFO_STANDING_GEOMETRIES 18     /* LS_OPT_STANDING: geometries the last frame traced from their standing lists   */
 #define LS_INFO_STANDING_BUILDS 19         /* standing lists built so far                                                    */
 #define LS_INFO_STANDING_RECORDS 20        /* records in the lists the last frame used                                       */
+#define LS_INFO_STANDING_BASE 21           /* 1: the last frame started from the standing base (LS_OPT_STANDING)             */
+#define LS_INFO_STANDING_BASE_BUILDS 22    /* standing bases built so far                                                    */
+#define LS_INFO_STANDING_BASE_NO_FINISH 23 /* frames so far that started from the base with nothing left to project: no finish pass */
 long ls_get_info(ls_tracer *tr, int what);
 
 /* Mean stage durations (milliseconds, hipEvents on the handle's stream) over every frame recorded

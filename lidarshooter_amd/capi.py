@@ -37,6 +37,7 @@ LS_INFO_BVH_INSTANCED = 7
 LS_INFO_RAY_QUERY_BUILT = 17
 LS_OPT_STANDING = 17
 LS_INFO_STANDING_GEOMETRIES, LS_INFO_STANDING_BUILDS, LS_INFO_STANDING_RECORDS = 18, 19, 20
+LS_INFO_STANDING_BASE, LS_INFO_STANDING_BASE_BUILDS, LS_INFO_STANDING_BASE_NO_FINISH = 21, 22, 23
 LS_INFO_CONCURRENT_STREAMS, LS_INFO_PIPELINE_MODE, LS_INFO_DEVICE_STATUS, LS_INFO_HOST_THREADS, LS_INFO_AZIMUTH_COUNT = 1, 2, 3, 4, 5
 ENGINE_AUTO, ENGINE_BVH, ENGINE_PROJECTION = 0, 1, 2
 STAGES = ("transform", "morton", "sort", "leaves", "range_tree", "hierarchy", "trace", "trace_aux", "pack")

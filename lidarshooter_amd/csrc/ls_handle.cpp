@@ -239,7 +239,7 @@ static int sensor_changed(ls_tracer *tr, SensorFields &before)
     tr->naz = tr->H;
     check_projection_ok(tr);
     if (tr->engine == 2 && !tr->projection_ok) tr->engine = 0;   // (the projection engine was asked for and no longer applies)
-    tr->keys_armed = tr->keys_b_armed = tr->keys_c_armed = false;
+    tr->keys_arm[0] = tr->keys_arm[1] = tr->keys_arm[2] = 0;
     tr->traced = false;
     tr->pack_split = 0;
     tr->begin_open = tr->progress_active = false;
@@ -383,6 +383,8 @@ void ls_tracer_destroy(ls_tracer *tr)
     hit_attr_release(tr);
     release(tr->best_keys_b); release(tr->big_queue_b); release(tr->points_b); release(tr->hits_b); release(tr->pack_status); release(tr->pack_status_ms);
     release(tr->best_keys_c); release(tr->big_queue_c); release(tr->points_c); release(tr->hits_c);
+    release(tr->base.keys); release(tr->base.big); release(tr->base.counts);
+    if (tr->base.counter) (void)hipFree(tr->base.counter);
     if (tr->d_n_points_b) (void)hipFree(tr->d_n_points_b);
     if (tr->d_n_points_c) (void)hipFree(tr->d_n_points_c);
     if (tr->ev_main) (void)hipEventDestroy(tr->ev_main);
@@ -438,9 +440,7 @@ int ls_tracer_set_shard(ls_tracer *tr, uint32_t first_az, uint32_t n_az)
     ++tr->sensor_gen;   // (the standing lists' keys)
     __atomic_store_n(tr->h_status + 1, 0u, __ATOMIC_RELAXED);   // (the survivor hint spoke for the old shard; a frame still running may write it once more: a hint, not a promise)
     tr->traced = false;
-    tr->keys_armed = false;
-    tr->keys_b_armed = false;
-    tr->keys_c_armed = false;
+    tr->keys_arm[0] = tr->keys_arm[1] = tr->keys_arm[2] = 0;
     return LS_OK;
 }
 
@@ -503,6 +503,9 @@ long ls_get_info(ls_tracer *tr, int what)
     case LS_INFO_STANDING_GEOMETRIES: return tr->standing_geometries;
     case LS_INFO_STANDING_BUILDS: return tr->standing_builds;
     case LS_INFO_STANDING_RECORDS: return tr->standing_records;
+    case LS_INFO_STANDING_BASE: return tr->base_in_use;
+    case LS_INFO_STANDING_BASE_BUILDS: return tr->base_builds;
+    case LS_INFO_STANDING_BASE_NO_FINISH: return tr->base_finish_skipped;
     default: return fail(tr, LS_ERR_INVALID_ARGUMENT, "unknown info key");
     }
 }
@@ -623,7 +626,7 @@ int ls_tracer_set_option(ls_tracer *tr, int option, int value)
     }
     case LS_OPT_STANDING:
         if (value < 0 || value > 1) return fail(tr, LS_ERR_INVALID_ARGUMENT, "LS_OPT_STANDING: 0 or 1");
-        tr->opt_standing = value;   // (a frame looks at it as it is issued; lists already built stay and are used again with 1)
+        tr->opt_standing = value;   // (a frame looks at it as it is issued; lists already built -- and a base -- stay and are used again with 1)
         return LS_OK;
     case LS_OPT_ENGINE:
         if (value < 0 || value > 2) return fail(tr, LS_ERR_INVALID_ARGUMENT, "engine must be 0 (auto), 1 (BVH) or 2 (projection)");

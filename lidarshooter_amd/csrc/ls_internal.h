@@ -143,6 +143,33 @@ struct DevBuf {
     size_t cap = 0;  // elements
 };
 
+// The standing base (ls_trace.cpp, next to route_standing): the per-ray minimum that the routed standing lists
+// give -- the same one every frame while the set stands, atomicMin does not depend on order -- kept once, 8 bytes per ray of the
+// shard.  A frame whose routed set is the base's starts from it (its keys are armed with it) instead of from all ones, and
+// launches no k_project_standing.  It belongs to one exact set: the frame's standing_bits and every routed geometry's key.
+// Built at the first eligible frame that finds its set equal to that of the `wait` - 1 frames before it; one that is dropped
+// before it has served kBaseBreakEven frames doubles `wait` (at most kStandingMaxWait), one that has served them puts it back.
+// frames: a build is ~28 us of device work behind a drained pipeline (the standing launch 9 - 14, its finish pass 5 - 6, a memset and a
+// copy of 4 MB per slot) and about twenty host calls, ~53 us if nothing of the two overlaps; a headline frame saves 6.4 us, one with
+// something left to project 4.9: 8 - 11 frames (EXPERIMENTS.md E28).  8 ships.
+constexpr uint64_t kBaseBreakEven = 8;
+struct StandingBase {
+    DevBuf<unsigned long long> keys;     // the base itself
+    DevBuf<uint8_t> big;                 // its build's big-footprint queue (big_capacity items) ...
+    uint32_t *counter = nullptr;         // ... and counter row (kCounterSlotWords words, zero between builds)
+    DevBuf<uint32_t> counts;             // hits per 256-ray block of the base, left by the build's finish pass
+    uint32_t gen = 0;                    // 0: none; else the generation the slots' arming words speak of
+    uint32_t next_gen = 2;
+    uint64_t bits = 0;                   // the set it was built for ...
+    std::vector<StandingKey> set;
+    uint64_t prev_bits = 0;              // ... and the set of the eligible frame issued last (none: empty)
+    std::vector<StandingKey> prev;
+    uint32_t same = 0;                   // eligible frames in a row with the set `prev`
+    uint32_t wait = kStandingFirstWait;
+    uint64_t served = 0;                 // frames that started from the current base
+    bool failed = false;                 // no memory for it: nothing is tried again until the set changes
+};
+
 // a small device table a call refreshes when it finds it out of date: uploaded through a pinned staging block of its own, so that
 // the caller's stream never waits for the host (T: plain data, compared byte for byte)
 template <typename T>
@@ -198,7 +225,10 @@ struct ls_tracer {
     lsi::DevBuf<uint8_t> big_queue;             // projection engine: triangles with very large footprints
     uint32_t big_capacity = 0;
     uint32_t *d_big_count = nullptr;
-    bool keys_armed = false;               // best_keys all ~0, counters 0 (k_pack re-arms them every frame)
+    // what each slot's keys hold between frames (slot 0: best_keys, 1: best_keys_b, 2: best_keys_c; k_pack re-arms them every
+    // frame): 0 unknown, 1 all ones, g >= 2 the standing base of generation g.  Slot 0's word also speaks for the counters: 0 there
+    // sends the next frame through launch_project_init
+    uint32_t keys_arm[3] = {0, 0, 0};
     uint32_t frame_parity = 0;             // which of the two block-counter arrays this frame adds into
     bool scene_materialized = false;       // verts / tris hold the transformed scene of the last commit
     struct LayoutEntry { std::string name; uint32_t vfirst, tfirst; };
@@ -221,7 +251,6 @@ struct ls_tracer {
     lsi::DevBuf<unsigned long long> best_keys_b; // parity 1 twins of best_keys, big_queue, points, hits, d_n_points
     lsi::DevBuf<uint8_t> big_queue_b, points_b, hits_b;
     uint32_t *d_n_points_b = nullptr;
-    bool keys_b_armed = false;
     // LS_OPT_PIPELINE = 2: whole frames rotate over three streams (three frames in flight); slot 0 / 1 use
     // the buffers above, slot 2 the ones below; every slot has its own block-count array
     hipStream_t slot_stream[3] = {nullptr, nullptr, nullptr};
@@ -235,7 +264,6 @@ struct ls_tracer {
     lsi::DevBuf<unsigned long long> best_keys_c;
     lsi::DevBuf<uint8_t> big_queue_c, points_c, hits_c;
     uint32_t *d_n_points_c = nullptr;
-    bool keys_c_armed = false;
     // three-stream mode, small shards: finish + pack of a frame as ONE launch with the chained prefix (k_finish_pack); per slot
     // the status words of its ray blocks and, behind them, the tag word the kernel itself steps (FinishPackArgs::epoch_word)
     lsi::DevBuf<unsigned long long> pack_status_ms;
@@ -249,6 +277,10 @@ struct ls_tracer {
     uint64_t sensor_gen = 0;
     std::vector<ls::StandingBatch> standing_batches;
     long standing_geometries = 0, standing_records = 0, standing_builds = 0;
+    lsi::StandingBase base;                    // the routed lists' per-ray minimum, kept (StandingBase)
+    std::vector<lsi::StandingKey> routed_keys; // the keys of the geometries route_standing routed (scratch of trace_locked)
+    long base_in_use = 0, base_builds = 0;     // LS_INFO_STANDING_BASE (the last frame started from it), LS_INFO_STANDING_BASE_BUILDS
+    long base_finish_skipped = 0;              // LS_INFO_STANDING_BASE_NO_FINISH: frames that started from it and launched no finish pass
     ls::RangeTree rt{};
     uint32_t range_entries = 0;
     uint32_t *d_maxabs = nullptr;

@@ -418,7 +418,8 @@ void launch_pack(hipStream_t s, const SensorTables &tb, float *t, uint32_t *gid,
 void launch_pack_keys(hipStream_t s, const SensorTables &tb, unsigned long long *keys, float *t, uint32_t *gid,
                       const uint32_t *block_counts, uint32_t *next_block_counts, uint32_t *big_count,
                       const GeomTable &gt, uint8_t *points32, void *hits, uint32_t *n_points, uint32_t compact = 0,
-                      const ProgressArgs *progress = nullptr, uint32_t rays_per_lane = 1);
+                      const ProgressArgs *progress = nullptr, uint32_t rays_per_lane = 1,
+                      const unsigned long long *base = nullptr);   // base: what the keys are re-armed to (nullptr: all ones)
 // projection engine: per-geometry streaming kernel, big-footprint kernel, resolve (+ row counts)
 size_t project_big_item_bytes();
 void launch_project_init(hipStream_t s, const ProjectParams &pp, unsigned long long *best, uint32_t *big_count,
@@ -446,6 +447,7 @@ struct FinishPackArgs {
     uint32_t n_blocks;              // ceil(rays / 256)
     uint32_t compact;               // points as 16-byte (x, y, z, ring) records (LS_OPT_HOST_OUTPUT = 2)
     uint32_t *cull_hint;            // as ProgressArgs::cull_hint
+    const unsigned long long *base; // what the keys are re-armed to (nullptr: all ones; rider mode passes nullptr)
 };
 // cull_list (nullable): room for project_cull_entries() words; the groups that survive k_cull are appended there per
 // geometry (counts in big_count[kCullCountAt + i], re-armed wherever big_count[0] is) and the waves of the culled

@@ -1198,6 +1198,8 @@ __global__ __launch_bounds__(kBlock) void k_rowcount(const uint32_t *__restrict_
 // FROM_KEYS (projection engine): the per-ray results are the 64-bit closest-hit keys; the kernel also
 // writes the dense t / gid arrays, re-arms the keys, zeroes the OTHER frame-parity's block counters
 // and the big-triangle queue length, so that a frame needs no memset and no resolve pass.
+// arm_to (nullable): what the keys are re-armed TO -- the kept per-ray minimum of the standing geometries (ls_trace.cpp, the
+// standing base) instead of all ones; a key that already equals it is left alone.
 template <bool FROM_KEYS>
 __global__ __launch_bounds__(kBlock) void k_pack(SensorTables tb, float *__restrict__ t_io, uint32_t *__restrict__ gid_io,
                                                  unsigned long long *__restrict__ keys,
@@ -1205,7 +1207,7 @@ __global__ __launch_bounds__(kBlock) void k_pack(SensorTables tb, float *__restr
                                                  uint32_t *__restrict__ next_block_counts, uint32_t *__restrict__ big_count,
                                                  GeomTable gt, float4 *__restrict__ points, uint4 *__restrict__ hits,
                                                  uint32_t *__restrict__ n_points, uint32_t compact, uint32_t block0, uint32_t n_blocks,
-                                                 ProgressArgs pg)
+                                                 ProgressArgs pg, const unsigned long long *__restrict__ arm_to)
 {
     // (block0, n_blocks: the launch covers ray blocks [block0, block0 + gridDim.x) of n_blocks -- a synchronous frame that
     // reports its progress to the host packs its two halves in two launches, ls_trace_scene_expand)
@@ -1222,10 +1224,11 @@ __global__ __launch_bounds__(kBlock) void k_pack(SensorTables tb, float *__restr
     const uint32_t q = block * kBlock + threadIdx.x;
     uint32_t gid = kInvalid;
     float t = -1.0f;
-    unsigned long long key = ~0ull;
+    unsigned long long key = ~0ull, arm = ~0ull;
     if (q < nq) {
         if (FROM_KEYS) {
             key = keys[q];
+            if (arm_to) arm = arm_to[q];
             // no dense per-ray arrays on this path: ls_debug_dense_hits rebuilds them from the records
         } else {
             gid = gid_io[q];
@@ -1255,8 +1258,8 @@ __global__ __launch_bounds__(kBlock) void k_pack(SensorTables tb, float *__restr
     for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
 
     if (FROM_KEYS) {
+        if (key != arm) keys[q] = arm;   // re-arm (a key nobody touched is armed already)
         if (key != ~0ull) {
-            keys[q] = ~0ull;   // re-arm (a key nobody touched is armed already)
             gid = (uint32_t)key;
             t = __uint_as_float((uint32_t)(key >> 32));
         }
@@ -1370,7 +1373,7 @@ __global__ __launch_bounds__(kBlock) void k_pack_wide(SensorTables tb, unsigned 
                                                       const uint32_t *__restrict__ block_counts, uint32_t *__restrict__ next_block_counts,
                                                       uint32_t *__restrict__ big_count, GeomTable gt, float4 *__restrict__ points,
                                                       uint4 *__restrict__ hits, uint32_t *__restrict__ n_points, uint32_t compact,
-                                                      uint32_t n_blocks, uint32_t *cull_hint)
+                                                      uint32_t n_blocks, uint32_t *cull_hint, const unsigned long long *__restrict__ arm_to)
 {
     __shared__ uint32_t s_part[kBlock / 64];
     __shared__ uint32_t s_cnt[RPT][kBlock / 64];
@@ -1379,7 +1382,7 @@ __global__ __launch_bounds__(kBlock) void k_pack_wide(SensorTables tb, unsigned 
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const uint32_t wg = blockIdx.x, block0 = wg * RPT;           // the first of this workgroup's 256-ray blocks
     const uint32_t q0 = block0 * kBlock + threadIdx.x;
-    unsigned long long key[RPT];
+    unsigned long long key[RPT], arm[RPT];
     uint32_t v[RPT], h[RPT];
     float st[RPT], ctv[RPT];
     float2 cs[RPT];
@@ -1387,6 +1390,11 @@ __global__ __launch_bounds__(kBlock) void k_pack_wide(SensorTables tb, unsigned 
     for (uint32_t j = 0; j < RPT; ++j) {
         const uint32_t q = q0 + j * kBlock;
         key[j] = q < nq ? keys[q] : ~0ull;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < RPT; ++j) {   // (what the keys are re-armed to: requested with the keys, k_pack)
+        const uint32_t q = q0 + j * kBlock;
+        arm[j] = arm_to && q < nq ? arm_to[q] : ~0ull;
     }
 #pragma unroll
     for (uint32_t j = 0; j < RPT; ++j) {
@@ -1413,7 +1421,7 @@ __global__ __launch_bounds__(kBlock) void k_pack_wide(SensorTables tb, unsigned 
     unsigned long long m[RPT];
 #pragma unroll
     for (uint32_t j = 0; j < RPT; ++j) {
-        if (key[j] != ~0ull) keys[q0 + j * kBlock] = ~0ull;   // re-arm
+        if (key[j] != arm[j]) keys[q0 + j * kBlock] = arm[j];   // re-arm
         m[j] = __ballot(key[j] != ~0ull);
         if (lane == 0) s_cnt[j][w] = (uint32_t)__popcll(m[j]);
     }
@@ -1800,13 +1808,14 @@ void launch_pack(hipStream_t s, const SensorTables &tb, float *t, uint32_t *gid,
     hipLaunchKernelGGL(k_pack<false>, dim3(blocks_for(nq)), dim3(kBlock), 0, s, tb, t, gid,
                        static_cast<unsigned long long *>(nullptr), block_counts, static_cast<uint32_t *>(nullptr),
                        static_cast<uint32_t *>(nullptr), gt, reinterpret_cast<float4 *>(points32),
-                       reinterpret_cast<uint4 *>(hits), n_points, compact, 0u, blocks_for(nq), ProgressArgs{nullptr, 0u, 0u, nullptr});
+                       reinterpret_cast<uint4 *>(hits), n_points, compact, 0u, blocks_for(nq), ProgressArgs{nullptr, 0u, 0u, nullptr},
+                       static_cast<const unsigned long long *>(nullptr));
 }
 
 void launch_pack_keys(hipStream_t s, const SensorTables &tb, unsigned long long *keys, float *t, uint32_t *gid,
                       const uint32_t *block_counts, uint32_t *next_block_counts, uint32_t *big_count,
                       const GeomTable &gt, uint8_t *points32, void *hits, uint32_t *n_points, uint32_t compact,
-                      const ProgressArgs *progress, uint32_t rays_per_lane)
+                      const ProgressArgs *progress, uint32_t rays_per_lane, const unsigned long long *base)
 {
     const uint32_t nq = tb.V * tb.naz;
     if (!nq) return;
@@ -1814,18 +1823,18 @@ void launch_pack_keys(hipStream_t s, const SensorTables &tb, unsigned long long 
     auto launch = [&](uint32_t block0, uint32_t count) {
         launch_k(k_pack<true>, dim3(count), dim3(kBlock), 0, s, tb, t, gid, keys, block_counts, next_block_counts, big_count, gt,
                  reinterpret_cast<float4 *>(points32), reinterpret_cast<uint4 *>(hits), n_points, compact, block0, nb,
-                 progress ? *progress : ProgressArgs{nullptr, 0u, 0u, nullptr});
+                 progress ? *progress : ProgressArgs{nullptr, 0u, 0u, nullptr}, base);
     };
     if (rays_per_lane >= 2u && (!progress || !progress->host) && compact != 2u) {
         uint32_t *hint = progress ? progress->cull_hint : nullptr;
         float4 *p4 = reinterpret_cast<float4 *>(points32);
         uint4 *h4 = reinterpret_cast<uint4 *>(hits);
         if (rays_per_lane >= 8u)
-            launch_k(k_pack_wide<8>, dim3((nb + 7u) / 8u), dim3(kBlock), 0, s, tb, keys, block_counts, next_block_counts, big_count, gt, p4, h4, n_points, compact, nb, hint);
+            launch_k(k_pack_wide<8>, dim3((nb + 7u) / 8u), dim3(kBlock), 0, s, tb, keys, block_counts, next_block_counts, big_count, gt, p4, h4, n_points, compact, nb, hint, base);
         else if (rays_per_lane >= 4u)
-            launch_k(k_pack_wide<4>, dim3((nb + 3u) / 4u), dim3(kBlock), 0, s, tb, keys, block_counts, next_block_counts, big_count, gt, p4, h4, n_points, compact, nb, hint);
+            launch_k(k_pack_wide<4>, dim3((nb + 3u) / 4u), dim3(kBlock), 0, s, tb, keys, block_counts, next_block_counts, big_count, gt, p4, h4, n_points, compact, nb, hint, base);
         else
-            launch_k(k_pack_wide<2>, dim3((nb + 1u) / 2u), dim3(kBlock), 0, s, tb, keys, block_counts, next_block_counts, big_count, gt, p4, h4, n_points, compact, nb, hint);
+            launch_k(k_pack_wide<2>, dim3((nb + 1u) / 2u), dim3(kBlock), 0, s, tb, keys, block_counts, next_block_counts, big_count, gt, p4, h4, n_points, compact, nb, hint, base);
         return;
     }
     if (!progress || !progress->host) { launch(0u, nb); return; }

@@ -1317,7 +1317,8 @@ __global__ __launch_bounds__(kBlock) void k_project_finish_wide(ProjectParams pp
 // each tagged with the frame's epoch (no reset between frames).  A workgroup only ever waits for
 // lower-numbered ones of its own set, which the dispatcher started earlier (the chained-scan premise).
 // ------------------------------------------------------------------------------------------
-template <bool COUNT>
+// BASED: the keys are re-armed to fa.base, the standing base (ls_trace.cpp), where they differ from it -- else to all ones
+template <bool COUNT, bool BASED>
 __device__ __forceinline__ void finish_pack_body(const ProjectParams &pp, const FinishPackArgs &fa, uint32_t block_idx,
                                                  uint32_t *scratch /* LDS, >= 560 words */,
                                                  unsigned long long *__restrict__ stats)
@@ -1341,7 +1342,12 @@ __device__ __forceinline__ void finish_pack_body(const ProjectParams &pp, const 
     V3 d = {0.f, 0.f, 0.f};
     if (q < n) {
         key = best[q];
-        best[q] = ~0ull;   // re-armed for the frame after the next
+        if (BASED) {
+            const unsigned long long arm = fa.base[q];   // (requested with the key)
+            if (key != arm) best[q] = arm;
+        } else {
+            best[q] = ~0ull;   // re-armed for the frame after the next
+        }
         v = q / tb.naz;
         h = tb.az0 + (q - v * tb.naz);
         // LidarDevice.cpp:310-316: d = (sin(theta)cos(phi), sin(theta)sin(phi), cos(theta))
@@ -1483,11 +1489,11 @@ __device__ __forceinline__ void finish_pack_body(const ProjectParams &pp, const 
     if (hits) hits[dst] = make_uint4(v * tb.H + h, fa.gt.geom_ids[lo], (gid - fa.gt.tri_first[lo]) >> fa.gt.prim_shift[lo], __float_as_uint(t));
 }
 
-template <bool COUNT>
+template <bool COUNT, bool BASED>
 __global__ __launch_bounds__(kBlock) void k_finish_pack(ProjectParams pp, FinishPackArgs fa, unsigned long long *__restrict__ stats)
 {
     __shared__ uint32_t scratch[576];
-    finish_pack_body<COUNT>(pp, fa, blockIdx.x, scratch, stats);
+    finish_pack_body<COUNT, BASED>(pp, fa, blockIdx.x, scratch, stats);
 }
 
 // One launch per frame: the workgroups of this frame's k_project and, from workgroup fp_start on, those
@@ -1503,7 +1509,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(80))) void k
     extern __shared__ __attribute__((aligned(16))) float s_chan[];
     const uint32_t rel = blockIdx.x - fp_start;
     if (rel < fa.n_blocks)
-        finish_pack_body<false>(pp, fa, rel, reinterpret_cast<uint32_t *>(&lds), nullptr);
+        finish_pack_body<false, false>(pp, fa, rel, reinterpret_cast<uint32_t *>(&lds), nullptr);   // (rider mode re-arms to all ones)
     else
         project_body<false, LDS_TABLES, MULTI, CULLED>(pp, batch, blockIdx.x < fp_start ? blockIdx.x : blockIdx.x - fa.n_blocks, lds, s_chan, best,
                                                big, big_capacity, big_count, nullptr, cull_list);
@@ -1912,8 +1918,9 @@ void launch_corners(hipStream_t s, const uint8_t *verts, uint32_t stride, const 
 void launch_finish_pack(hipStream_t s, const ProjectParams &pp, const FinishPackArgs &fa, unsigned long long *stats)
 {
     if (!fa.n_blocks) return;
-    if (stats) hipLaunchKernelGGL(k_finish_pack<true>, dim3(fa.n_blocks), dim3(kBlock), 0, s, pp, fa, stats);
-    else launch_k(k_finish_pack<false>, dim3(fa.n_blocks), dim3(kBlock), 0, s, pp, fa, stats);
+    if (stats) hipLaunchKernelGGL((k_finish_pack<true, false>), dim3(fa.n_blocks), dim3(kBlock), 0, s, pp, fa, stats);   // (a counting frame starts from no base)
+    else if (fa.base) launch_k(k_finish_pack<false, true>, dim3(fa.n_blocks), dim3(kBlock), 0, s, pp, fa, stats);
+    else launch_k(k_finish_pack<false, false>, dim3(fa.n_blocks), dim3(kBlock), 0, s, pp, fa, stats);
 }
 
 }  // namespace ls

@@ -178,6 +178,7 @@ namespace {
 void route_standing(ls_tracer *tr, std::vector<ls::GeomSource> &srcs, bool &any_culled, uint64_t &standing_bits, bool graphed)
 {
     tr->standing_batches.clear();
+    tr->routed_keys.clear();
     tr->standing_geometries = tr->standing_records = 0;
     standing_bits = 1469598103934665603ull;
     // (a frame graph that also holds a caller's work -- ls_frame_graph_begin: a group's collective -- keeps its launch sequence:
@@ -192,6 +193,7 @@ void route_standing(ls_tracer *tr, std::vector<ls::GeomSource> &srcs, bool &any_
             const StandingKey now = standing_key(tr, ge, tr->layout[i].tfirst);
             use = std::memcmp(&now, &st.key, sizeof(now)) == 0;
         }
+        if (use && !graphed) tr->routed_keys.push_back(st.key);   // (what a standing base of this set is known by)
         if (use && graphed && !st.in_graphs) {
             const bool none_cached = !tr->fgraph[0].exec && !tr->fgraph[1].exec && !tr->fgraph[2].exec;
             if (none_cached || st.same >= kStandingGraphWait) st.in_graphs = true;
@@ -215,6 +217,117 @@ void route_standing(ls_tracer *tr, std::vector<ls::GeomSource> &srcs, bool &any_
         srcs[i].boxes = nullptr;
         srcs[i].corners = nullptr;
     }
+}
+
+// ---- the standing base (ls_internal.h: StandingBase) ------------------------------------------------------------------
+// While the routed set stands, every frame runs the same records through the same triangle tests and atomicMins them into keys
+// that the pack has just reset: the same per-ray minimum every time, whatever the order.  So it is kept, and a frame's final key
+// is min(base, keys of everything else), bit for bit.
+
+void base_drop(StandingBase &b)
+{
+    if (b.gen) b.wait = b.served < kBaseBreakEven ? std::min(b.wait * 2u, kStandingMaxWait) : kStandingFirstWait;
+    b.gen = 0;
+    b.served = 0;
+    b.same = 0;
+}
+
+// room for `need` elements, contents lost; false when there is no memory (the base is an optimisation: the frame goes on without)
+template <typename T>
+bool base_room(DevBuf<T> &buf, size_t need)
+{
+    if (need <= buf.cap) return true;
+    if (buf.p) (void)hipFree(buf.p);   // (waits for whatever still reads it)
+    buf.p = nullptr;
+    buf.cap = 0;
+    if (hipMalloc(reinterpret_cast<void **>(&buf.p), need * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        buf.p = nullptr;
+        return false;
+    }
+    buf.cap = need;
+    return true;
+}
+
+// the base of the set route_standing has just routed, by the launches a frame would use, on the handle's stream: behind every
+// frame in flight (their packs may still read the old base in the same buffer), ahead of every later frame of any slot stream
+// (main_epoch).  The finish pass folds the queued big footprints in and leaves the base's hits per ray block in b.counts.  No
+// host wait.
+int base_build(ls_tracer *tr, const ls::ProjectParams &pp, uint64_t bits)
+{
+    StandingBase &b = tr->base;
+    int rc;
+    if ((rc = order_after_projects(tr))) return rc;
+    const size_t nr = shard_rays(tr);
+    bool ok = base_room(b.keys, nr) && base_room(b.big, (size_t)tr->big_capacity * ls::project_big_item_bytes()) && base_room(b.counts, (nr + 255) / 256);
+    if (ok && !b.counter) {
+        if (hipMalloc(reinterpret_cast<void **>(&b.counter), ls::kCounterSlotWords * sizeof(uint32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            b.counter = nullptr;
+            ok = false;
+        } else {
+            LS_HIP(hipMemsetAsync(b.counter, 0, ls::kCounterSlotWords * sizeof(uint32_t), tr->stream));
+        }
+    }
+    if (!ok) { b.failed = true; return LS_OK; }   // nothing is tried again until the set changes
+    LS_HIP(hipMemsetAsync(b.keys.p, 0xFF, nr * 8, tr->stream));
+    for (const ls::StandingBatch &sb : tr->standing_batches) ls::launch_project_standing(tr->stream, pp, sb, b.keys.p, b.big.p, tr->big_capacity, b.counter);
+    ls::launch_project_finish(tr->stream, pp, b.keys.p, b.big.p, tr->big_capacity, b.counter, b.counts.p, nullptr, 1u);
+    LS_HIP(hipMemsetAsync(b.counter, 0, sizeof(uint32_t), tr->stream));   // (the queue length: the next build starts from an empty queue)
+    LS_HIP(hipGetLastError());
+    ++tr->main_epoch;   // every slot stream orders its next frame after the build
+    b.gen = b.next_gen;
+    if (++b.next_gen < 2u) b.next_gen = 2u;
+    b.bits = bits;
+    b.set = tr->routed_keys;
+    b.served = 0;
+    ++tr->base_builds;
+    return LS_OK;
+}
+
+// Whether this frame starts from the base (-> base: its keys, else nullptr).  eligible: the frame could use one at all -- it is
+// no rider, counting, timing, progress or graphed frame, and route_standing routed something.  A frame that is not leaves the
+// base alone: it is known by its set, and the next eligible frame with that set uses it again.
+int base_for_frame(ls_tracer *tr, const ls::ProjectParams &pp, bool eligible, uint64_t bits, const unsigned long long *&base)
+{
+    StandingBase &b = tr->base;
+    base = nullptr;
+    tr->base_in_use = 0;
+    if (!eligible) { b.same = 0; return LS_OK; }
+    const std::vector<StandingKey> &now = tr->routed_keys;
+    auto is_now = [&](uint64_t bits2, const std::vector<StandingKey> &set) {
+        return bits2 == bits && set.size() == now.size() && std::memcmp(static_cast<const void *>(set.data()), static_cast<const void *>(now.data()), now.size() * sizeof(StandingKey)) == 0;
+    };
+    if (b.gen && !is_now(b.bits, b.set)) base_drop(b);
+    if (!b.gen) {
+        if (b.same && is_now(b.prev_bits, b.prev)) {
+            if (b.same < 0xFFFFFFFFu) ++b.same;
+        } else {
+            b.prev_bits = bits;
+            b.prev = now;
+            b.same = 1;
+            b.failed = false;
+        }
+        if (b.failed || b.same < b.wait) return LS_OK;
+        if (const int rc = base_build(tr, pp, bits)) return rc;
+        if (!b.gen) return LS_OK;
+    }
+    base = b.keys.p;
+    ++b.served;
+    tr->base_in_use = 1;
+    return LS_OK;
+}
+
+// the slot's keys as the frame about to be projected wants them -- all ones (want = 1), or the base of generation want --, on the
+// frame's stream.  The frame's pack re-arms them to the same, so a stream of like frames never comes through the copy.
+int arm_keys(ls_tracer *tr, uint32_t slot, unsigned long long *keys, uint32_t want, hipStream_t s)
+{
+    if (tr->keys_arm[slot] == want) return LS_OK;
+    const size_t bytes = (size_t)shard_rays(tr) * 8;
+    if (want == 1u) LS_HIP(hipMemsetAsync(keys, 0xFF, bytes, s));
+    else LS_HIP(hipMemcpyAsync(keys, tr->base.keys.p, bytes, hipMemcpyDeviceToDevice, s));
+    tr->keys_arm[slot] = want;
+    return LS_OK;
 }
 
 }  // namespace
@@ -357,12 +470,12 @@ int ensure_outputs(ls_tracer *tr)
     {
         const size_t c0 = tr->row_counts.cap;
         if ((rc = ensure(tr, tr->row_counts, 4 * ((nr + 255) / 256) + 8))) return rc;  // two frame-parity arrays (+ two: three-stream mode)
-        if (tr->row_counts.cap != c0) tr->keys_armed = false;
+        if (tr->row_counts.cap != c0) tr->keys_arm[0] = 0;
     }
     if (use_projection(tr)) {
         const size_t cap0 = tr->best_keys.cap;
         if ((rc = ensure(tr, tr->best_keys, nr))) return rc;
-        if (tr->best_keys.cap != cap0) tr->keys_armed = false;
+        if (tr->best_keys.cap != cap0) tr->keys_arm[0] = 0;
         if (!tr->big_queue.p) {
             tr->big_capacity = 2048u;  // culled per 256-ray workgroup in k_project_finish; overflow is expanded in place
             if ((rc = ensure(tr, tr->big_queue, (size_t)tr->big_capacity * ls::project_big_item_bytes()))) return rc;
@@ -377,7 +490,7 @@ int ensure_outputs(ls_tracer *tr)
     if (tr->opt_pipeline == 2 && use_projection(tr)) {
         const size_t cap0 = tr->best_keys_c.cap;
         if ((rc = ensure(tr, tr->best_keys_c, nr))) return rc;
-        if (tr->best_keys_c.cap != cap0) tr->keys_c_armed = false;
+        if (tr->best_keys_c.cap != cap0) tr->keys_arm[2] = 0;
         if (!tr->big_queue_c.p && (rc = ensure(tr, tr->big_queue_c, (size_t)tr->big_capacity * ls::project_big_item_bytes()))) return rc;
         if (!tr->ext_points) {
             if ((rc = ensure(tr, tr->points_c, nr * 32))) return rc;
@@ -389,12 +502,12 @@ int ensure_outputs(ls_tracer *tr)
     if (use_projection(tr)) {   // the fused finish + pack launch's status words: one region per key set
         const size_t cap1 = tr->pack_status_ms.cap;
         if ((rc = ensure(tr, tr->pack_status_ms, 3 * ((nr + 255) / 256 + 8)))) return rc;
-        if (tr->pack_status_ms.cap != cap1) tr->keys_armed = false;   // (fresh memory: initialised with the keys)
+        if (tr->pack_status_ms.cap != cap1) tr->keys_arm[0] = 0;   // (fresh memory: initialised with the keys)
     }
     if ((tr->opt_pipeline || tr->pipe_seq) && use_projection(tr)) {   // twins: needed as long as the rotation may stand on parity 1
         const size_t cap0 = tr->best_keys_b.cap;
         if ((rc = ensure(tr, tr->best_keys_b, nr))) return rc;
-        if (tr->best_keys_b.cap != cap0) tr->keys_b_armed = false;
+        if (tr->best_keys_b.cap != cap0) tr->keys_arm[1] = 0;
         if (!tr->big_queue_b.p && (rc = ensure(tr, tr->big_queue_b, (size_t)tr->big_capacity * ls::project_big_item_bytes()))) return rc;
         if (!tr->ext_points) {
             if ((rc = ensure(tr, tr->points_b, nr * 32))) return rc;
@@ -498,12 +611,13 @@ void frame_graph_free(FrameGraph &fg)
 
 // what decides the SEQUENCE of launches of a frame (their arguments may change from frame to frame: those are patched)
 // (standing_bits: a bit per geometry for "traced from its standing list", route_standing)
-uint64_t frame_signature(const ls_tracer *tr, const std::vector<ls::GeomSource> &srcs, uint64_t standing_bits, uint32_t slot)
+uint64_t frame_signature(const ls_tracer *tr, const std::vector<ls::GeomSource> &srcs, uint64_t standing_bits, bool based, uint32_t slot)
 {
     uint64_t h = 1469598103934665603ull;
     auto mix = [&](uint64_t v) { h = (h ^ v) * 1099511628211ull; };
     mix(tr->fg_bracket ? tr->fg_tag | 1ull : 0ull);
     mix(standing_bits);
+    mix(based ? 1u : 0u);   // (the frame starts from the standing base: no k_project_standing, another pack argument)
     mix(slot);
     mix(tr->V);
     mix(shard_rays(tr) ? 1u : 0u);
@@ -767,7 +881,12 @@ int trace_once(ls_tracer *tr, uint32_t frame, ls_frame *out, bool readback)
             d_n = slot == 1 ? tr->d_n_points_b : tr->d_n_points_c;
         }
         host_targets();
-        if (!tr->keys_armed) {
+        std::vector<ls::GeomSource> &srcs = tr->project_srcs;
+        bool any_culled = false;
+        if ((rc = project_sources(tr, srcs, any_culled))) return rc;
+        uint64_t standing_bits = 0;
+        route_standing(tr, srcs, any_culled, standing_bits, multi && tr->opt_frame_graph && !tr->fg_broken);
+        if (!tr->keys_arm[0]) {
             // first frame (or a new shard / raster): key set 0, all queue counters, the block counts.  In three-
             // stream mode the other streams' frames use those counters too: the initialisation completes first
             ls::launch_project_init(s, pp, tr->best_keys.p, tr->d_big_count, tr->row_counts.p);
@@ -778,9 +897,14 @@ int trace_once(ls_tracer *tr, uint32_t frame, ls_frame *out, bool readback)
                     LS_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(tr->pack_status_ms.p + (size_t)k * (n_blocks + 8u) + n_blocks), 1, 1, s));
             }
             if (multi) LS_HIP(hipStreamSynchronize(s));
-            tr->keys_armed = true;
+            tr->keys_arm[0] = 1;
             tr->frame_parity = 0;
         }
+        // the standing base: kept, built (on the handle's stream, before the frame's own stream takes over) or dropped.  Never for a
+        // frame that goes out as a captured graph or reports its progress -- nor a rider, counting, timing or bracketed one:
+        // route_standing routed nothing for those
+        const unsigned long long *base = nullptr;
+        if ((rc = base_for_frame(tr, pp, !pipelined && !tr->opt_frame_graph && !tr->progress_req && tr->standing_geometries > 0, standing_bits, base))) return rc;
         if (multi) {
             // the frame's stream first sees what is enqueued on the handle's stream: the library's own mesh copies,
             // or anything at all when the stream is the caller's (host API calls are not cheap: only when needed)
@@ -792,25 +916,13 @@ int trace_once(ls_tracer *tr, uint32_t frame, ls_frame *out, bool readback)
             if (dep) LS_HIP(hipStreamWaitEvent(s, tr->ev_main, 0));
             tr->slot_epoch[slot] = tr->main_epoch;
         }
-        if (slot == 1 && !tr->keys_b_armed) {
-            LS_HIP(hipMemsetAsync(tr->best_keys_b.p, 0xFF, (size_t)shard_rays(tr) * 8, s));
-            tr->keys_b_armed = true;
-        }
-        if (slot == 2 && !tr->keys_c_armed) {
-            LS_HIP(hipMemsetAsync(tr->best_keys_c.p, 0xFF, (size_t)shard_rays(tr) * 8, s));
-            tr->keys_c_armed = true;
-        }
+        if ((rc = arm_keys(tr, slot, keys, base ? tr->base.gen : 1u, s))) return rc;
         uint32_t *counts = tr->row_counts.p + (size_t)(multi ? slot : tr->frame_parity) * n_blocks;
         uint32_t *next_counts = tr->row_counts.p + (size_t)(multi ? 3u : 1u - tr->frame_parity) * n_blocks;
         // LS_OPT_TIMING = 2 (the dominant kernel alone): the two events ride on the k_project dispatch
         hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;
         const bool ride = tr->opt_timing == 2;
         mark(tr, 7, ride ? &ev_k0 : nullptr);
-        std::vector<ls::GeomSource> &srcs = tr->project_srcs;
-        bool any_culled = false;
-        if ((rc = project_sources(tr, srcs, any_culled))) return rc;
-        uint64_t standing_bits = 0;
-        route_standing(tr, srcs, any_culled, standing_bits, multi && tr->opt_frame_graph && !tr->fg_broken);
         // survivor list of this frame's k_cull: one of three (as many frames as can be in flight)
         uint32_t *cull_list = nullptr;
         if (any_culled) {
@@ -873,20 +985,23 @@ int trace_once(ls_tracer *tr, uint32_t frame, ls_frame *out, bool readback)
             fa.n_blocks = n_blocks;
             fa.compact = compact;
             fa.cull_hint = nullptr;   // (rider mode re-arms the counters of the frame after the next: nothing to read there)
+            fa.base = nullptr;        // (and the keys to all ones)
             tr->pipe_pending = true;
             ++tr->pipe_seq;
             if (readback && (rc = flush_pipeline(tr))) return rc;
         } else {
             // LS_OPT_FRAME_GRAPH (three-stream mode): the launches below are captured into this slot's graph, or only
             // described and compared with it; either way the frame then goes out as one graph launch
-            if (multi && tr->opt_frame_graph && !tr->fg_broken && (rc = frame_graph_open(tr, slot, s, frame_signature(tr, srcs, standing_bits, slot)))) return rc;
+            if (multi && tr->opt_frame_graph && !tr->fg_broken && (rc = frame_graph_open(tr, slot, s, frame_signature(tr, srcs, standing_bits, base != nullptr, slot)))) return rc;
             // one launch per 16 geometries (the descriptors travel as kernel arguments)
             if (ride) mark(tr, 8, &ev_k1);
             { static const int no_hits = tune_int("LS_PACK_NO_HITS", 0); if (no_hits && !readback) d_hits = nullptr; }   // (experiment: what the 16-byte hit records cost)
             ls::launch_project(s, pp, srcs.data(), (uint32_t)srcs.size(), keys, bigq, tr->big_capacity, big_count, stats, nullptr, cull_list,
                                ev_k0, ev_k1, survivors_hint);
             // the geometries traced from their standing lists: one launch per kGeomsPerLaunch of them, its grid exact
-            for (const ls::StandingBatch &sb : tr->standing_batches) ls::launch_project_standing(s, pp, sb, keys, bigq, tr->big_capacity, big_count);
+            // (none when the frame started from the standing base: the keys hold their minimum already)
+            if (!base)
+                for (const ls::StandingBatch &sb : tr->standing_batches) ls::launch_project_standing(s, pp, sb, keys, bigq, tr->big_capacity, big_count);
             if (!ride) mark(tr, 8);
             // Three-stream mode, a shard of at most kFuseBlocks ray blocks: finish + pack as ONE launch (k_finish_pack: the
             // chained prefix of rider mode; a few hundred workgroups, all resident at once, publish within a microsecond of
@@ -920,6 +1035,7 @@ int trace_once(ls_tracer *tr, uint32_t frame, ls_frame *out, bool readback)
                 fa.n_blocks = n_blocks;
                 fa.compact = compact;
                 fa.cull_hint = any_culled ? hint_word : nullptr;
+                fa.base = base;
                 ls::launch_finish_pack(s, pp, fa, nullptr);
                 mark(tr, 9);
                 mark(tr, 10);
@@ -928,12 +1044,18 @@ int trace_once(ls_tracer *tr, uint32_t frame, ls_frame *out, bool readback)
                 // 15.2 -> 13.4 us per frame with three in flight, 24.3 -> 25.4+ with one -- ls_project.hip, k_project_finish_wide)
                 static const int rpl_env = tune_int("LS_PROJECT_RAYS_PER_LANE", 0);   // (experiment: 1 switches it off)
                 const uint32_t rpl = multi && !progress && !stats ? (rpl_env ? (uint32_t)rpl_env : ls::project_rays_per_lane(n_blocks)) : 1u;
-                ls::launch_project_finish(s, pp, keys, bigq, tr->big_capacity, big_count, counts, stats, rpl);
+                // A frame that started from the base and had nothing left to project: the queue is empty and the keys ARE the base,
+                // whose hits per ray block the build's finish pass left in base.counts -- the pass would only count them again
+                static const int skip_finish = tune_int("LS_BASE_SKIP_FINISH", 1);
+                bool projected = !base || !skip_finish;
+                for (size_t i = 0; i < srcs.size() && !projected; ++i) projected = srcs[i].ntris != 0u;
+                if (projected) ls::launch_project_finish(s, pp, keys, bigq, tr->big_capacity, big_count, counts, stats, rpl);
+                else { counts = tr->base.counts.p; ++tr->base_finish_skipped; }
                 mark(tr, 9);
                 // (a frame that reports its progress sends 8-byte (ray, t) records: ls_trace_scene_expand rebuilds the points)
                 pg.cull_hint = any_culled ? hint_word : nullptr;
                 ls::launch_pack_keys(s, tb, keys, tr->hit_t.p, tr->hit_gid.p, counts, next_counts, big_count, gt, d_points, d_hits, d_n,
-                                     progress ? 2u : compact, &pg, rpl);
+                                     progress ? 2u : compact, &pg, rpl, base);
                 mark(tr, 10);
             }
             if (multi) {
@@ -954,6 +1076,8 @@ int trace_once(ls_tracer *tr, uint32_t frame, ls_frame *out, bool readback)
     } else {
         if (!tr->bvh_built) return fail(tr, LS_ERR_NOT_COMMITTED, "the BVH engine was selected after the last commit");
         tr->standing_geometries = tr->standing_records = 0;   // (LS_INFO_STANDING_*: this frame uses no list)
+        tr->base_in_use = 0;
+        tr->base.same = 0;   // (and is no frame of the projection engine's run of like frames; a base stays, known by its set)
         if ((rc = flush_pipeline(tr))) return rc;
         // the ray queues' heads are zero: the last BVH frame's k_rowcount left them so (a frame that never got that far, or
         // the first one, zeroes them here)
@@ -1026,7 +1150,7 @@ int trace_once(ls_tracer *tr, uint32_t frame, ls_frame *out, bool readback)
         mark(tr, 8);
         ls::launch_rowcount(s, tr->hit_gid.p, shard_rays(tr), tr->row_counts.p, tr->d_queue_heads);
         tr->queue_heads_armed = shard_rays(tr) != 0u;
-        tr->keys_armed = false;  // the counter array was just used with the BVH layout
+        tr->keys_arm[0] = 0;  // the counter array was just used with the BVH layout
         mark(tr, 9);
         const ls::GeomTable gt = geom_table(tr);
         ls::launch_pack(s, tb, tr->hit_t.p, tr->hit_gid.p, tr->row_counts.p, gt, d_points, d_hits, d_n, compact);
