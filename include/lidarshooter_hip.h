@@ -1338,6 +1338,78 @@ int ls_sample_surface_host(ls_tracer *tr, const ls_surface_sample_desc *desc, co
                            const uint8_t *select, uint32_t n_select, void *samples, void *info);
 int ls_surface_sample_check(const ls_surface_sample_desc *desc);   /* host only, no device call */
 
+/* ---- the nearest cloud point to each query, within a radius.  Every query above takes the mesh as its target: ls_closest_points gives
+ * cloud -> mesh, ls_sample_surface draws the points for mesh -> cloud, and this call answers them: which point of a cloud is nearest to
+ * a point, and how far.  It is the other half of a Chamfer distance or an F-score at a threshold (the completeness term: surface
+ * sample -> cloud), of ICP correspondences with a maximum correspondence distance, of associating one frame's returns with the next
+ * frame's, and of spacing and outlier statistics inside one cloud -- on clouds and samples that already sit in device memory in the
+ * library's own record layouts.
+ *   desc:      radius: the search radius, finite, 2^-20 <= radius <= 2^20.  cloud_stride / query_stride: bytes from one point to the
+ *              next, a multiple of 4 in 12 .. 128, with x, y, z as float32 at bytes 0, 4, 8 of every record (only these 12 bytes of a
+ *              record are read) -- so that the 32-byte points of a frame, the 48-byte records of ls_sample_surface, the 32-byte records
+ *              of ls_closest_points (their point leads the record; any other record with the pointer advanced to its point), and packed
+ *              12- or 16-byte xyz go in as they are.
+ *              flags: LS_CLOUD_NEAREST_SKIP_SAME_INDEX -- cloud point i is no candidate for query i: a cloud against itself.
+ *   query_to_cloud3x4: NULL, or a row-major 3 x 4 transform applied to every query first.
+ *   d_cloud:   n_cloud points, 4-byte aligned; may be NULL only when n_cloud == 0.  d_queries: likewise, n_queries points.
+ *   d_out:     n_queries records of 16 bytes, 16-byte aligned; may be NULL only when n_queries == 0.  Every record is written:
+ *              index  u32 @0   the cloud point's index; 0xFFFFFFFF when nothing was found
+ *              dist2  f32 @4   d2 below; +inf when nothing was found
+ *              dist   f32 @8   sqrtf(dist2)
+ *              flags  u32 @12  bit 0 = found; bit 1 = the query was outside the domain
+ *   d_info:    NULL, or 16 bytes, 8-byte aligned: n_found u32 @0 (with radius = tau, F-score's count), n_query_outside u32 @4,
+ *              n_cloud_indexed u32 @8 (the cloud points that take part), one reserved zero word.  Integer counts: the same bytes in
+ *              any order.
+ * The call needs NO committed scene: the handle provides the stream, the scratch, the error text and the call's place among the
+ * frames it has in flight (the cloud will usually be a frame's output).
+ * The definition (csrc/ls_cloud_nearest.h: float32, every operation rounded once, no fmaf):
+ *   1. D = radius * 65536.0f, r2 = radius * radius;
+ *   2. a point takes part iff its three coordinates are finite and each |c| <= D: cloud points and queries alike, a query after the
+ *      transform ((m0 x + m1 y) + m2 z) + m3 per row;
+ *   3. a query that does not take part gets index 0xFFFFFFFF, dist2 = dist = +inf and flags 2;
+ *   4. for a query q and a cloud point p_i that take part: dx = p.x - q.x, dy and dz likewise, d2 = (dx dx + dy dy) + dz dz; i is a
+ *      candidate iff d2 <= r2 and, under SKIP_SAME_INDEX, i is not the query's own index;
+ *   5. the answer is the minimum over the candidates of the 64-bit key (bits(d2) << 32) | i: d2 >= +0, so bit order is value order;
+ *      ties go to the lowest index; a minimum has no order (ls_scene_distance_grid's key);
+ *   6. dist = sqrtf(d2), flags 1.  No candidate: the record of 3 with flags 0;
+ *   7. n_cloud == 0: nothing is a candidate; every query gets the record 3 or 6 gives it without one; LS_OK.
+ * How the candidates are found is not part of the definition.  The library builds a hashed grid of cells of edge radius * 1.015625f
+ * over the cloud, per call, and visits the 27 cells around a query's.  The domain rule of step 2 is what makes that provably complete
+ * in float32: |c| <= 2^16 radius keeps a rounded quotient c / h within 2^-8 of a cell of the true one whatever the radius, the float
+ * test of step 4 admits |dx| no larger than radius (1 + 2^-21), and together these stay inside the 2^-6 by which a cell is wider than
+ * the radius -- so the cells of every pair that passes step 4 differ by at most 1 per axis (the argument in full:
+ * csrc/ls_cloud_nearest.h).  A point beyond 65 536 radii of the origin takes no part instead of being found unreliably.
+ * LS_ERR_INVALID_ARGUMENT before any device call, nothing written, in this order: a frame graph is open; NULL desc; NULL d_out with
+ * n_queries > 0; NULL d_cloud with n_cloud > 0; NULL d_queries with n_queries > 0; unknown flag bits or a non-zero reserved word; a
+ * radius that is not finite or outside [2^-20, 2^20]; a stride that is not a multiple of 4 in 12 .. 128; a non-finite transform;
+ * misaligned pointers for the device call (cloud and queries 4 bytes, out 16, info 8).  Then LS_ERR_OUT_OF_RANGE: n_cloud > 2^27;
+ * n_queries > 2^32 - 256; sort scratch that is too small.  ls_cloud_nearest_check returns the descriptor's part of this (host only,
+ * no device call).  No hierarchy is touched and LS_INFO_RAY_QUERY_BUILT is left as it is; stream order, the one-call-at-a-time rule
+ * and the frame graph rule are those of ls_trace_rays.  The output must not overlap the inputs.  The call keeps 28 bytes per cloud
+ * point, 8 bytes per bucket (2 n_cloud rounded up to a power of two, at least 1024) and the sort's scratch on the handle, released
+ * with the query state.
+ * Not offered: the k nearest; all neighbours within the radius; an unbounded nearest (a radius is what bounds the work per query); an
+ * index kept across calls -- every call sorts the cloud anew, so 2^20 queries in slices of 2^10 pay for the index 2^10 times: pass
+ * the queries in one call --; float sums of distances (the caller reduces `dist`, e.g. with torch); a call of the ITracer adapter. */
+#define LS_CLOUD_NEAREST_SKIP_SAME_INDEX 1u   /* candidate i is skipped for query i: a cloud against itself */
+
+typedef struct ls_cloud_nearest_desc {        /* 32 bytes, no pointers */
+    float    radius;          /* finite, 2^-20 <= radius <= 2^20 */
+    uint32_t flags;
+    uint32_t cloud_stride;    /* bytes from one cloud point to the next: a multiple of 4, 12 .. 128; x, y, z f32 at 0, 4, 8 */
+    uint32_t query_stride;    /* likewise for the queries */
+    uint32_t reserved[4];     /* 0 */
+} ls_cloud_nearest_desc;
+
+int ls_cloud_nearest(ls_tracer *tr, void *hip_stream, const ls_cloud_nearest_desc *desc, const float *query_to_cloud3x4,
+                     const void *d_cloud, uint32_t n_cloud, const void *d_queries, uint32_t n_queries,
+                     void *d_out, void *d_info);
+/* The same with host memory (pageable, any alignment) in and out, on the handle's stream; returns when out and info are filled. */
+int ls_cloud_nearest_host(ls_tracer *tr, const ls_cloud_nearest_desc *desc, const float *query_to_cloud3x4,
+                          const void *cloud, uint32_t n_cloud, const void *queries, uint32_t n_queries,
+                          void *out, void *info);
+int ls_cloud_nearest_check(const ls_cloud_nearest_desc *desc);   /* host only, no device call */
+
 /* ---- clouds in a driver's own PointCloud2 layout.  Every frame call above leaves the same fixed cloud: 32-byte XYZIR records
  * (XYZIRBytes.cpp:24-40), compacted, and next to it the ls_hit records (and, for beams, the echo words).  What a driver publishes
  * differs: Velodyne's 22-byte XYZIRT with a per-point `time` (what LIO-SAM, FAST-LIO and KISS-ICP deskew by), Ouster's organized

@@ -172,6 +172,16 @@ int ls_debug_surface_weights(const float *tris9, uint32_t n, float *area_out, ui
 int ls_debug_surface_pick(const uint64_t *prefix, uint32_t n, uint64_t r64, uint32_t *tri_out);
 int ls_debug_surface_point(const float tri9[9], uint32_t x2, uint32_t x3, float out9[9]);
 
+/* ls_cloud_nearest's index on the host (no device, no handle): the sequences its kernels run (csrc/ls_cloud_nearest.h).
+ * ls_debug_cloud_cell: for n points (xyz: 3 floats each) under `radius`, whether each takes part (takes_part_out[n], 0 / 1) and its
+ * cell (cell_out[3 n]; zeros for a point that does not take part).  LS_ERR_INVALID_ARGUMENT for a radius the call refuses or a NULL
+ * pointer with n > 0.
+ * ls_debug_cloud_bucket: the bucket of a cell in a table of 2^log2_buckets (10 .. 27); 0xFFFFFFFF for a NULL cell or another size.
+ * The tests hold the 27-cell claim against the first and construct hash collisions with the second; no result of the device is ever
+ * compared with either. */
+int ls_debug_cloud_cell(float radius, const float *xyz, uint32_t n, int32_t *cell_out, uint8_t *takes_part_out);
+uint32_t ls_debug_cloud_bucket(const int32_t cell[3], uint32_t log2_buckets);
+
 /* one record of ls_format_cloud on the host (no device, no handle): the operation sequence k_format_cloud runs per record
  * (csrc/ls_cloud_format.h).  point32: the 32-byte point, or NULL (zeros: the format names none of its fields); hit: the ls_hit, or
  * NULL -- the miss cell of cell_ray (an organized cloud's cell nobody fills); echo_word; col_time_value / chan_time_value: the

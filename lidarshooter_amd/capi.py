@@ -68,6 +68,7 @@ SYMBOLS = (
     "ls_scene_grid", "ls_scene_grid_host", "ls_scene_grid_check",
     "ls_scene_distance_grid", "ls_scene_distance_grid_host", "ls_scene_distance_grid_check",
     "ls_sample_surface", "ls_sample_surface_host", "ls_surface_sample_check",
+    "ls_cloud_nearest", "ls_cloud_nearest_host", "ls_cloud_nearest_check",
     "ls_format_cloud", "ls_format_cloud_host", "ls_cloud_format_check", "ls_cloud_format_from_point_fields", "ls_column_times",
 )
 # include/lidarshooter_hip_debug.h: test / measurement hooks (not part of the drop-in surface)
@@ -79,6 +80,7 @@ DEBUG_SYMBOLS = ("ls_debug_dense_hits", "ls_debug_trace_bruteforce", "ls_debug_s
                  "ls_debug_motion_normal", "ls_debug_hit_velocity", "ls_debug_format_record", "ls_debug_voxel_walk", "ls_debug_scene_grid_triangle", "ls_debug_scene_grid_queued",
                  "ls_debug_distance_grid_triangle", "ls_debug_distance_grid_queued",
                  "ls_debug_surface_weights", "ls_debug_surface_pick", "ls_debug_surface_point",
+                 "ls_debug_cloud_cell", "ls_debug_cloud_bucket",
                  "ls_debug_band_map_fit", "ls_debug_band_guess", "ls_debug_tracer_band_map",
                  "ls_debug_force_group_cull", "ls_debug_download_cull", "ls_debug_cull_survivors", "ls_debug_cull_tables", "ls_debug_chan_query")
 # ls_debug_cull_survivors: which k_cull instantiation ran
@@ -289,6 +291,25 @@ class SurfaceSampleDesc(C.Structure):
         return d
 
 
+# ls_cloud_nearest: per query the nearest point of a cloud within a radius; index 0xFFFFFFFF and +inf distances when nothing was found
+# (flags bit 0: found, bit 1: the query was outside the domain); the call's info counts
+LS_CLOUD_NEAREST_SKIP_SAME_INDEX = 1
+CLOUD_NEAREST_DTYPE = np.dtype([("index", "<u4"), ("dist2", "<f4"), ("dist", "<f4"), ("flags", "<u4")])
+CLOUD_NEAREST_INFO_DTYPE = np.dtype([("n_found", "<u4"), ("n_query_outside", "<u4"), ("n_cloud_indexed", "<u4"), ("reserved", "<u4")])
+
+
+class CloudNearestDesc(C.Structure):
+    """ls_cloud_nearest_desc (32 bytes): the radius and the bytes from one point to the next in the cloud and in the queries"""
+    _fields_ = [("radius", C.c_float), ("flags", C.c_uint32), ("cloud_stride", C.c_uint32), ("query_stride", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+    @classmethod
+    def make(cls, radius, cloud_stride=12, query_stride=12, flags=0):
+        d = cls()
+        d.radius, d.flags, d.cloud_stride, d.query_stride = float(radius), int(flags), int(cloud_stride), int(query_stride)
+        return d
+
+
 NODE_DTYPE = np.dtype([("llo", "<f4", 3), ("left", "<u4"), ("lhi", "<f4", 3), ("right", "<u4"),
                        ("rlo", "<f4", 3), ("pad0", "<u4"), ("rhi", "<f4", 3), ("pad1", "<u4")])
 LEAF_BIT = 0x80000000
@@ -455,6 +476,12 @@ def load() -> C.CDLL:
     L.ls_debug_surface_weights.argtypes = [vp, u32, vp, vp, vp, vp]
     L.ls_debug_surface_pick.argtypes = [vp, u32, C.c_uint64, u32p]
     L.ls_debug_surface_point.argtypes = [vp, u32, u32, vp]
+    L.ls_cloud_nearest.argtypes = [vp, vp, C.POINTER(CloudNearestDesc), vp, vp, u32, vp, u32, vp, vp]
+    L.ls_cloud_nearest_host.argtypes = [vp, C.POINTER(CloudNearestDesc), vp, vp, u32, vp, u32, vp, vp]
+    L.ls_cloud_nearest_check.argtypes = [C.POINTER(CloudNearestDesc)]
+    L.ls_debug_cloud_cell.argtypes = [C.c_float, vp, u32, vp, vp]
+    L.ls_debug_cloud_bucket.argtypes = [vp, u32]
+    L.ls_debug_cloud_bucket.restype = u32
     L.ls_debug_hit_velocity.argtypes = [f32p, C.c_float, f32p, f32p, f32p]
     L.ls_format_cloud.argtypes = [vp, vp, C.POINTER(CloudFormat), vp, vp, vp, vp, u32, vp, vp, vp]
     L.ls_format_cloud_host.argtypes = [vp, C.POINTER(CloudFormat), vp, vp, vp, u32, vp, vp, vp]
@@ -1132,6 +1159,38 @@ class Tracer:
         rc = self.L.ls_sample_surface(self.h, stream, C.byref(desc), None if m is None else m.ctypes.data, d_select or None, n_select,
                                       d_samples or None, d_info or None)
         return -1 if rc == -1 else int(self._check(rc, "ls_sample_surface"))
+
+    @staticmethod
+    def _strided_points(a, stride):
+        """an array of whole records of `stride` bytes (any dtype and shape) -> (bytes, record count)"""
+        b = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+        if b.size % int(stride):
+            raise ValueError("the array is not a whole number of records of %d bytes" % stride)
+        return b, b.size // int(stride)
+
+    def cloudNearest(self, desc: CloudNearestDesc, cloud, queries, query_to_cloud=None):
+        """The nearest cloud point to each query within desc.radius (ls_cloud_nearest_host; needs no committed scene): `cloud` and
+        `queries` arrays of whole records of desc.cloud_stride / desc.query_stride bytes with x, y, z float32 at bytes 0, 4, 8 (a
+        float32 (n, 3) array for stride 12, a frame's (n, 32) uint8 points for 32, ...), `query_to_cloud` None or 12 floats
+        (row-major 3 x 4).  -> (rc, records CLOUD_NEAREST_DTYPE[n_queries], info CLOUD_NEAREST_INFO_DTYPE[()])"""
+        c, n_cloud = self._strided_points(cloud, desc.cloud_stride)
+        q, n_queries = self._strided_points(queries, desc.query_stride)
+        out, info = np.zeros(n_queries, CLOUD_NEAREST_DTYPE), np.zeros(1, CLOUD_NEAREST_INFO_DTYPE)
+        m = None if query_to_cloud is None else np.ascontiguousarray(query_to_cloud, np.float32).reshape(12)
+        rc = self.L.ls_cloud_nearest_host(self.h, C.byref(desc), None if m is None else m.ctypes.data, c.ctypes.data if n_cloud else None,
+                                          n_cloud, q.ctypes.data if n_queries else None, n_queries, out.ctypes.data if n_queries else None,
+                                          info.ctypes.data)
+        self._check(rc, "ls_cloud_nearest_host")
+        return int(rc), out, info[0]
+
+    def cloudNearestDevice(self, desc: CloudNearestDesc, d_cloud: int, n_cloud: int, d_queries: int, n_queries: int, d_out: int,
+                           d_info: int = 0, query_to_cloud=None, stream=None) -> int:
+        """ls_cloud_nearest on device pointers (n_queries 16-byte records out, 16-byte aligned, and, with d_info != 0, the 16 bytes of
+        the info); enqueued on `stream` (a hipStream_t as an int, None: the handle's), no wait.  -> 0"""
+        m = None if query_to_cloud is None else np.ascontiguousarray(query_to_cloud, np.float32).reshape(12)
+        rc = self.L.ls_cloud_nearest(self.h, stream, C.byref(desc), None if m is None else m.ctypes.data, d_cloud or None, n_cloud,
+                                     d_queries or None, n_queries, d_out or None, d_info or None)
+        return int(self._check(rc, "ls_cloud_nearest"))
 
     def applyReturnModel(self, model: ReturnModel, hits, rays=None, reflectivity=None, frame_index: int = 0):
         """Sensor returns from hit records (ls_apply_return_model_host): `hits` and `rays` as hitAttributes takes them, `reflectivity`

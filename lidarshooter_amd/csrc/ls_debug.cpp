@@ -14,6 +14,7 @@
 #include "ls_scene_grid.h"
 #include "ls_distance_grid.h"
 #include "ls_surface_sample.h"
+#include "ls_cloud_nearest.h"
 
 #include <algorithm>
 #include <vector>
@@ -480,6 +481,29 @@ int ls_debug_surface_point(const float tri9[9], uint32_t x2, uint32_t x3, float 
     ls::surface_bary(x2, x3, &out9[6], &out9[7], &out9[8]);
     ls::surface_point(tri9, out9[6], out9[7], out9[8], out9);
     return LS_OK;
+}
+
+int ls_debug_cloud_cell(float radius, const float *xyz, uint32_t n, int32_t *cell_out, uint8_t *takes_part_out)
+{
+    if (n && (!xyz || !cell_out || !takes_part_out)) return LS_ERR_INVALID_ARGUMENT;
+    ls_cloud_nearest_desc desc{};
+    desc.radius = radius;
+    desc.cloud_stride = desc.query_stride = 12;
+    if (ls::cloud_nearest_args_invalid(desc, nullptr)) return LS_ERR_INVALID_ARGUMENT;
+    const ls::CloudNearest d = ls::cloud_nearest(desc, nullptr);
+    for (size_t i = 0; i < n; ++i) {
+        const float *p = xyz + 3 * i;
+        const bool part = ls::cloud_takes_part(d.D, p[0], p[1], p[2]);
+        takes_part_out[i] = part ? 1 : 0;
+        for (int a = 0; a < 3; ++a) cell_out[3 * i + a] = part ? ls::cloud_cell(d.h, p[a]) : 0;
+    }
+    return LS_OK;
+}
+
+uint32_t ls_debug_cloud_bucket(const int32_t cell[3], uint32_t log2_buckets)
+{
+    if (!cell || log2_buckets < ls::kCloudMinLog2 || log2_buckets > ls::kCloudMaxLog2) return 0xFFFFFFFFu;
+    return ls::cloud_bucket(cell[0], cell[1], cell[2], (1u << log2_buckets) - 1u);
 }
 
 int ls_debug_format_record(const ls_cloud_format *fmt, const void *point32, const ls_hit *hit, uint32_t echo_word, float col_time_value,

@@ -414,6 +414,11 @@ struct ls_tracer {
         // P[0 .. n_tris] and, behind it, a pair {sum, count} per 256 triangles (one call at a time, as the sweep)
         lsi::DevBuf<uint32_t> surface_area;
         lsi::DevBuf<uint64_t> surface_prefix;
+        // ls_cloud_nearest: the index of one call (ls::CloudIndex) -- three words per cloud point and the count word behind them, a
+        // 16-byte record per point, a pair per bucket; its sort goes through sort_temp (one call at a time, as the sweep)
+        lsi::DevBuf<uint32_t> cloud_words;
+        lsi::DevBuf<uint4> cloud_sorted;
+        lsi::DevBuf<uint2> cloud_range;
         std::vector<RayQuerySlot> built;       // per layout entry
         std::vector<int> layout_ids;           // geometry ids of the layout the slots were made for ...
         std::vector<uint32_t> layout_firsts;   // ... and their first vertex, first triangle in it

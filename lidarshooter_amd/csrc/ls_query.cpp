@@ -223,7 +223,7 @@ void ray_query_release(ls_tracer *tr)
     release(q.sweep_rays); release(q.sweep_hits); release(q.sweep_counts);
     release(q.beam_rays); release(q.beam_hits); release(q.beam_blocks); release(q.beam_counts);
     release(q.cloud_map); release(q.label_acc); release(q.label_rays); release(q.voxel_keys); release(q.scene_queue); release(q.dist_queue);
-    release(q.surface_area); release(q.surface_prefix);
+    release(q.surface_area); release(q.surface_prefix); release(q.cloud_words); release(q.cloud_sorted); release(q.cloud_range);
     if (q.d_maxabs) (void)hipFree(q.d_maxabs);
     if (q.d_counters) (void)hipFree(q.d_counters);
     if (q.ev_ready) (void)hipEventDestroy(q.ev_ready);

@@ -44,8 +44,10 @@ def kernels(asm_path):
 def build(tree, out_dir):
     csrc = os.path.join(tree, "lidarshooter_amd", "csrc")
     res = {}
+    # the translation units: the Makefile's kernel objects (a .hip without one -- ls_standing.hip -- is compiled as part of another)
+    units = set(re.search(r"^KERN_OBJ\s*:=(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).split())
     for fn in sorted(os.listdir(csrc)):
-        if not fn.endswith(".hip"):
+        if not fn.endswith(".hip") or fn[:-4] + ".o" not in units:
             continue
         asm = os.path.join(out_dir, fn + ".s")
         subprocess.check_call([HIPCC, "--offload-arch=gfx950", *FLAGS, "-S", "--cuda-device-only", "-o", asm, os.path.join(csrc, fn)])
